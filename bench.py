@@ -6,8 +6,8 @@ candidate initial trajectories of DESIGN.md section 5.4 hedging the slow instanc
 already resident in HBM.
 
   N = 1   workload = BASELINE.json configs[1]: 1024 instances on the GPU at the PARITY-PRESERVING operating point: candidate 0 (the reference's cold
-          start) runs the reference's 100 iterations, `solver.answers_equal_to_the_reference_path_alone` says for which share of the instances the
-          returned trajectory is bit for bit what the reference path alone returns (or that path fails).  Extra legs measured after the timed region:
+          start) runs the reference's 100 iterations.  With --full, `solver.answers_equal_to_the_reference_path_alone` says for which share of the instances the
+          returned trajectory is bit for bit what the reference path alone returns (or that path fails).  Extra legs measured after the timed region (--full):
           the latency-tuned point with candidate 0 capped at 60 iterations and what its hedges cost in solution quality (`hedged_caps_60`), the
           warm-started cycle, the per-GPU share of
           configs[3] (car-like n=50, B=4096), configs[2] (unicycle n=80, 16 polygons, B=4096) on a placement where clearance rows bind and on one
@@ -16,13 +16,22 @@ already resident in HBM.
           instance at a time, and the CPU baseline.
   N > 1   workload = BASELINE.json configs[3]: 4096 instances per GPU (32768 at N=8), rank r draws its inputs from seed+r; no data-path
           collective inside the timed region.  After it, the per-rank results (status, dt, x -- device resident) are all-gathered over
-          RCCL so that every rank holds the whole job's answer; that exchange is timed separately and reported as `gather_ms`.  The line
-          carries `per_gpu_reference`: rank 0 alone on the same 4096 instances, timed in the same run before the joint timed region.
+          RCCL so that every rank holds the whole job's answer; that exchange is timed separately and reported as `gather_ms`.  With --full
+          the line carries `per_gpu_reference`: rank 0 alone on the same 4096 instances, timed in the same run before the joint timed region.
 
 `value` counts CONVERGED solves only (a Controller::step that returns false makes the planner reset and command zero,
 src/mpc_local_planner_ros.cpp:394-404); `value_all_solves` counts every instance.
 
-Contract: python bench.py --gpus N --steps K --warmup W   (torchrun for N>1) -> ONE JSON line on rank 0.
+A plain run sets up, warms up, times K steps, writes the outputs of the last step (--dump-outputs) and prints the line.  Everything else -- the
+parity check against the reference path alone, the check that the last step reproduces the warm-up step, the measured FMA peaks of the roofline
+block, the extra legs, the CPU baseline and, for N > 1, rank 0's solo reference -- runs only with --full (--no-legs, --no-cpu-baseline and
+--no-parity-check drop parts of it).
+
+--dump-outputs DIR: what the timed path returned in its last step (rank 0's shard for N > 1) as DIR/<name>.npy in float64: x (B, n, 3),
+u (B, n, 2), dt (B,), status (B,), iterations (B,).  The inputs are drawn from fixed seeds, so two builds given the same arguments can be
+compared output for output.  Above 64 MB in all, a fixed seeded sample of instances is written, with their indices in instance_index.npy.
+
+Contract: python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]   (torchrun for N>1) -> ONE JSON line on rank 0.
 """
 from __future__ import annotations
 
@@ -170,6 +179,26 @@ def executed_work(key, kernel_ms, convention_flops_per_launch=None, n_simd=1024,
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES, seed=0):
+    """--dump-outputs: `arrays` (name -> numpy array, leading dimension = instance) as dirname/<name>.npy in float64.  Above `limit` bytes in all, the
+    same fixed seeded sample of instances from every array (rows in ascending order), their indices in instance_index.npy.  Returns the names written."""
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    B = next(iter(arrays.values())).shape[0]
+    per_instance = sum(a[0].nbytes for a in arrays.values())
+    if B * per_instance > limit:
+        keep = max(1, limit // (per_instance + 8))
+        idx = np.sort(np.random.default_rng(seed).choice(B, size=keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["instance_index"] = idx.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), np.ascontiguousarray(a))
+    return sorted(arrays)
+
+
 class Leg:
     """one solver + device-resident inputs/outputs of one workload"""
 
@@ -259,7 +288,12 @@ def main():
     ap.add_argument("--no-parity-check", action="store_true", help="skip the reference-path-alone run behind solver.answers_equal_to_the_reference_path_alone (profiling runs: keeps the kernel statistics of rocprofv3 to the headline launches)")
     ap.add_argument("--force-dist", action="store_true", help="developer check on a one-GPU box: take the N > 1 code path (process group, barriers, RCCL "
                     "all-gather of the results) with a world of one rank")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: parity and reproducibility checks, measured FMA peaks, the extra "
+                    "legs, the CPU baseline, rank 0's solo reference at N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     import torch.distributed as dist
@@ -298,7 +332,7 @@ def main():
     for _ in range(args.warmup):
         leg.step()
     leg.sync()
-    ref_out = (leg.xo.clone(), leg.uo.clone(), leg.do.clone(), leg.st.clone(), leg.it.clone()) if args.warmup > 0 else None
+    ref_out = (leg.xo.clone(), leg.uo.clone(), leg.do.clone(), leg.st.clone(), leg.it.clone()) if args.full and args.warmup > 0 else None
     # The timed region and, for N > 1, everything around it -- rank 0's solo reference (the denominator for scaling efficiency, measured in THIS run: same box, same clocks,
     # same warm-up state), the barriers, the maximum over the ranks, the RCCL all-gather of the results AFTER the timed region and the check that every rank's slice of the
     # gathered arrays is what it computed -- is ONE function that the CPU test suite drives under gloo at world 8 (tests/test_multi_gpu_cpu.py): sharding.run_sharded_job
@@ -315,10 +349,13 @@ def main():
 
         def results(self):
             return leg.st, leg.do, leg.xo
-    job = sharding.run_sharded_job(_Timed(), args.steps, 0, rank, world, B * world, device=dev, solo_reference=True, force_gather=args.force_dist)
-    kernel_ms = kernel_ms[-args.steps:]          # (rank 0's solo reference ran the same steps before the timed ones)
+    job = sharding.run_sharded_job(_Timed(), args.steps, 0, rank, world, B * world, device=dev, solo_reference=args.full, force_gather=args.force_dist)
+    kernel_ms = kernel_ms[-args.steps:]          # (with --full, rank 0's solo reference ran the same steps before the timed ones)
     elapsed, solo_elapsed = job["elapsed"], job["solo_elapsed"]
     sstat, ok = leg.stats()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"x": leg.xo.cpu().numpy(), "u": leg.uo.cpu().numpy(), "dt": leg.do.cpu().numpy(), "status": leg.st.cpu().numpy(),
+                                         "iterations": leg.it.cpu().numpy()})
     reproducible = None
     if ref_out is not None:
         reproducible = bool(all(torch.equal(a_, b_) for a_, b_ in zip(ref_out, (leg.xo, leg.uo, leg.do, leg.st, leg.it))))
@@ -341,7 +378,8 @@ def main():
         achieved_gbs = bytes_per_launch / (k_ms * 1e-3) / 1e9
         flops_per_iter = 914.0 * (n - 1)               # SURVEY.md 8d convention
         from mpc_local_planner_amd import _lib as mlib
-        pk64, pk32 = mlib.measured_fma_peak(local_rank, True), mlib.measured_fma_peak(local_rank, False)
+        # the FMA-rate micro-benchmark takes launches of its own: --full only (without it the measured-peak fields are None)
+        pk64, pk32 = (mlib.measured_fma_peak(local_rank, True), mlib.measured_fma_peak(local_rank, False)) if args.full else (None, None)
         fp64_tf = B * sstat["iters_total_mean"] * flops_per_iter / (k_ms * 1e-3) / 1e12
         fp64_useful_tf = B * sstat["iters_mean"] * flops_per_iter / (k_ms * 1e-3) / 1e12
         ex_h = executed_work(f"carlike_n{n}_B{B}_c{len(kinds)}", k_ms, B * sstat["iters_total_mean"] * flops_per_iter)
@@ -395,7 +433,7 @@ def main():
     # reference's 100 iterations).  An instance counts as "equal" when the reference path converges and the headline returns candidate 0's trajectory,
     # bit for bit the reference path's, or when the reference path does not converge (then a hedge may answer).
     st_r = dt_r = None
-    if len(kinds) > 1 and not args.no_parity_check:
+    if args.full and len(kinds) > 1 and not args.no_parity_check:
         win_h, _ = leg.solver.last_candidates(B)
         lr = Leg(m, torch, dev, m.config_carlike_min_time(n=n), B, m.workloads.carlike_min_time_inputs(B, seed=sharding.rank_seed(m.workloads.SEED_CONFIG2, rank)))
         lr.step(); lr.sync()
@@ -410,8 +448,8 @@ def main():
                                              "exactly its trajectory (bit for bit), hedges answer only instances it leaves unsolved" % caps[0])
         lr.close()
 
-    # ---- extra legs (N = 1 only; after the timed region)
-    if not multi and not args.no_legs:
+    # ---- extra legs (--full, N = 1 only; after the timed region)
+    if args.full and not multi and not args.no_legs:
         legs = {}
         if len(kinds) > 1 and st_r is not None:
             # the latency-tuned operating point of rounds 2/3: candidate 0 capped at 60 iterations.  Faster, but instances the reference path would still
@@ -627,7 +665,7 @@ def main():
                                      "note": "bench.py --gpus N>1 runs configs[3] (4096 instances per GPU); its per-GPU reference on one GPU is this leg, not the N=1 headline (1024 instances)"}
     else:
         leg.close()
-    if rank == 0 and not args.no_cpu_baseline and not multi:
+    if args.full and rank == 0 and not args.no_cpu_baseline and not multi:
         line["cpu_baseline"] = cpu_baseline(n)
     if multi:
         dist.destroy_process_group()

@@ -33,6 +33,29 @@ def test_executed_work_from_the_committed_counter_pass():
     assert t is not None and 4.0e6 < t < 1.0e7          # 2 x FETCH_SIZE + WRITE_SIZE of the headline launch: ~1.5 x the 4.15 MB of algorithmic bytes
 
 
+def test_dump_outputs_writes_float_arrays_and_samples_above_the_limit(tmp_path):
+    import numpy as np
+    b = _bench()
+    B, n = 64, 5
+    rng = np.random.default_rng(3)
+    arrays = {"x": rng.standard_normal((B, n, 3)), "u": rng.standard_normal((B, n, 2)), "dt": rng.standard_normal(B),
+              "status": rng.integers(-2, 1, B).astype(np.int32), "iterations": rng.integers(5, 100, B).astype(np.int32)}
+    assert b.dump_outputs(str(tmp_path / "all"), arrays) == ["dt", "iterations", "status", "u", "x"]
+    for k, a in arrays.items():
+        d = np.load(tmp_path / "all" / (k + ".npy"))
+        assert d.dtype == np.float64 and np.array_equal(d, a)
+    per = (5 * n + 3) * 8
+    names = b.dump_outputs(str(tmp_path / "part"), arrays, limit=20 * per)
+    again = b.dump_outputs(str(tmp_path / "again"), arrays, limit=20 * per)
+    assert names == again and "instance_index" in names
+    idx = np.load(tmp_path / "part" / "instance_index.npy")
+    assert np.array_equal(idx, np.load(tmp_path / "again" / "instance_index.npy")) and np.all(np.diff(idx) > 0)
+    total = sum(os.path.getsize(tmp_path / "part" / (k + ".npy")) - 128 for k in names)          # (128-byte .npy headers)
+    assert 0 < len(idx) < B and total <= 20 * per
+    for k, a in arrays.items():
+        assert np.array_equal(np.load(tmp_path / "part" / (k + ".npy")), a[idx.astype(int)])
+
+
 def test_committed_bench_line_keeps_the_contract():
     line = json.loads(open(os.path.join(ROOT, "profiles", "r06_bench.json")).read().strip().splitlines()[-1])
     base = json.load(open(os.path.join(ROOT, "BASELINE.json")))

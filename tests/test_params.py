@@ -213,10 +213,22 @@ def test_wrong_typed_values_keep_the_default_like_roscpp():
 REF = "/root/reference"
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree is only present in the build container")
-def test_the_references_own_parameter_files_load():
-    """the four parameter files the reference ships; BASELINE.json's configs 1 and 2 are the quadratic-form and the car-like file with n overridden"""
-    ex = os.path.join(REF, "mpc_local_planner_examples", "cfg")
+def test_the_references_own_parameter_files_load(tmp_path):
+    """the four parameter files the reference ships; BASELINE.json's configs 1 and 2 are the quadratic-form and the car-like file with n overridden.  Their parameter
+    trees are recorded in tests/golden/reference_param_files.json (generator: tests/golden/make_reference_params.py) and written back to YAML files here; where the
+    reference tree is present, the recording must still be what its files hold."""
+    import json
+    import yaml
+    rec = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_param_files.json")))["files"]
+    assert len(rec) == 4
+    for rel, tree in rec.items():
+        if os.path.isdir(REF):
+            with open(os.path.join(REF, rel)) as f:
+                assert (yaml.safe_load(f) or {}) == tree, rel
+        os.makedirs(os.path.dirname(str(tmp_path / rel)), exist_ok=True)
+        with open(tmp_path / rel, "w") as f:
+            yaml.safe_dump(tree, f)
+    ex = os.path.join(str(tmp_path), "mpc_local_planner_examples", "cfg")
     car, _, _ = P.config_from_yaml(os.path.join(ex, "carlike", "mpc_local_planner_params.yaml"))
     ours = m.config_carlike_min_time(n=20)
     for name in ("model", "n", "dt_ref", "dt_free", "dt_lb", "dt_ub", "objective", "collocation"):
@@ -235,7 +247,7 @@ def test_the_references_own_parameter_files_load():
     assert ctrl["grid_adaptation"] is False
     mt, ctrl, _ = P.config_from_yaml(os.path.join(ex, "diff_drive", "mpc_local_planner_params_minimum_time.yaml"))
     assert mt.objective == A.OBJ_MIN_TIME and ctrl["outer_ocp_iterations"] == 5 and mt.hessian_mode == P.HESSIAN_EXACT
-    node, ctrl, _ = P.config_from_yaml(os.path.join(REF, "mpc_local_planner", "cfg", "test_mpc_optim_node.yaml"), namespace=None)
+    node, ctrl, _ = P.config_from_yaml(os.path.join(str(tmp_path), "mpc_local_planner", "cfg", "test_mpc_optim_node.yaml"), namespace=None)
     assert node.model == A.MODEL_UNICYCLE and node.n == 20 and node.has_Qf == 1 and list(node.xf_fixed) == [1, 1, 1] and ctrl["publish_ocp_results"]
 
 

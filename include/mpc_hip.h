@@ -91,7 +91,8 @@ enum mpc_stage_data {                 /* mpc_config.stage_data */
     MPC_STAGE_AUTO = 0,               /* decided per handle and precision at mpc_create.  fp64: global memory when the LDS form leaves at least half of a CU's SIMDs without a wave and
                                        * the global form fills more of them (bit-identical results either way).  Plain fp32: already when the LDS form leaves one of four empty --
                                        * there the two forms agree to rounding only, so an fp32 handle reproduces itself run to run but not the results of library versions
-                                       * before 0.5.0 (which kept fp32 in LDS).  Both phases of MPC_MIXED keep the LDS form */
+                                       * before 0.5.0 (which kept fp32 in LDS).  MPC_MIXED: its fp32 phase follows the fp64
+                                       * rule (global memory from about n = 140 on), its fp64 refinement phase keeps the LDS form (mpc_launch_plan.hpp) */
     MPC_STAGE_LDS = 1,                /* the whole working set of an instance in LDS (97 words per grid point) */
     MPC_STAGE_GLOBAL = 2              /* stage records and gains in a per-workgroup block of global memory (L2 / Infinity-Cache resident), 34 words per grid point in LDS;
                                        * every kernel level (r06: the extended terms too -- terminal ball, via-points, turning footprints, dynamic obstacles, cost variants) */
@@ -217,9 +218,9 @@ typedef struct mpc_config {
                                        * working memory is Ipopt's) */
     int32_t two_wave_min_batch;       /* launches with at least this many instances run the kernel variant for TWO resident waves per SIMD (236 registers, no scratch; fp64, headline
                                        * kernel level without clearance rows, and only where the LDS record fits eight times into a compute unit: about n <= 24 grid points -- the
-                                       * grid sizes of the reference's shipped parameter files).  0 -> the default 4096 (measured on the MI355X for n = 12 / 20 / 24: x1.03 / x1.0 / x1.3 there, x1.06 / x1.4 / x1.37
-                                       * at 8192, x1.46 / x1.64 / x1.6 at 32768 instances; below the threshold n = 12 loses -- x0.83 at 2048 -- and n = 20 / 24 gain x1.13 / x1.29: a small
-                                       * launch lasts as long as its slowest wave, which runs fastest alone); negative -> never.  Results are bit-identical either way.  No counterpart in the reference */
+                                       * grid sizes of the reference's shipped parameter files).  0 -> the default 4096 (a smaller launch lasts as long as its slowest wave, which
+                                       * runs fastest alone; measurements: DESIGN.md 5.1, profiles/r06_w2_probe.log); negative -> never.  Results are bit-identical either way.
+                                       * No counterpart in the reference */
     int32_t line_search;              /* enum mpc_line_search (solver/ipopt/ipopt_string_options/line_search_method) */
     /* full weight matrices (state_weights / control_weights / final_state_weights / weight_matrix given as n x n lists, column major,
      * src/controller.cpp:565-573,580-588,656-664,690-698): Q, R, Qf, terminal_ball_S above hold the DIAGONALS, these the off-diagonal terms
@@ -409,7 +410,7 @@ int mpc_synchronize(mpc_solver* s);
  * HIP events on the solver's own stream (call after mpc_synchronize). */
 int mpc_last_kernel_ms(mpc_solver* s, float* ms);
 
-/* Dynamic LDS bytes of one workgroup of the solve kernel for this handle = the working set of ONE planner instance that lives in LDS (mpc_wave_layout.hpp::WaveLayout + the
+/* Dynamic LDS bytes of one workgroup of the solve kernel for this handle = the working set of ONE planner instance that lives in LDS (mpc_layout.hpp::WaveLayout + the
  * problem record; with mpc_config.stage_data in the global form the factorisation data is not part of it).  A compute unit of the MI355X has 160 KB and its register file
  * holds four of these one-wave workgroups: min(4, 163840 / bytes) are resident per CU -- 4 at BASELINE configs[1] (n = 50, fp64: 40 128 B), 4 at configs[2] (n = 80, 16 polygons,
  * four clearance rows per grid point: 33 200 B in the global form MPC_STAGE_AUTO picks; 83 760 B = 1 per CU in the LDS form), 4 at configs[4]'s shape in fp64 (n = 120: 34 928 B;

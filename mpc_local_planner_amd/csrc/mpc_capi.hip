@@ -12,6 +12,7 @@
 #include "../../include/mpc_hip.h"
 #include "mpc_core.hpp"
 #include "mpc_problem.hpp"
+#include "mpc_launch_plan.hpp"
 #include "mpc_wave.hpp"
 #include "mpc_solve_kernel.hpp"
 #include "mpc_costmap.hpp"
@@ -39,18 +40,10 @@ struct mpc_solver {
     mpc_config cfg;
     mpc::Problem<double> P64;
     mpc::Problem<float> P32;
-    mpc::WaveLayout WL;         // everything in LDS
-    mpc::WaveLayout WLg;        // factorisation data (GAIN, STG) in global memory (mpc_wave.hpp::GlobalStage): the LDS record is a third
-    bool w2_gs;                 // (developer builds) the two-wave kernel in the global form
-    bool w2_ok;                 // fp64 launches with more instances than the device has SIMDs may take the two-waves-per-SIMD kernel (global form, <= 256 registers): decided per launch (launch_model)
-    size_t wave_lds_w2;         // its dynamic LDS
-    int w2_min_batch;           // from this many instances per launch on
-    bool gs64, gs32;            // which of the two the fp64 / fp32 launches of this handle use (mpc_config.stage_data; MPC_STAGE_AUTO: the one that puts more workgroups on a CU)
-    void* d_gstage;             // n_gslots blocks of factorisation data (WLg.GSW words each), NULL when neither precision uses them
-    int* d_gslots;              // [n_gslots] claim words of the blocks (0 = free)
+    mpc::LaunchPlan plan;       // which kernel each launch runs (mpc_launch_plan.hpp)
+    void* d_gstage;             // 8 pools of n_gslots blocks (plan.block_bytes each), NULL when the plan has none
+    int* d_gslots;              // [8][n_gslots] claim words of the blocks (0 = free)
     int n_gslots;
-    size_t wave_lds;            // dynamic LDS of the kernel instantiation of cfg.precision (MPC_MIXED: the fp64 one, the larger)
-    size_t wave_lds32;          // MPC_MIXED: dynamic LDS of the fp32 phase
     int32_t* d_iters1;          // MPC_MIXED: iterations of the fp32 phase
     int device;
     int max_batch;
@@ -82,25 +75,18 @@ struct mpc_solver {
     bool timed;
 };
 
-// which kernel instantiation serves this solver: the one with the rarely used rows / terms / coupling slots, or the headline one
-static bool solver_ext(const mpc_solver* s) {
-    const mpc::Problem<double>& P = s->P64;
-    return P.ball || P.via || P.integral_form || P.dyn_obst || P.hess_mode || P.costx ||
-           (P.n_obst > 0 && (P.footprint_kind == MPC_FOOTPRINT_LINE || P.footprint_kind == MPC_FOOTPRINT_TWO_CIRCLES || P.footprint_kind == MPC_FOOTPRINT_POLYGON));
-}
-
 // which XCC ids the device's workgroups run on (bit i of *mask: some workgroup saw HW_REG_XCC_ID & 7 == i): 8 bits on an MI355X, 1 in a partitioned mode
 namespace mpc {
 __global__ void xcc_probe_kernel(unsigned* mask) {
     if (threadIdx.x == 0) atomicOr(mask, 1u << ((unsigned)__builtin_amdgcn_s_getreg((3 << 11) | 20) & 7u));
 }
 }  // namespace mpc
-// resident workgroups per CU of the solve kernel a launch record selects (per precision and model: the instantiations live in mpc_solve_inst.hip)
-static hipError_t pool_kernel_occupancy(bool f32, int model, const mpc::SolveLaunch& a, int* out) {
+// resident workgroups per CU of the solve kernel that serves a kernel choice (per precision and model: the instantiations live in mpc_solve_inst.hip)
+static hipError_t kernel_occupancy(bool f32, int model, const mpc::KernelChoice& k, int* out) {
 #ifdef MPC_DEV_ONE_MODEL
-    (void)model; return f32 ? hipErrorInvalidConfiguration : mpc::solve_occupancy<double, MPC_DEV_ONE_MODEL>(a, out);
+    (void)model; return f32 ? hipErrorInvalidConfiguration : mpc::solve_occupancy<double, MPC_DEV_ONE_MODEL>(k, out);
 #else
-#define MPC_OCC(M) (f32 ? mpc::solve_occupancy<float, M>(a, out) : mpc::solve_occupancy<double, M>(a, out))
+#define MPC_OCC(M) (f32 ? mpc::solve_occupancy<float, M>(k, out) : mpc::solve_occupancy<double, M>(k, out))
     switch (model) {
         case MPC_MODEL_UNICYCLE: return MPC_OCC(mpc::MODEL_UNICYCLE);
         case MPC_MODEL_SIMPLE_CAR: return MPC_OCC(mpc::MODEL_SIMPLE_CAR);
@@ -174,41 +160,7 @@ int mpc_create(const mpc_config* cfg, int32_t max_batch, int32_t device, mpc_sol
     g_err[0] = 0;
     if (!cfg || !out || max_batch <= 0) { set_err("mpc_create: bad argument"); return MPC_EINVAL; }
     *out = nullptr;
-    if (cfg->n < 3 || cfg->n > 4096) { set_err("mpc_create: n out of range [3,4096]"); return MPC_EINVAL; }
-    if (cfg->model < 0 || cfg->model > 3) { set_err("mpc_create: unknown model"); return MPC_EINVAL; }
-    if (cfg->collocation != MPC_COLLOC_FORWARD && cfg->collocation != MPC_COLLOC_MIDPOINT && cfg->collocation != MPC_COLLOC_CRANK_NICOLSON) {
-        set_err("mpc_create: unknown collocation method"); return MPC_EINVAL; }
-    if (cfg->objective != MPC_OBJ_MIN_TIME && cfg->objective != MPC_OBJ_QUADRATIC && cfg->objective != MPC_OBJ_MIN_TIME_VIA_POINTS) { set_err("mpc_create: unknown objective"); return MPC_EINVAL; }
-    if (cfg->objective == MPC_OBJ_MIN_TIME_VIA_POINTS && (cfg->max_via_points < 1 || cfg->max_via_points > 64)) {
-        set_err("mpc_create: minimum_time_via_points needs 1 <= max_via_points <= 64"); return MPC_EINVAL; }
-    if (cfg->objective != MPC_OBJ_QUADRATIC && !cfg->dt_free) { set_err("mpc_create: minimum_time needs a variable grid (dt_free)"); return MPC_EINVAL; }
-    if (!(cfg->dt_ref > 0)) { set_err("mpc_create: dt_ref must be > 0"); return MPC_EINVAL; }
-    if (cfg->max_obstacles < 0 || cfg->max_obstacles > 4096 || (cfg->max_obstacles > 0 && (cfg->max_vertices < 1 || cfg->max_vertices > 64)) || cfg->max_obstacle_rows > 16) {
-        set_err("mpc_create: obstacle capacities out of range (max_obstacles <= 4096, max_vertices <= 64, max_obstacle_rows <= 16)"); return MPC_EINVAL; }
-    if (cfg->max_obstacles > 0 && cfg->footprint_kind != MPC_FOOTPRINT_POINT && cfg->footprint_kind != MPC_FOOTPRINT_CIRCLE && cfg->footprint_kind != MPC_FOOTPRINT_LINE &&
-        cfg->footprint_kind != MPC_FOOTPRINT_TWO_CIRCLES && cfg->footprint_kind != MPC_FOOTPRINT_POLYGON) {
-        set_err("mpc_create: unknown footprint model"); return MPC_EINVAL; }
-    if (cfg->max_obstacles > 0 && cfg->footprint_kind == MPC_FOOTPRINT_POLYGON && (cfg->footprint_n_vertices < 1 || cfg->footprint_n_vertices > 16)) {
-        set_err("mpc_create: the polygon footprint needs 1..16 vertices"); return MPC_EINVAL; }
-    for (int j = 0; j < 2; ++j)
-        if (!(cfg->u_lb[j] < cfg->u_ub[j])) { set_err("mpc_create: control box must be finite and non-empty"); return MPC_EINVAL; }
-    if (cfg->precision != MPC_FP64 && cfg->precision != MPC_FP32 && cfg->precision != MPC_MIXED) { set_err("mpc_create: unknown precision"); return MPC_EINVAL; }
-    if (cfg->cost_integration != MPC_COST_LEFT_SUM && cfg->cost_integration != MPC_COST_TRAPEZOIDAL) { set_err("mpc_create: unknown cost_integration"); return MPC_EINVAL; }
-    if (cfg->hybrid_cost_minimum_time && cfg->objective != MPC_OBJ_QUADRATIC) { set_err("mpc_create: hybrid_cost_minimum_time belongs to the quadratic_form objective"); return MPC_EINVAL; }
-    if (cfg->n_candidates == 1 && cfg->candidate_kind[0] != MPC_CAND_REFERENCE) {
-        set_err("mpc_create: a single candidate must be MPC_CAND_REFERENCE (other kinds only run as hedges next to it: n_candidates >= 2)"); return MPC_EINVAL; }
-    if (cfg->precision == MPC_MIXED && (cfg->max_obstacles > 0 || cfg->objective == MPC_OBJ_MIN_TIME_VIA_POINTS)) {
-        set_err("mpc_create: MPC_MIXED is implemented for problems without clearance rows and via-points (their association would be redone by the refinement phase)"); return MPC_EINVAL; }
-    if (cfg->hessian_mode != MPC_HESSIAN_EXACT && cfg->hessian_mode != MPC_HESSIAN_CONVEXIFIED) { set_err("mpc_create: unknown hessian_mode"); return MPC_EINVAL; }
-    if (cfg->mu_strategy != MPC_MU_ADAPTIVE && cfg->mu_strategy != MPC_MU_MONOTONE) { set_err("mpc_create: unknown mu_strategy"); return MPC_EINVAL; }
-    if (cfg->line_search != MPC_LS_DEFAULT && cfg->line_search != MPC_LS_MERIT && cfg->line_search != MPC_LS_FILTER) { set_err("mpc_create: unknown line_search"); return MPC_EINVAL; }
-    if (cfg->max_time_us < 0) { set_err("mpc_create: max_time_us must be >= 0 (0 = no budget)"); return MPC_EINVAL; }
-    if (cfg->n_candidates < 0 || cfg->n_candidates > MPC_MAX_CANDIDATES) { set_err("mpc_create: n_candidates must be in [0, MPC_MAX_CANDIDATES]"); return MPC_EINVAL; }
-    for (int k = 0; k < cfg->n_candidates; ++k)
-        if (cfg->candidate_kind[k] < MPC_CAND_REFERENCE || cfg->candidate_kind[k] > MPC_CAND_HERMITE_RF || cfg->candidate_max_iter[k] < 0) {
-            set_err("mpc_create: unknown candidate kind or negative candidate_max_iter"); return MPC_EINVAL; }
-    if (cfg->dt_free && !(cfg->dt_lb < cfg->dt_ub)) { set_err("mpc_create: dt_lb must be below dt_ub on the variable grid"); return MPC_EINVAL; }
-    if (cfg->dt_free && !(cfg->dt_ref >= cfg->dt_lb && cfg->dt_ref <= cfg->dt_ub)) { set_err("mpc_create: dt_ref must lie in [dt_lb, dt_ub] on the variable grid"); return MPC_EINVAL; }
+    if (const char* why = mpc::config_error(*cfg)) { set_err(why); return MPC_EINVAL; }
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev <= 0) {
@@ -217,10 +169,13 @@ int mpc_create(const mpc_config* cfg, int32_t max_batch, int32_t device, mpc_sol
     }
     if (device < 0 || device >= ndev) { set_err("mpc_create: device index out of range"); return MPC_ENODEV; }
     HIP_TRY(hipSetDevice(device));
+    const mpc::LaunchPlan plan = mpc::make_launch_plan(*cfg);
+    if (const char* why = mpc::plan_error(plan)) { set_err(why); return MPC_EINVAL; }
     mpc_solver* s = new (std::nothrow) mpc_solver;
     if (!s) return MPC_ENOMEM;
     memset(s, 0, sizeof(*s));
     s->cfg = *cfg;
+    s->plan = plan;
     mpc::fill_problem<double>(*cfg, s->P64);
     mpc::fill_problem<float>(*cfg, s->P32);
 #ifdef MPC_DEV_SWITCHES      // developer A/B switches read from the environment: compiled out of the shipped library
@@ -232,80 +187,9 @@ int mpc_create(const mpc_config* cfg, int32_t max_batch, int32_t device, mpc_sol
         s->P64.n_cand = 1;                                   // phase 2 refines the winner
         if (!(cfg->mu_init_dual > 0)) s->P64.mu_init_dual = 1e-5;      // phase 1 ended at a barrier of ~1e-5
         s->P64.mu_init_warm = 1e-3;                          // instances phase 1 did not converge start phase 2 from its last iterate
-        s->P64.mu_strategy = 1;                              // the refinement follows the central path from mu = 1e-5 down: the monotone rule (measured: 4.2 refinement
-                                                             // iterations against 9.4 with the adaptive one, which re-derives mu from the fp32 iterate's complementarity)
+        s->P64.mu_strategy = 1;                              // the refinement follows the central path from mu = 1e-5 down: the monotone rule (fewer refinement iterations than
+                                                             // the adaptive one, which re-derives mu from the fp32 iterate's complementarity: CHANGELOG.md)
         if (s->P64.max_iter > 40) s->P64.max_iter = 40;      // a refinement that needs more than that is a solve of its own (phase-1 failures would hold the launch for 100)
-    }
-    {
-        const int O = cfg->max_obstacles > 0 ? cfg->max_obstacles : 0;
-        const int M = O > 0 ? (cfg->max_obstacle_rows > 0 ? cfg->max_obstacle_rows : 4) : 0;
-        const int ntrig = ((cfg->model == MPC_MODEL_KINEMATIC_BICYCLE || cfg->model == MPC_MODEL_SIMPLE_CAR_FRONT) ? 4 : 3) +
-                          (cfg->collocation == MPC_COLLOC_CRANK_NICOLSON ? 2 : 0);
-        auto layout = [&](bool gs) {
-            return mpc::WaveLayout::make(cfg->n, M, O, cfg->max_vertices > 0 ? cfg->max_vertices : 1, ntrig, s->P64.n_via,
-                                         (O > 0 && (cfg->footprint_kind == MPC_FOOTPRINT_LINE || cfg->footprint_kind == MPC_FOOTPRINT_TWO_CIRCLES ||
-                                                    cfg->footprint_kind == MPC_FOOTPRINT_POLYGON || cfg->enable_dynamic_obstacles)) ? M : 0,
-                                         (O > 0 && cfg->enable_dynamic_obstacles) ? O : 0, solver_ext(s) ? mpc::NSTG_EXT : mpc::NSTG_BASE,
-                                         (O > 0 && cfg->enable_dynamic_obstacles && (cfg->footprint_kind == MPC_FOOTPRINT_LINE || cfg->footprint_kind == MPC_FOOTPRINT_TWO_CIRCLES ||
-                                                                                      cfg->footprint_kind == MPC_FOOTPRINT_POLYGON)) ? M : 0,
-                                         cfg->precision == MPC_FP32 ? 4 : 8, gs);      // (MPC_MIXED has no clearance rows: both of its phases see the same layout)
-        };
-        s->WL = layout(false);
-        s->WLg = layout(true);
-    }
-    auto lds_of = [](const mpc::WaveLayout& L, size_t tsize, size_t psize) { return ((((size_t)L.total * tsize) + 15) & ~(size_t)15) + 16 + ((psize + 15) & ~(size_t)15); };
-    // Where the factorisation data lives, per precision (MPC_STAGE_AUTO).  The register file holds these kernels at one wave per SIMD, so a CU has room for four workgroups; an
-    // LDS record that fits fewer than four times leaves SIMDs without a wave.  Measured on the MI355X (profiles/r05_stage_data_probe.log): at EQUAL residency the global form
-    // costs 24 % per iteration at n = 50 and ~5 % at n = 80 / 120; it pays x2.2 - x2.8 at n = 120 in fp64 (1 -> 4 workgroups per CU) and x1.3 - x1.5 from residency alone at n = 80
-    // with 16 polygons.  The rule, stated once (also in include/mpc_hip.h): fp64 takes the global form when the LDS form leaves at least HALF of a CU's SIMDs empty and the global
-    // form fills more of them; plain fp32 already when the LDS form leaves ONE of four empty (n = 120: 7.06 -> 6.43 ms since the block is laid out in tiles) -- in fp32 the two
-    // forms agree to rounding, not bit for bit (the compiler contracts / packs the fp32 lane-parallel passes differently around global loads), so an fp32 handle under
-    // MPC_STAGE_AUTO reproduces itself run to run but not the results of builds before 0.5.0; both phases of MPC_MIXED keep the LDS form.  Every kernel level exists in both forms (r06: the extended levels too).
-    {
-        const bool can_gs = true;      // (r06: every kernel level exists in the global form)
-        auto per_cu = [](size_t lds) { const size_t k = (160u * 1024u) / lds; return k > 4 ? (size_t)4 : k; };
-        auto choose = [&](size_t tsize, size_t psize) {
-            if (!can_gs || cfg->stage_data == MPC_STAGE_LDS) return false;
-            if (cfg->stage_data == MPC_STAGE_GLOBAL) return true;
-            const size_t a = lds_of(s->WL, tsize, psize), g = lds_of(s->WLg, tsize, psize);
-            if (a > 160u * 1024u) return g <= 160u * 1024u;           // only the global form fits at all
-            // (plain fp32: 3 -> 4 workgroups per CU at n = 120 measured 10 % faster since the block is laid out in tiles -- 7.06 -> 6.43 ms; the two forms agree to rounding there, not
-            //  bit for bit.  Not the fp32 phase of MPC_MIXED: 9.06 -> 9.88 ms for both phases, the hand-off between the forms costs more than the phase gains)
-            return per_cu(a) <= ((tsize == 4 && cfg->precision == MPC_FP32) ? 3u : 2u) && per_cu(g) > per_cu(a);
-        };
-        if (cfg->stage_data != MPC_STAGE_AUTO && cfg->stage_data != MPC_STAGE_LDS && cfg->stage_data != MPC_STAGE_GLOBAL) { set_err("mpc_create: unknown stage_data"); delete s; return MPC_EINVAL; }
-        s->gs32 = cfg->precision != MPC_FP64 && choose(4, sizeof(mpc::Problem<float>));
-        // (the refinement phase of MPC_MIXED -- one candidate, a handful of iterations -- measured faster in the LDS form: 9.0 against 9.4 ms for both phases at n = 120, B = 1024)
-        s->gs64 = cfg->precision != MPC_FP32 && (cfg->precision != MPC_MIXED || cfg->stage_data == MPC_STAGE_GLOBAL) && choose(8, sizeof(mpc::Problem<double>));
-    }
-    // Two waves per SIMD (mpc_solve_kernel.hpp, W2): the fp64 headline level without clearance rows, when the LDS record fits eight times into a CU (everything in LDS: about
-    // n <= 24 grid points -- the grid sizes of the reference's shipped parameter files).  A launch takes it when it has at least w2_min_batch instances (the device then has waves
-    // waiting for a SIMD, and a second resident wave fills the issue slots the first leaves idle); below that a launch lasts as long as its slowest wave, which runs fastest
-    // alone.  Same arithmetic on the same numbers: results bit for bit those of the one-wave kernels.  (With the factorisation data in global memory the second wave buys
-    // nothing -- measured at n = 50, profiles/r06_w2_probe.log: the form's cost is the CU's vector-memory path, which eight waves share --, so grids whose LDS form does not fit
-    // eight times keep the one-wave kernels.)
-    s->w2_gs = false;
-    s->wave_lds_w2 = lds_of(s->WL, 8, sizeof(mpc::Problem<double>));
-    s->w2_ok = cfg->precision == MPC_FP64 && cfg->stage_data == MPC_STAGE_AUTO && !solver_ext(s) && cfg->max_obstacles <= 0 && s->wave_lds_w2 <= (160u * 1024u) / 8u;
-    s->w2_min_batch = cfg->two_wave_min_batch > 0 ? cfg->two_wave_min_batch : 4096;      // (measured under the filter line search, profiles/r06_w2_probe.log, n = 12 / 20 / 24: x1.03 / x1.00-1.02 / x1.30-1.34 there, x1.06 / x1.4 / x1.37 at 8192, x1.46 / x1.64 / x1.6 at 32768; below: x0.83 / x1.13 / x1.29 at 2048, x0.81 / x1.02 / x1.02 at 1024 -- a small launch lasts as long as its slowest wave, which runs fastest alone)
-    if (cfg->two_wave_min_batch < 0) s->w2_ok = false;
-#ifdef MPC_DEV_SWITCHES
-    if (const char* e = getenv("MPC_W2_FORCE")) {      // developer A/B: the 256-register kernel variant whatever the record's size (LDS form)
-        if (e[0] == '1' && cfg->two_wave_min_batch >= 0 && cfg->precision == MPC_FP64 && !solver_ext(s) && cfg->max_obstacles <= 0) { s->w2_ok = true; s->w2_gs = false; s->wave_lds_w2 = lds_of(s->WL, 8, sizeof(mpc::Problem<double>)); }
-    }
-    if (const char* e = getenv("MPC_W2_GS")) {      // developer A/B: the two-wave kernel in the global form where the LDS form does not fit eight times
-        if (e[0] == '1' && !s->w2_ok && cfg->two_wave_min_batch >= 0 && cfg->precision == MPC_FP64 && cfg->stage_data == MPC_STAGE_AUTO && !solver_ext(s) && cfg->max_obstacles <= 0 && lds_of(s->WLg, 8, sizeof(mpc::Problem<double>)) <= (160u * 1024u) / 8u) {
-            s->w2_gs = true; s->w2_ok = true; s->wave_lds_w2 = lds_of(s->WLg, 8, sizeof(mpc::Problem<double>));
-        }
-    }
-#endif
-    s->wave_lds32 = lds_of(s->gs32 ? s->WLg : s->WL, 4, sizeof(mpc::Problem<float>));
-    s->wave_lds = cfg->precision == MPC_FP32 ? s->wave_lds32 : lds_of(s->gs64 ? s->WLg : s->WL, 8, sizeof(mpc::Problem<double>));
-    if (s->wave_lds > 160u * 1024u) {
-        set_err("mpc_create: the working set of one instance (n, max_obstacles, max_vertices, precision) does not fit in the 160 KB of LDS "
-                "of a compute unit (about n <= 215 grid points in fp64 without obstacles; n <= 590 with the factorisation data in global memory)");
-        delete s;
-        return MPC_EINVAL;
     }
     s->device = device;
     s->max_batch = max_batch;
@@ -340,30 +224,16 @@ int mpc_create(const mpc_config* cfg, int32_t max_batch, int32_t device, mpc_sol
         if (er == hipSuccess) er = hipMemset(s->d_rows_dropped, 0, Bm * 4);
     }
     if (cfg->precision == MPC_MIXED && er == hipSuccess) er = hipMalloc((void**)&s->d_iters1, Bm * 4);
-    if (s->gs32 || s->gs64 || s->w2_gs || s->WL.GSW > 0) {
-        // blocks of factorisation data / of the clearance rows' elastic arrays (every layout with clearance rows has one, WaveLayout::GSW), a pool per XCD (mpc_solve_kernel.hpp): per XCD as many as the whole device has CUs -- an XCD has an eighth of them and a CU holds at
-        // most 8 of these one-wave workgroups (2 per SIMD under the register budget of any build), so a pool can never run dry --, never more than the largest launch has
-        // workgroups.  Stale contents are never read: every word is written before it is read within a solve.
+    if (plan.block_bytes > 0) {
+        // the per-XCD pools of blocks (mpc_solve_kernel.hpp), sized by mpc::pool_blocks_per_xcd from the device: the resident workgroups per CU of the kernel that claims
+        // the blocks (occupancy API: registers, LDS, one-wave workgroups) and the CUs of an XCD (the device's CUs over the distinct XCC ids a probe launch sees).  Stale
+        // contents are never read: every word is written before it is read within a solve.  Memory: 8 pools x per_xcd x block bytes (MI355X, n = 120 in fp64:
+        // 8 x 256 x 73 KB = 150 MB per handle; include/mpc_hip.h, mpc_create).
         hipDeviceProp_t prop;
         if (er == hipSuccess) er = hipGetDeviceProperties(&prop, device);
-        const size_t c32 = (cfg->precision != MPC_FP64 && s->P32.n_cand > 1) ? (size_t)s->P32.n_cand : 1, c64 = (cfg->precision != MPC_FP32 && s->P64.n_cand > 1) ? (size_t)s->P64.n_cand : 1;
-        const size_t grid = Bm * (c32 > c64 ? c32 : c64);
-        // Pool size per XCD = twice what ONE XCD can hold at once, from the runtime: workgroups per CU of the kernel that uses the pool (occupancy API: registers,
-        // LDS, one-wave workgroups) x the CUs of an XCD (the device's CUs / the number of distinct XCC ids a probe launch sees: 8 on an MI355X, 1 in a partitioned mode).  A
-        // pool can then never run dry, and the factor two keeps the claim probe of mpc_solve_kernel.hpp at a step or two when every CU is full.  Never more than the largest
-        // launch has workgroups.  Memory: 8 pools x per_xcd x block bytes (MI355X, n = 120 in fp64: 8 x 256 x 73 KB = 150 MB per handle; include/mpc_hip.h, mpc_create).
-        size_t per_cu = 8;      // (two one-wave workgroups per SIMD: the upper limit of any build)
-        int n_xcc = 1;
         if (er == hipSuccess) {
-            int occ = 0;
-            mpc::SolveLaunch a{};
-            a.level = !solver_ext(s) ? 0 : (s->P64.costx ? 2 : 1);
-            const bool f32 = cfg->precision == MPC_FP32;
-            a.w2 = !f32 && s->w2_gs;
-            const bool gsf = f32 ? s->gs32 : (s->gs64 || s->w2_gs);
-            a.L = gsf ? s->WLg : s->WL;
-            a.lds = f32 ? s->wave_lds32 : (s->w2_gs ? s->wave_lds_w2 : s->wave_lds);
-            if (pool_kernel_occupancy(f32, cfg->model, a, &occ) == hipSuccess && occ > 0) per_cu = (size_t)occ;
+            int occ = 0, n_xcc = 1;
+            if (kernel_occupancy(cfg->precision == MPC_FP32, cfg->model, mpc::plan_launch(plan, cfg->precision == MPC_FP32, 0), &occ) != hipSuccess) occ = 0;
             unsigned* d_mask = nullptr; unsigned h_mask = 0;
             if (hipMalloc((void**)&d_mask, 4) == hipSuccess) {
                 if (hipMemset(d_mask, 0, 4) == hipSuccess) {
@@ -372,20 +242,19 @@ int mpc_create(const mpc_config* cfg, int32_t max_batch, int32_t device, mpc_sol
                 }
                 (void)hipFree(d_mask);
             }
+            s->n_gslots = mpc::pool_blocks_per_xcd(plan, occ, prop.multiProcessorCount, n_xcc);
         }
-        const size_t cus_per_xcd = ((size_t)prop.multiProcessorCount + (size_t)n_xcc - 1) / (size_t)n_xcc;
-        size_t per_xcd = er == hipSuccess ? 2 * per_cu * cus_per_xcd : 512;
-        if (per_xcd < 64) per_xcd = 64;
-        s->n_gslots = (int)per_xcd;
-        const size_t blk64 = cfg->precision != MPC_FP32 ? (size_t)((s->gs64 || s->w2_gs) ? s->WLg.GSW : s->WL.GSW) * 8 : 0, blk32 = cfg->precision != MPC_FP64 ? (size_t)(s->gs32 ? s->WLg.GSW : s->WL.GSW) * 4 : 0;
-        if (er == hipSuccess) er = hipMalloc(&s->d_gstage, 8 * per_xcd * (blk64 > blk32 ? blk64 : blk32) + (size_t)mpc::GlobalStage::kPrefetchPad * 8);
+        const size_t pool_bytes = 8 * (size_t)s->n_gslots * plan.block_bytes + (size_t)mpc::GlobalStage::kPrefetchPad * 8;
+        if (er == hipSuccess) er = hipMalloc(&s->d_gstage, pool_bytes);
+#ifdef MPC_DEV_SWITCHES
         // developer check (scripts/dev/gs_sweep.py under MPC_POISON_GSTAGE=1): every word of the pool starts as a NaN pattern, so a word that some path consumes before writing it shows up in the results
-        if (er == hipSuccess) { if (const char* e = getenv("MPC_POISON_GSTAGE")) { if (e[0] == '1') er = hipMemset(s->d_gstage, 0xFF, 8 * per_xcd * (blk64 > blk32 ? blk64 : blk32) + (size_t)mpc::GlobalStage::kPrefetchPad * 8); } }
-        if (er == hipSuccess) er = hipMalloc((void**)&s->d_gslots, 8 * per_xcd * 4);
-        if (er == hipSuccess) er = hipMemset(s->d_gslots, 0, 8 * per_xcd * 4);
+        if (er == hipSuccess) { if (const char* e = getenv("MPC_POISON_GSTAGE")) { if (e[0] == '1') er = hipMemset(s->d_gstage, 0xFF, pool_bytes); } }
+#endif
+        if (er == hipSuccess) er = hipMalloc((void**)&s->d_gslots, 8 * (size_t)s->n_gslots * 4);
+        if (er == hipSuccess) er = hipMemset(s->d_gslots, 0, 8 * (size_t)s->n_gslots * 4);
     }
     if (cfg->dual_warm_start || cfg->precision == MPC_MIXED) {
-        s->dual_words = mpc::IpmWave<double, 0, 0>::dual_words(s->WL.NS);
+        s->dual_words = mpc::dual_words(plan.WL.NS);
         if (er == hipSuccess) er = hipMalloc((void**)&s->d_dual, Bm * (size_t)s->dual_words * 8);
         if (er == hipSuccess) er = hipMemset(s->d_dual, 0, Bm * (size_t)s->dual_words * 8);
     }
@@ -453,13 +322,9 @@ static hipError_t launch_model(mpc_solver* s, const mpc::Problem<T>& P, int B, c
                                const double* dtp, const double* xi, const double* ui, const double* dti, const mpc_obstacles& ob, double* xo, double* uo,
                                double* dto, int32_t* st, int32_t* it) {
     mpc::SolveLaunch a;
-    a.level = !solver_ext(s) ? 0 : (s->P64.costx ? 2 : 1);
-    a.lds = sizeof(T) == 4 ? s->wave_lds32 : s->wave_lds;
+    a.k = mpc::plan_launch(s->plan, sizeof(T) == 4, B);
     a.stream = s->stream;
-    a.w2 = sizeof(T) == 8 && s->w2_ok && B >= s->w2_min_batch;
-    if (a.w2) a.lds = s->wave_lds_w2;
-    const bool gs = a.w2 ? s->w2_gs : (sizeof(T) == 4 ? s->gs32 : s->gs64);
-    a.L = gs ? s->WLg : s->WL; a.B = B;
+    a.B = B;
     a.gstage = s->d_gstage; a.gslots = s->d_gslots; a.n_gslots = s->n_gslots;
     a.x0 = x0; a.xf = xf; a.u_prev = up; a.dt_prev = dtp; a.x_init = xi; a.u_init = ui; a.dt_init = dti; a.obst = ob;
     a.n_grid = s->use_ngrid ? s->d_ngrid : nullptr; a.n_via = s->p_nvia; a.via = s->p_via;
@@ -679,7 +544,7 @@ int mpc_grid_update_device(mpc_solver* s, int32_t B, const double* d_x0_new, dou
     mpc::GridUpdateArgs a;
     memset(&a, 0, sizeof(a));
     a.x0 = d_x0_new; a.x = d_x; a.u = d_u; a.dt = d_dt; a.n_stride = s->cfg.n;
-    a.dual = s->d_dual; a.dual_words = s->dual_words; a.dual_ns = s->WL.NS;
+    a.dual = s->d_dual; a.dual_words = s->dual_words; a.dual_ns = s->plan.WL.NS;
     if (!s->cfg.dt_free) {
         if (!d_x0_new) { set_err("mpc_grid_update_device: the fixed grid shifts towards the new start state (d_x0_new)"); return MPC_EINVAL; }
         a.mode = 0;
@@ -787,7 +652,7 @@ int mpc_synchronize(mpc_solver* s) {
 
 int mpc_lds_bytes(const mpc_solver* s, int64_t* bytes) {
     if (!s || !bytes) return MPC_EINVAL;
-    *bytes = (int64_t)s->wave_lds;
+    *bytes = (int64_t)s->plan.lds();
     return MPC_OK;
 }
 
@@ -795,17 +660,12 @@ int mpc_occupancy(mpc_solver* s, int32_t B, int32_t* workgroups_per_cu, int64_t*
     if (!s || !workgroups_per_cu || B <= 0) return MPC_EINVAL;
     g_err[0] = 0;
     HIP_TRY(hipSetDevice(s->device));
-    const bool f32 = s->cfg.precision == MPC_FP32;
-    mpc::SolveLaunch a{};
-    a.level = !solver_ext(s) ? 0 : (s->P64.costx ? 2 : 1);
-    a.w2 = !f32 && s->w2_ok && B >= s->w2_min_batch;
-    const bool gs = a.w2 ? s->w2_gs : (f32 ? s->gs32 : s->gs64);
-    a.L = gs ? s->WLg : s->WL;
-    a.lds = f32 ? s->wave_lds32 : (a.w2 ? s->wave_lds_w2 : s->wave_lds);
+    const bool f32 = s->cfg.precision == MPC_FP32;      // (MPC_MIXED: its fp64 phase)
+    const mpc::KernelChoice k = mpc::plan_launch(s->plan, f32, B);
     int occ = 0;
-    HIP_TRY(pool_kernel_occupancy(f32, s->cfg.model, a, &occ));
+    HIP_TRY(kernel_occupancy(f32, s->cfg.model, k, &occ));
     *workgroups_per_cu = occ;
-    if (lds_bytes) *lds_bytes = (int64_t)a.lds;
+    if (lds_bytes) *lds_bytes = (int64_t)k.lds;
     return MPC_OK;
 }
 

@@ -9,6 +9,47 @@ namespace mpc {
 // what mpc_config.line_search = MPC_LS_DEFAULT means: 0 the l1 merit, 1 Ipopt's filter
 constexpr int kDefaultLineSearch = 1;
 
+// why mpc_create refuses a configuration (the text mpc_last_error reports), or nullptr.  Checks of the configuration alone; mpc_create adds the device's.
+inline const char* config_error(const mpc_config& c) {
+    if (c.n < 3 || c.n > 4096) return "mpc_create: n out of range [3,4096]";
+    if (c.model < 0 || c.model > 3) return "mpc_create: unknown model";
+    if (c.collocation != MPC_COLLOC_FORWARD && c.collocation != MPC_COLLOC_MIDPOINT && c.collocation != MPC_COLLOC_CRANK_NICOLSON)
+        return "mpc_create: unknown collocation method";
+    if (c.objective != MPC_OBJ_MIN_TIME && c.objective != MPC_OBJ_QUADRATIC && c.objective != MPC_OBJ_MIN_TIME_VIA_POINTS) return "mpc_create: unknown objective";
+    if (c.objective == MPC_OBJ_MIN_TIME_VIA_POINTS && (c.max_via_points < 1 || c.max_via_points > 64))
+        return "mpc_create: minimum_time_via_points needs 1 <= max_via_points <= 64";
+    if (c.objective != MPC_OBJ_QUADRATIC && !c.dt_free) return "mpc_create: minimum_time needs a variable grid (dt_free)";
+    if (!(c.dt_ref > 0)) return "mpc_create: dt_ref must be > 0";
+    if (c.max_obstacles < 0 || c.max_obstacles > 4096 || (c.max_obstacles > 0 && (c.max_vertices < 1 || c.max_vertices > 64)) || c.max_obstacle_rows > 16)
+        return "mpc_create: obstacle capacities out of range (max_obstacles <= 4096, max_vertices <= 64, max_obstacle_rows <= 16)";
+    if (c.max_obstacles > 0 && c.footprint_kind != MPC_FOOTPRINT_POINT && c.footprint_kind != MPC_FOOTPRINT_CIRCLE && c.footprint_kind != MPC_FOOTPRINT_LINE &&
+        c.footprint_kind != MPC_FOOTPRINT_TWO_CIRCLES && c.footprint_kind != MPC_FOOTPRINT_POLYGON)
+        return "mpc_create: unknown footprint model";
+    if (c.max_obstacles > 0 && c.footprint_kind == MPC_FOOTPRINT_POLYGON && (c.footprint_n_vertices < 1 || c.footprint_n_vertices > 16))
+        return "mpc_create: the polygon footprint needs 1..16 vertices";
+    for (int j = 0; j < 2; ++j)
+        if (!(c.u_lb[j] < c.u_ub[j])) return "mpc_create: control box must be finite and non-empty";
+    if (c.precision != MPC_FP64 && c.precision != MPC_FP32 && c.precision != MPC_MIXED) return "mpc_create: unknown precision";
+    if (c.cost_integration != MPC_COST_LEFT_SUM && c.cost_integration != MPC_COST_TRAPEZOIDAL) return "mpc_create: unknown cost_integration";
+    if (c.hybrid_cost_minimum_time && c.objective != MPC_OBJ_QUADRATIC) return "mpc_create: hybrid_cost_minimum_time belongs to the quadratic_form objective";
+    if (c.n_candidates == 1 && c.candidate_kind[0] != MPC_CAND_REFERENCE)
+        return "mpc_create: a single candidate must be MPC_CAND_REFERENCE (other kinds only run as hedges next to it: n_candidates >= 2)";
+    if (c.precision == MPC_MIXED && (c.max_obstacles > 0 || c.objective == MPC_OBJ_MIN_TIME_VIA_POINTS))
+        return "mpc_create: MPC_MIXED is implemented for problems without clearance rows and via-points (their association would be redone by the refinement phase)";
+    if (c.hessian_mode != MPC_HESSIAN_EXACT && c.hessian_mode != MPC_HESSIAN_CONVEXIFIED) return "mpc_create: unknown hessian_mode";
+    if (c.mu_strategy != MPC_MU_ADAPTIVE && c.mu_strategy != MPC_MU_MONOTONE) return "mpc_create: unknown mu_strategy";
+    if (c.line_search != MPC_LS_DEFAULT && c.line_search != MPC_LS_MERIT && c.line_search != MPC_LS_FILTER) return "mpc_create: unknown line_search";
+    if (c.max_time_us < 0) return "mpc_create: max_time_us must be >= 0 (0 = no budget)";
+    if (c.n_candidates < 0 || c.n_candidates > MPC_MAX_CANDIDATES) return "mpc_create: n_candidates must be in [0, MPC_MAX_CANDIDATES]";
+    for (int k = 0; k < c.n_candidates; ++k)
+        if (c.candidate_kind[k] < MPC_CAND_REFERENCE || c.candidate_kind[k] > MPC_CAND_HERMITE_RF || c.candidate_max_iter[k] < 0)
+            return "mpc_create: unknown candidate kind or negative candidate_max_iter";
+    if (c.dt_free && !(c.dt_lb < c.dt_ub)) return "mpc_create: dt_lb must be below dt_ub on the variable grid";
+    if (c.dt_free && !(c.dt_ref >= c.dt_lb && c.dt_ref <= c.dt_ub)) return "mpc_create: dt_ref must lie in [dt_lb, dt_ub] on the variable grid";
+    if (c.stage_data != MPC_STAGE_AUTO && c.stage_data != MPC_STAGE_LDS && c.stage_data != MPC_STAGE_GLOBAL) return "mpc_create: unknown stage_data";
+    return nullptr;
+}
+
 template <typename T>
 inline void fill_problem(const mpc_config& c, mpc::Problem<T>& P) {
     P.model = c.model;

@@ -4,10 +4,10 @@
 // instantiated in the translation unit that includes this header (plain `hipcc mpc_capi.hip`, developer builds).
 #pragma once
 #include <hip/hip_runtime.h>
-#include <cstdlib>
 
 #include "../../include/mpc_hip.h"
 #include "mpc_core.hpp"
+#include "mpc_launch_plan.hpp"
 #include "mpc_wave.hpp"
 
 namespace mpc {
@@ -203,10 +203,8 @@ void mpc_ipm_wave_kernel(
 
 // everything one launch needs besides the problem record (plain pointers: device memory of the handle / of the caller)
 struct SolveLaunch {
-    int level;                  // 0 headline kernel, 1 + rare rows / terms / coupling slots, 2 + cost variants
-    size_t lds;                 // dynamic LDS of one workgroup
+    KernelChoice k;             // which kernel, on which record (mpc_launch_plan.hpp)
     hipStream_t stream;
-    WaveLayout L;
     int B;
     const double *x0, *xf, *u_prev, *dt_prev, *x_init, *u_init, *dt_init;
     mpc_obstacles obst;
@@ -216,90 +214,62 @@ struct SolveLaunch {
     const int32_t* iters_add;
     double *x_out, *u_out, *dt_out;
     int32_t *status, *iters;
-    void* gstage;               // L.GSW > 0: 8 x n_gslots blocks of factorisation data in global memory (L.GSW words of T each; n_gslots per XCD), claimed by the workgroups through `gslots`; else NULL
+    void* gstage;               // k.L.GSW > 0: 8 x n_gslots blocks of factorisation data in global memory (L.GSW words of T each; n_gslots per XCD), claimed by the workgroups through `gslots`; else NULL
     int* gslots;                // [8][n_gslots] 0 = free, 1 = taken (all 0 between launches)
     int n_gslots;
-    bool w2;                    // the two-waves-per-SIMD kernel (fp64, level 0, no clearance rows, L.GSF: mpc_capi.hip decides per launch)
 };
 
 constexpr int kFixedLayoutNS = 50;
 
-// the kernel instantiation that serves a launch record (nullptr + an error for a combination that does not exist)
+// the kernel instantiation that serves a kernel choice (nullptr for a combination that does not exist): four per (arithmetic type, model) in either form -- the
+// headline level without / with clearance rows and the two extended levels (always with) --, and in fp64 the fixed-layout kernel and the two-wave kernel
 template <typename T, int MODEL>
-auto select_kernel(const SolveLaunch& a, hipError_t& err) -> decltype(&mpc_ipm_wave_kernel<T, MODEL, 0, true>) {
-    err = hipSuccess;
-    // four instantiations per (arithmetic type, model): the headline level without / with clearance rows, and the two extended levels (always with)
-#ifdef MPC_DEV_SWITCHES
-    static const bool force_obst = getenv("MPC_FORCE_OBST_KERNEL") != nullptr;      // developer switch (A/B of the two headline instantiations); not in the shipped library
-#else
-    constexpr bool force_obst = false;
-#endif
-    auto kern = a.level == 0 ? ((a.L.M > 0 || force_obst) ? mpc_ipm_wave_kernel<T, MODEL, 0, true> : mpc_ipm_wave_kernel<T, MODEL, 0, false>)
-                             : (a.level == 2 ? mpc_ipm_wave_kernel<T, MODEL, 2, true> : mpc_ipm_wave_kernel<T, MODEL, 1, true>);
-    // factorisation data in global memory (WaveLayout::GSF; mpc_capi.hip decides per handle and precision)
-    if (a.L.GSF) {      // (r06: the extended levels too -- turning footprints, moving obstacles, cost variants at grid sizes whose LDS record fits fewer than four times)
-        kern = a.level == 0 ? ((a.L.M > 0 || force_obst) ? mpc_ipm_wave_kernel<T, MODEL, 0, true, 0, true> : mpc_ipm_wave_kernel<T, MODEL, 0, false, 0, true>)
-                            : (a.level == 2 ? mpc_ipm_wave_kernel<T, MODEL, 2, true, 0, true> : mpc_ipm_wave_kernel<T, MODEL, 1, true, 0, true>);
-    }
-    // fp64 headline kernel on a grid of kFixedLayoutNS points per record (the grid size of BASELINE configs[1] / [3]): the instantiation whose LDS layout is a
-    // compile-time constant (mpc_wave.hpp::FixedLayout) -- same code, same results bit for bit, ~3 % fewer instructions; every other size runs the generic one
+auto select_kernel(const KernelChoice& k) -> decltype(&mpc_ipm_wave_kernel<T, MODEL, 0, true>) {
+    const bool no_rows = k.level == 0 && k.L.M == 0;      // the headline level without clearance rows (OBST = false)
+    auto kern = k.level == 0 ? (k.L.M > 0 ? mpc_ipm_wave_kernel<T, MODEL, 0, true> : mpc_ipm_wave_kernel<T, MODEL, 0, false>)
+                             : (k.level == 2 ? mpc_ipm_wave_kernel<T, MODEL, 2, true> : mpc_ipm_wave_kernel<T, MODEL, 1, true>);
+    if (k.L.GSF)
+        kern = k.level == 0 ? (k.L.M > 0 ? mpc_ipm_wave_kernel<T, MODEL, 0, true, 0, true> : mpc_ipm_wave_kernel<T, MODEL, 0, false, 0, true>)
+                            : (k.level == 2 ? mpc_ipm_wave_kernel<T, MODEL, 2, true, 0, true> : mpc_ipm_wave_kernel<T, MODEL, 1, true, 0, true>);
     if constexpr (sizeof(T) == 8) {
-#ifdef MPC_DEV_SWITCHES
-        static const bool no_fixed = getenv("MPC_NO_FIXED_LAYOUT") != nullptr;      // developer switch (A/B); not in the shipped library
-#else
-        constexpr bool no_fixed = false;
-#endif
-        using IW = IpmWave<T, MODEL, 0, false, kFixedLayoutNS>;
-        if (a.level == 0 && a.L.M == 0 && a.L.GSF == 0 && !force_obst && !no_fixed && IW::LayoutT::matches(a.L)) kern = mpc_ipm_wave_kernel<T, MODEL, 0, false, kFixedLayoutNS>;
-    }
-    if constexpr (sizeof(T) == 8) {
-        if (a.w2) {
-            if (a.level != 0 || a.L.M > 0) { err = hipErrorInvalidConfiguration; return nullptr; }
-#ifdef MPC_DEV_SWITCHES
-            kern = a.L.GSF ? mpc_ipm_wave_kernel<T, MODEL, 0, false, 0, true, true> : mpc_ipm_wave_kernel<T, MODEL, 0, false, 0, false, true>;
-            {      // developer A/B: the 256-register variant of the fixed-layout kernel (one wave per SIMD all the same: its record is 40 KB)
-                using IW = IpmWave<T, MODEL, 0, false, kFixedLayoutNS>;
-                if (!a.L.GSF && IW::LayoutT::matches(a.L)) kern = mpc_ipm_wave_kernel<T, MODEL, 0, false, kFixedLayoutNS, false, true>;
-            }
-#else
-            if (a.L.GSF) { err = hipErrorInvalidConfiguration; return nullptr; }
-            kern = mpc_ipm_wave_kernel<T, MODEL, 0, false, 0, false, true>;
-#endif
-        }
+        // fp64 headline kernel on a grid of kFixedLayoutNS points per record (the grid size of BASELINE configs[1] / [3]): the instantiation whose LDS layout is a
+        // compile-time constant (mpc_layout.hpp::FixedLayout) -- same code, same results bit for bit, ~3 % fewer instructions; every other size runs the generic one
+        if (no_rows && !k.L.GSF && IpmWave<T, MODEL, 0, false, kFixedLayoutNS>::LayoutT::matches(k.L)) kern = mpc_ipm_wave_kernel<T, MODEL, 0, false, kFixedLayoutNS>;
+        if (k.w2) kern = no_rows && !k.L.GSF ? mpc_ipm_wave_kernel<T, MODEL, 0, false, 0, false, true> : nullptr;
+    } else if (k.w2) {
+        kern = nullptr;
     }
     return kern;
 }
 
 template <typename T, int MODEL>
 hipError_t launch_solve(const SolveLaunch& a, const Problem<T>& P) {
-    if (a.L.GSW > 0 && !a.gstage) return hipErrorInvalidConfiguration;
-    hipError_t err;
-    auto kern = select_kernel<T, MODEL>(a, err);
-    if (!kern) return err;
-    if (a.lds > 48u * 1024u) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds);
+    if (a.k.L.GSW > 0 && !a.gstage) return hipErrorInvalidConfiguration;
+    auto kern = select_kernel<T, MODEL>(a.k);
+    if (!kern) return hipErrorInvalidConfiguration;
+    if (a.k.lds > 48u * 1024u) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.k.lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(kern, dim3((unsigned)a.B * (unsigned)(P.n_cand > 1 ? P.n_cand : 1)), dim3(kWave), a.lds, a.stream, P, a.L, a.B, a.x0, a.xf, a.u_prev, a.dt_prev,
+    hipLaunchKernelGGL(kern, dim3((unsigned)a.B * (unsigned)(P.n_cand > 1 ? P.n_cand : 1)), dim3(kWave), a.k.lds, a.stream, P, a.k.L, a.B, a.x0, a.xf, a.u_prev, a.dt_prev,
                        a.x_init, a.u_init, a.dt_init, a.obst, a.n_grid, a.n_via, a.via, a.cc, a.iters_add, a.x_out, a.u_out, a.dt_out, a.status, a.iters, a.gstage, a.gslots, a.n_gslots);
     return hipSuccess;
 }
 
-// resident one-wave workgroups per CU of the kernel that serves a launch record (registers, LDS): what sizes the per-XCD block pools (mpc_capi.hip)
+// resident workgroups per CU of the kernel that serves a kernel choice (registers, LDS): mpc_occupancy, and what sizes the per-XCD block pools (mpc_capi.hip)
 template <typename T, int MODEL>
-hipError_t solve_occupancy(const SolveLaunch& a, int* out) {
-    hipError_t err;
-    auto kern = select_kernel<T, MODEL>(a, err);
-    if (!kern) return err;
-    if (a.lds > 48u * 1024u) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds);
+hipError_t solve_occupancy(const KernelChoice& k, int* out) {
+    auto kern = select_kernel<T, MODEL>(k);
+    if (!kern) return hipErrorInvalidConfiguration;
+    if (k.lds > 48u * 1024u) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds);
         if (e != hipSuccess) return e;
     }
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(out, kern, kWave, a.lds);
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(out, kern, kWave, k.lds);
 }
 
 #if defined(MPC_SPLIT_BUILD) && !defined(MPC_SOLVE_INST)
-#define MPC_EXTERN_LAUNCH(T, M) extern template hipError_t launch_solve<T, M>(const SolveLaunch&, const Problem<T>&); extern template hipError_t solve_occupancy<T, M>(const SolveLaunch&, int*);
+#define MPC_EXTERN_LAUNCH(T, M) extern template hipError_t launch_solve<T, M>(const SolveLaunch&, const Problem<T>&); extern template hipError_t solve_occupancy<T, M>(const KernelChoice&, int*);
 MPC_EXTERN_LAUNCH(double, 0) MPC_EXTERN_LAUNCH(double, 1) MPC_EXTERN_LAUNCH(double, 2) MPC_EXTERN_LAUNCH(double, 3)
 MPC_EXTERN_LAUNCH(float, 0) MPC_EXTERN_LAUNCH(float, 1) MPC_EXTERN_LAUNCH(float, 2) MPC_EXTERN_LAUNCH(float, 3)
 #undef MPC_EXTERN_LAUNCH

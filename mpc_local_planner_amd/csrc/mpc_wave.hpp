@@ -20,7 +20,8 @@
 // reference citations of every formula.
 //
 // File map (r05: one struct, six parts -- the .inc files are included INSIDE struct IpmWave):
-//   mpc_wave_layout.hpp   WaveLayout / FixedLayout / GlobalStage, wavefront reductions
+//   mpc_layout.hpp        WaveLayout / FixedLayout / GlobalStage (plain C++: the host plans launches with them, mpc_launch_plan.hpp)
+//   mpc_wave_layout.hpp   stage-record slot tables, wavefront reductions
 //   mpc_wave.hpp          this file: members, accessors, sweep-pointer abstraction (LDS or global memory)
 //   mpc_wave_rows.inc     terminal ball, via-points, clearance rows (geometry, footprints, association)
 //   mpc_wave_passes.inc   point evaluation, line-search trials, KKT error + stage records, condensed barrier terms
@@ -58,6 +59,7 @@ struct IpmWave {
     static constexpr int NTRB = (MODEL == MODEL_KINEMATIC_BICYCLE || MODEL == MODEL_SIMPLE_CAR_FRONT) ? 4 : 3;
     static_assert(NSC == 0 || (EXT == 0 && !OBST), "the fixed layout exists for the headline instantiation only");
     static_assert(!GS || NSC == 0, "the fixed layout keeps its factorisation data in LDS");
+    static_assert(!W2 || (!GS && EXT == 0 && !OBST), "the two-wave kernel exists for the headline instantiation in the LDS form only");
     using LayoutT = typename LayoutOf<NSC, NTRB, NSTG>::type;
     const Problem<T>& P;     // lives in LDS (copied once per workgroup): wave-uniform constants are fetched with
     const LayoutT L;         // broadcast ds_reads instead of being pinned in (and spilled from) scalar registers; the layout
@@ -137,7 +139,7 @@ struct IpmWave {
     // cost variants: minimum-time term in the objective (minimum-time objectives and the hybrid quadratic form); off-diagonal weights /
     // trapezoidal rule (EXT instantiation only: everything below `costx()` is delta code on top of the diagonal left-sum arithmetic)
     __device__ __forceinline__ bool mintime() const { return (flags >> 16) & 1; }
-    __device__ __forceinline__ bool costx() const { return EXT >= 2; }      // that instantiation is only launched for such problems (mpc_capi.hip::solver_ext)
+    __device__ __forceinline__ bool costx() const { return EXT >= 2; }      // that instantiation is only launched for such problems (mpc_launch_plan.hpp, the level)
     // off-diagonal part of W x and of x' W x for the symmetric matrix with off-diagonal terms o = (01, 02, 12)
     __device__ __forceinline__ void offmul(const T o[3], const T x[3], T y[3]) const {
         y[0] = o[0] * x[1] + o[1] * x[2]; y[1] = o[0] * x[0] + o[2] * x[2]; y[2] = o[1] * x[0] + o[2] * x[1];
@@ -240,11 +242,7 @@ struct IpmWave {
     // pair (which the compiler parks in a lane of a spill register when it runs out: 1/32 of the space), and the phases in between have the vector registers for themselves.
     // The 256-register kernels (W2) do that with the solve loop's scalars -- some sixty of them: barrier parameter, penalty, step data, the KKT error's pieces --, which is where
     // their scratch traffic came from (profiles/r06_wave_kernel_n20_two_waves.md).  Pure copies: results unchanged.
-    static constexpr bool kUniformScalars = W2
-#ifdef MPC_UNIFORM_SCALARS_ALL      // developer A/B: the same in the one-wave kernels
-        || true
-#endif
-        ;
+    static constexpr bool kUniformScalars = W2;
     __device__ __forceinline__ static double uni_(double v) { return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v))); }
     __device__ __forceinline__ static float uni_(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
     // pow() of the device library is some 300 instructions and three dozen fp64 literals; inlined at its two (rarely executed) call sites of the solve loop the compiler

@@ -72,17 +72,9 @@
     // So: partitioned while mu > max(tol, 1e-6) (Problem::pit_mu_min), max(tol, 1e-4) in the kernels with clearance rows (pit_floor()).
     static constexpr bool kPartitionedSweeps = true;
     __device__ __forceinline__ T pit_floor() const { return OBST ? t_max(P.pit_mu_min, T(1e-4)) : P.pit_mu_min; }
-    // (the two-wave kernel of the LDS form only runs grids of at most 24 points -- its record has to fit eight times into a CU --: the partitioned sweeps are compiled out of it, a
+    // (the two-wave kernel only runs grids of at most 24 points -- its LDS record has to fit eight times into a CU --: the partitioned sweeps are compiled out of it, a
     //  third of its code; two resident waves per SIMD share the instruction cache: instruction-fetch waits 17 % -> see profiles/r06_wave_kernel_n20_two_waves.md)
-    __device__ __forceinline__ bool pit_enabled() const { return kPartitionedSweeps && !(W2 && (!GS
-#ifdef MPC_W2_GS_NO_PIT      // developer A/B: the two-wave kernel on the global form with serial sweeps only
-                                                                                                                         || true
-#endif
-                                                                                                                         ))
-#ifdef MPC_GS_NO_PIT         // developer A/B: the global form with serial sweeps only (a third less code in kernels whose four waves per CU share the instruction cache)
-                                                                                                                         && !GS
-#endif
-                                                                                                                         && EXT < 2 && P.pit != 0 && L.n >= 40 && 3 * L.NS >= 100 && L.NTR * L.NS >= 100 && 5 * L.NS >= 192; }
+    __device__ __forceinline__ bool pit_enabled() const { return kPartitionedSweeps && !W2 && EXT < 2 && P.pit != 0 && L.n >= 40 && 3 * L.NS >= 100 && L.NTR * L.NS >= 100 && 5 * L.NS >= 192; }
     // excess of negative eigenvalues of a combine's pivot block: n-(W) + n-(P+ - W^-1) - 5, by Jacobi's signature rule (negative pivots of the elimination without exchanges).
     // W (the element's, 5 x 5, in the hand-off tile) is swept in place -- the symmetric sweep operator leaves -W^-1 and shows the same pivots as the elimination --, then
     // G = P+ + (-W^-1) is eliminated.  Wave-uniform arithmetic on the upper triangles, values read with uniform LDS addresses / v_readlane: a few hundred instructions per

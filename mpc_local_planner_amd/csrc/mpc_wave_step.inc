@@ -357,8 +357,7 @@
     }
 
     // ---- multipliers kept in the handle between control cycles (dual_warm_start).  Block layout (doubles): [0] grid size, [1] pi_dt lower,
-    //      [2] pi_dt upper, [3] terminal-ball multiplier, then the LDS word ranges LAM (3 NS), YR (4 NS), PL (2 NS), PU (2 NS) verbatim.
-    __host__ __device__ static int dual_words(int ns) { return 4 + 11 * ns; }
+    //      [2] pi_dt upper, [3] terminal-ball multiplier, then the LDS word ranges LAM (3 NS), YR (4 NS), PL (2 NS), PU (2 NS) verbatim: mpc::dual_words(NS) doubles.
     __device__ __forceinline__ void store_duals(double* blk) const {
         const int NS = L.NS;
         if (lane == 0) { blk[0] = double(L.n); blk[1] = double(SCL(SC_PDL)); blk[2] = double(SCL(SC_PDU)); blk[3] = ball() ? double(SCL(SC_TY)) : 0.0; }

@@ -1,6 +1,6 @@
 """developer script (GPU): the two-waves-per-SIMD kernel against the one-wave kernels of the same handle configuration, over the batch size.  mpc_config.two_wave_min_batch = -1 switches the two-wave
-kernel off, 1 on for every launch; W2_N=<grid points> (default 50: there only a library built with -DMPC_DEV_SWITCHES has a two-wave kernel -- the global form, MPC_W2_GS=1).  Prints kernel times, converged solves/s and whether the outputs are
-bit-identical."""
+kernel off, 1 on for every launch; W2_N=<grid points> (default 20; the two-wave kernel exists where the LDS record fits eight times into a CU, about n <= 24 -- on larger
+grids both legs run the one-wave kernel).  Prints kernel times, converged solves/s and whether the outputs are bit-identical."""
 import os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
@@ -21,7 +21,7 @@ def run(cfg, inp, B, reps=4):
 sets = {"headline100": dict(candidates=(0, 5, 5, 7), candidate_max_iter=(100, 45, 40, 35), candidate_param=(0.0, 2.0, 3.0, 1.5)),
         "share100_60_50_40": dict(candidates=(0, 5, 5, 7), candidate_max_iter=(100, 60, 50, 40), candidate_param=(0.0, 2.0, 3.0, 1.5)),
         "single": {}}
-N = int(os.environ.get("W2_N", "50"))
+N = int(os.environ.get("W2_N", "20"))
 which = sys.argv[1:] or ["headline100", "share100_60_50_40"]
 for name in which:
     print(f"# {name}, n = {N}")

@@ -152,7 +152,17 @@ int32_t mpc_version(void) { return 600; }      // 0.6.0: mpc_config.two_wave_min
 #ifdef MPC_PROFILE
 // developer build only (-DMPC_PROFILE): per-wave phase cycle counters of the last wave-kernel launch
 int mpc_debug_profile(long long* out, int rows) {
+#ifdef MPC_SPLIT_BUILD
+    std::memset(out, 0, sizeof(long long) * 16 * (size_t)rows);
+    hipError_t e = hipSuccess;
+#define MPC_PROFILE_ADD(T, M) if (e == hipSuccess) e = mpc::solve_profile_add<T, M>(out, rows);
+    MPC_PROFILE_ADD(double, 0) MPC_PROFILE_ADD(double, 1) MPC_PROFILE_ADD(double, 2) MPC_PROFILE_ADD(double, 3)
+    MPC_PROFILE_ADD(float, 0) MPC_PROFILE_ADD(float, 1) MPC_PROFILE_ADD(float, 2) MPC_PROFILE_ADD(float, 3)
+#undef MPC_PROFILE_ADD
+    return (int)e;
+#else
     return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_mpc_prof), sizeof(long long) * 16 * (size_t)rows, 0, hipMemcpyDeviceToHost);
+#endif
 }
 #endif
 

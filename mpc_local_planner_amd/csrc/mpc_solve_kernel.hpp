@@ -4,6 +4,7 @@
 // instantiated in the translation unit that includes this header (plain `hipcc mpc_capi.hip`, developer builds).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <vector>
 
 #include "../../include/mpc_hip.h"
 #include "mpc_core.hpp"
@@ -268,11 +269,30 @@ hipError_t solve_occupancy(const KernelChoice& k, int* out) {
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(out, kern, kWave, k.lds);
 }
 
+#ifdef MPC_PROFILE
+// developer build (-DMPC_PROFILE): every translation unit has a g_mpc_prof of its own, and the split build launches the solve kernels from the objects of
+// mpc_solve_inst.hip: mpc_debug_profile adds up what each of them holds (the counters of the pairs that did not run stay zero)
+template <typename T, int MODEL>
+hipError_t solve_profile_add(long long* acc, int rows) {
+    std::vector<long long> b((size_t)16 * rows);
+    hipError_t e = hipMemcpyFromSymbol(b.data(), HIP_SYMBOL(g_mpc_prof), sizeof(long long) * b.size(), 0, hipMemcpyDeviceToHost);
+    for (size_t i = 0; e == hipSuccess && i < b.size(); ++i) acc[i] += b[i];
+    return e;
+}
+#endif
+
 #if defined(MPC_SPLIT_BUILD) && !defined(MPC_SOLVE_INST)
-#define MPC_EXTERN_LAUNCH(T, M) extern template hipError_t launch_solve<T, M>(const SolveLaunch&, const Problem<T>&); extern template hipError_t solve_occupancy<T, M>(const KernelChoice&, int*);
+#ifdef MPC_PROFILE
+#define MPC_EXTERN_PROFILE(T, M) extern template hipError_t solve_profile_add<T, M>(long long*, int);
+#else
+#define MPC_EXTERN_PROFILE(T, M)
+#endif
+#define MPC_EXTERN_LAUNCH(T, M) extern template hipError_t launch_solve<T, M>(const SolveLaunch&, const Problem<T>&); extern template hipError_t solve_occupancy<T, M>(const KernelChoice&, int*); \
+                                MPC_EXTERN_PROFILE(T, M)
 MPC_EXTERN_LAUNCH(double, 0) MPC_EXTERN_LAUNCH(double, 1) MPC_EXTERN_LAUNCH(double, 2) MPC_EXTERN_LAUNCH(double, 3)
 MPC_EXTERN_LAUNCH(float, 0) MPC_EXTERN_LAUNCH(float, 1) MPC_EXTERN_LAUNCH(float, 2) MPC_EXTERN_LAUNCH(float, 3)
 #undef MPC_EXTERN_LAUNCH
+#undef MPC_EXTERN_PROFILE
 #endif
 
 }  // namespace mpc

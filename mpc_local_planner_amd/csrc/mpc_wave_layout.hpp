@@ -52,6 +52,12 @@ __device__ __forceinline__ double rd_lane(double v, int src) {
     return __hiloint2double(hi, lo);
 }
 __device__ __forceinline__ float rd_lane(float v, int src) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src)); }
+// the value of lane `src` (per-lane index) in every lane: ds_bpermute on the 32-bit halves
+__device__ __forceinline__ double lane_gather(double v, int src) {
+    const int lo = __builtin_amdgcn_ds_bpermute(4 * src, __double2loint(v)), hi = __builtin_amdgcn_ds_bpermute(4 * src, __double2hiint(v));
+    return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ float lane_gather(float v, int src) { return __int_as_float(__builtin_amdgcn_ds_bpermute(4 * src, __float_as_int(v))); }
 
 struct OpSum { template <typename T> __device__ __forceinline__ static T f(T a, T b) { return a + b; } };
 struct OpMin { template <typename T> __device__ __forceinline__ static T f(T a, T b) { return b < a ? b : a; } };

@@ -61,7 +61,7 @@
     // r04, inertia: a factorisation is accepted when the KKT matrix has Ipopt's inertia (riccati_root).  The serial sweep reads it off the signs of its control pivots R_k.  Here
     // every row counts the negative eigenvalues of the pivots of ITS segment (those of the segment's own cost-to-go from the identity border, not the serial ones), and
     // every combine eliminates the pair (costate, state) at a boundary: the block [[W, -I], [-I, P+]] over the five components that have a costate column has the inertia
-    // In(W) + In(P+ - W^-1) (Haynsworth), five negative eigenvalues when all is well -- pit_block_inertia() returns the excess.  The sum of all of it plus the root system's
+    // In(W) + In(P+ - W^-1) (Haynsworth), five negative eigenvalues when all is well -- pit_combine_inertia() / pit_block_inertia() return the excess.  The sum of all of it plus the root system's
     // count is the matrix's, whatever the elimination order (Sylvester); tests/test_pit_math.py::test_inertia_of_the_kkt_matrix_from_the_sweeps holds both counts to the
     // eigenvalues of the dense matrix, including the cases where a negative pivot in one place is made up for in another.
     // Where the serial sweeps take over (r04, measured on the MI355X with the inertia test in both, scripts/dev/pit_*_sweep.py): the combines' I - W P+ is eliminated without
@@ -75,30 +75,55 @@
     // (the two-wave kernel only runs grids of at most 24 points -- its LDS record has to fit eight times into a CU --: the partitioned sweeps are compiled out of it, a
     //  third of its code; two resident waves per SIMD share the instruction cache: instruction-fetch waits 17 % -> see profiles/r06_wave_kernel_n20_two_waves.md)
     __device__ __forceinline__ bool pit_enabled() const { return kPartitionedSweeps && !W2 && EXT < 2 && P.pit != 0 && L.n >= 40 && 3 * L.NS >= 100 && L.NTR * L.NS >= 100 && 5 * L.NS >= 192; }
-    // excess of negative eigenvalues of a combine's pivot block: n-(W) + n-(P+ - W^-1) - 5, by Jacobi's signature rule (negative pivots of the elimination without exchanges).
-    // W (the element's, 5 x 5, in the hand-off tile) is swept in place -- the symmetric sweep operator leaves -W^-1 and shows the same pivots as the elimination --, then
-    // G = P+ + (-W^-1) is eliminated.  Wave-uniform arithmetic on the upper triangles, values read with uniform LDS addresses / v_readlane: a few hundred instructions per
-    // combine against the ~4 k a partitioned factorisation saves.  ok = false when a pivot vanishes (the caller then repeats the factorisation with the serial sweep).
+    // excess of negative eigenvalues of the pivot blocks of the three combines: n-(W) + n-(P+ - W^-1) - 5 each, by Jacobi's signature rule (negative pivots of the
+    // elimination without exchanges).  W (the element's, 5 x 5) is swept in place -- the symmetric sweep operator leaves -W^-1 and shows the same pivots as the
+    // elimination --, then G = P+ + (-W^-1) is eliminated (upper triangles; mpc_core.hpp::pit_block_inertia_tri has the arithmetic, compiled for the host by the tests).
+    // Nothing of a combine depends on these counts, so they are taken after the last combine, all three at once: row s < 3 evaluates the block that took in ITS
+    // segment's element -- W is the row's own wn (lane 9 + b holds W[a][b] as wn[a]; the asymmetry of the accumulated tile is rounding), P+ is the value function at the
+    // segment's end, which that combine saved for the forward pass (pit_tile(s) + 50: word 10 a + b = P+[a][b]).  Same values, same arithmetic as one block per
+    // combine; one serial chain of ten pivots instead of three.  ok = false when a pivot vanishes in any of them (the caller then repeats the factorisation with the
+    // serial sweep).
+    // (The kernels with a run-time layout keep one wave-uniform count per combine, pit_block_inertia(): there the code of the lane-parallel pass pushed the
+    //  compiler into a stack frame -- 800-864 B of scratch per lane and 3-8 % longer launches of config 3 / config 5 / n = 20.)
     template <bool LP_A>
     __device__ __forceinline__ int pit_block_inertia(const int TB, const T (&Vp)[6], bool& ok) const {
         const int TW = TB + 96;
-        T w[15], g[15];                               // upper triangles (mpc_core.hpp::pit_block_inertia_tri has the arithmetic, compiled for the host by the tests)
+        T w[15], g[15];
 #pragma unroll
         for (int a = 0; a < 5; ++a)
 #pragma unroll
             for (int b = a; b < 5; ++b) {
                 const int u = a * (9 - a) / 2 + b;
-                w[u] = T(sm[TW + 16 * a + 9 + b]);                                        // W[a][b] lives in lane 9 + b as wn[a] (the asymmetry of the accumulated tile is rounding)
+                w[u] = T(sm[TW + 16 * a + 9 + b]);                                        // W[a][b] lives in lane 9 + b as wn[a]
                 g[u] = rd_lane(Vp[a], LP_A ? b : (b < 2 ? 6 + b : 10 + b));
             }
         return pit_block_inertia_tri(w, g, ok);
+    }
+    __device__ __forceinline__ int pit_combine_inertia(const T (&wn)[5], int row, bool& ok) const {
+        const int tb = pit_tile(row < 3 ? row : 0) + 50;
+        const int src = (local_lane() & 48) + 9;
+        sync();                                                            // (the combines' saves were made by other lanes)
+        T w[15], g[15];
+#pragma unroll
+        for (int a = 0; a < 5; ++a)
+#pragma unroll
+            for (int b = a; b < 5; ++b) {
+                const int u = a * (9 - a) / 2 + b;
+                w[u] = lane_gather(wn[a], src + b);
+                g[u] = T(sm[tb + 10 * a + b]);
+            }
+        bool okr = true;
+        const int neg = pit_block_inertia_tri(w, g, okr);
+        const int okw = okr ? 1 : 0;
+        ok = ok && (__builtin_amdgcn_readlane(okw, 0) & __builtin_amdgcn_readlane(okw, 16) & __builtin_amdgcn_readlane(okw, 32)) != 0;
+        return __builtin_amdgcn_readlane(neg, 0) + __builtin_amdgcn_readlane(neg, 16) + __builtin_amdgcn_readlane(neg, 32);
     }
     // one combine step.  LP_A: the value function's P+ columns sit in lane set A (then the result's sit in B), else the other way round.
     // In: Vp / Wp / omp = value function at the segment's end, the element's tile in LDS at TB.  Out: the same registers = value function at the
     // segment's start; the eliminated tile and the old value function go to `save` for the forward pass; wpiv = min |pivot| so far.
     template <bool LP_A>
     __device__ __forceinline__ void combine(const int TB, const int save, const CombLane& cl, const int lm, T (&Vp)[6], T (&Wp)[3], T& omp, T& wpiv, int& inert, bool& iok) const {
-        inert += pit_block_inertia<LP_A>(TB, Vp, iok);        // first: nothing of the combine is live yet
+        if constexpr (NSC == 0) inert += pit_block_inertia<LP_A>(TB, Vp, iok);        // first: nothing of the combine is live yet
         const int TW = TB + 96;
         T Wt[5], WV[5], A[6], U[6], St[6], Ra[6];
 #pragma unroll
@@ -311,6 +336,7 @@
         put_tile(0);
         combine<true>(TB, pit_tile(0), comb_lane(c, true, TB), lm, Vp, Wp, omp, wpiv, inert, iok);
         PIT_DBG_W("V0")
+        if constexpr (NSC != 0) inert += pit_combine_inertia(wn, row, iok);
         MPC_MARK("PIT_COMBINE_END");
 #ifdef MPC_PROFILE
         prof_setup += __builtin_readcyclecounter() - tp1;
@@ -318,7 +344,7 @@
         if (!(rd_lane(wpiv, 0) > T(1e-9)) || !iok) return 0;           // a pivot of I - W P+ (or of the inertia count) broke down: the caller repeats this factorisation with the serial sweep
         // ---- root: the value function at stage 0 has its P columns in lane set B (lane 15 = column 5)
         RicState<T> Vr;
-        Vr.neg = inert;                                                    // segments' control pivots + the excess of the three combine blocks (pit_block_inertia)
+        Vr.neg = inert;                                                    // segments' control pivots + the excess of the three combine blocks (pit_combine_inertia)
         Vr.P[5][5] = rd_lane(Vp[5], 15);
         Vr.p[5] = rd_lane(Vp[5], 8);
         Vr.S[5][0] = rd_lane(Vp[5], 9); Vr.S[5][1] = rd_lane(Vp[5], 10); Vr.S[5][2] = rd_lane(Vp[5], 11);

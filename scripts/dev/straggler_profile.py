@@ -1,4 +1,4 @@
-"""developer tool: where the slowest reference-path solves of the config-2 batch spend their time (MPC_HIP_LIB = a -DMPC_PROFILE single-TU build, see phase_profile.py)"""
+"""developer tool: where the slowest reference-path solves of the config-2 batch spend their time (MPC_HIP_LIB = a -DMPC_PROFILE build, see phase_profile.py)"""
 import sys, os, ctypes as C, numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import mpc_local_planner_amd as m

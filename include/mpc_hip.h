@@ -336,6 +336,20 @@ int mpc_step_batch_device(mpc_solver* s, int32_t B,
  * x_init/u_init/x_out/u_out are meaningful.  HOST pointer, copied; NULL restores the uniform size cfg.n. */
 int mpc_set_grid_sizes(mpc_solver* s, const int32_t* n_grid, int32_t B);
 
+/* Parameter sets: instances of ONE handle and ONE launch that solve with different numbers -- e.g. the robots of a fleet, each configured from its own
+ * parameter file (the reference runs Controller::configure per robot, src/controller.cpp:225-805).  sets[0 .. n_sets) are complete mpc_configs; instance b
+ * of the following mpc_solve_batch* / mpc_step_batch* / mpc_grid_update_device calls uses sets[set_of[b]] and returns, bit for bit, what a handle created
+ * with that configuration returns for the same inputs (every precision and kernel form, candidates, dual_warm_start, grid adaptation against its own dt_ref).
+ * A set may differ from the handle's configuration in the double fields only (model parameters, dt_ref / dt_lb / dt_ub, weights and off-diagonal terms,
+ * control and control-rate bounds, tol / mu_init* / acceptable_tol, clearance distances, footprint radius / line / polygon coordinates, terminal ball,
+ * via-point weights, candidate_param); every int32_t field has to equal the handle's, and so do which control-rate bounds are finite and whether the
+ * off-diagonal cost terms are all zero (they select rows and the kernel level).  A refused set is MPC_EINVAL and mpc_last_error names the set and the
+ * field ("mpc_set_parameter_sets: set 3: du_ub[1] is finite here and infinite in the handle's configuration"); so is a set_of[b] outside [0, n_sets); n_sets or B
+ * outside [1, max_batch] is MPC_EBATCH.  A refused call changes nothing.  HOST pointers, copied (the call waits until the copy is on the device); the sets stay
+ * in force until the next call -- mpc_reset keeps them -- and a solve or grid update with more than B instances is MPC_EBATCH.  sets == NULL gives every
+ * instance the handle's own configuration again.  Cost: one 896-byte (fp32: 528-byte) record read per workgroup. */
+int mpc_set_parameter_sets(mpc_solver* s, int32_t n_sets, const mpc_config* sets, int32_t B, const int32_t* set_of);
+
 /* The grid update between two control cycles for a whole batch, on the device and in place on the previous solve's outputs
  * (d_x / d_u / d_dt = that solve's x_out / u_out / dt_out, handed back as x_init / u_init / dt_init of the next solve), so that a batched
  * closed loop needs no host round trip:

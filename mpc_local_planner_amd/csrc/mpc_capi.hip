@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <string>
 #include <vector>
 
 #include "../../include/mpc_hip.h"
@@ -38,8 +39,20 @@ void set_err(const char* what) { snprintf(g_err, sizeof(g_err), "%s", what); }
 
 struct mpc_solver {
     mpc_config cfg;
-    mpc::Problem<double> P64;
+    mpc::Problem<double> P64;   // the handle's own records (host copies: what selects the kernel and sizes the launch)
     mpc::Problem<float> P32;
+    // device table of problem records (mpc_set_parameter_sets): entry 0 is the handle's own configuration, entries 1 .. n_sets the sets in force; a solve
+    // kernel copies entry set_of[b] (entry 0 while p_set_of is NULL) into the LDS of instance b.  One allocation: fp64 records | fp32 records | dt_ref per entry
+    unsigned char* d_tab;
+    mpc::Problem<double>* d_tab64;      // NULL for a handle without fp64 launches
+    mpc::Problem<float>* d_tab32;       // NULL for a handle without fp32 launches
+    double* d_dtref;                    // dt_ref of every entry (single-step grid adaptation of mpc_grid_update_device)
+    int tab_cap;                        // entries the table has room for
+    int32_t* d_set_of;                  // [max_batch] table entry of instance b (1 + its set), allocated by the first mpc_set_parameter_sets
+    const int32_t* p_set_of;            // what the kernels read: d_set_of while sets are in force, else NULL
+    int sets_B;                         // batch size the sets were given for (solves must not exceed it)
+    unsigned char* h_tab;               // pinned staging of the table uploads
+    size_t h_tab_cap;
     mpc::LaunchPlan plan;       // which kernel each launch runs (mpc_launch_plan.hpp)
     void* d_gstage;             // 8 pools of n_gslots blocks (plan.block_bytes each), NULL when the plan has none
     int* d_gslots;              // [8][n_gslots] claim words of the blocks (0 = free)
@@ -113,6 +126,34 @@ static hipError_t stage_carve(mpc_solver* s, const size_t* sz, int count, void**
     return hipSuccess;
 }
 
+// byte offsets of the three pieces of a record table of `entries` entries (256-byte aligned), and its size
+struct TabLayout {
+    size_t o64, o32, odt, bytes;
+    TabLayout(const mpc_config& c, size_t entries) {
+        auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+        const size_t b64 = c.precision != MPC_FP32 ? entries * sizeof(mpc::Problem<double>) : 0, b32 = c.precision != MPC_FP64 ? entries * sizeof(mpc::Problem<float>) : 0;
+        o64 = 0; o32 = up(b64); odt = o32 + up(b32); bytes = odt + up(entries * 8);
+    }
+};
+
+// writes table entry e (records and dt_ref of configuration c) into a host image of the table
+static void put_entry(const mpc_config& hcfg, const mpc_config& c, size_t entries, size_t e, unsigned char* img) {
+    const TabLayout t(hcfg, entries);
+    mpc::Problem<double> P64;
+    mpc::Problem<float> P32;
+    mpc::fill_records(c, P64, P32);
+    if (hcfg.precision != MPC_FP32) memcpy(img + t.o64 + e * sizeof(P64), &P64, sizeof(P64));
+    if (hcfg.precision != MPC_FP64) memcpy(img + t.o32 + e * sizeof(P32), &P32, sizeof(P32));
+    memcpy(img + t.odt + e * 8, &c.dt_ref, 8);
+}
+
+static void point_tables(mpc_solver* s) {
+    const TabLayout t(s->cfg, (size_t)s->tab_cap);
+    s->d_tab64 = s->cfg.precision != MPC_FP32 ? reinterpret_cast<mpc::Problem<double>*>(s->d_tab + t.o64) : nullptr;
+    s->d_tab32 = s->cfg.precision != MPC_FP64 ? reinterpret_cast<mpc::Problem<float>*>(s->d_tab + t.o32) : nullptr;
+    s->d_dtref = reinterpret_cast<double*>(s->d_tab + t.odt);
+}
+
 extern "C" {
 
 void mpc_config_defaults(mpc_config* c) {
@@ -146,7 +187,7 @@ void mpc_config_defaults(mpc_config* c) {
 }
 
 const char* mpc_last_error(void) { return g_err; }
-int32_t mpc_version(void) { return 600; }      // 0.6.0: mpc_config.two_wave_min_batch and mpc_config.line_search took the last reserved words (same size).  0.5.0: mpc_config.stage_data took a reserved word (same size); a solve restores clearance rows that jam.  0.4.0: mpc_config.mu_strategy / max_time_us took reserved words (same size), MPC_TIME_LIMIT; a solve accepts factorisations on their inertia
+int32_t mpc_version(void) { return 700; }      // 0.7.0: mpc_set_parameter_sets (per-instance double parameters of mpc_config, one launch).  0.6.0: mpc_config.two_wave_min_batch and mpc_config.line_search took the last reserved words (same size).  0.5.0: mpc_config.stage_data took a reserved word (same size); a solve restores clearance rows that jam.  0.4.0: mpc_config.mu_strategy / max_time_us took reserved words (same size), MPC_TIME_LIMIT; a solve accepts factorisations on their inertia
 // history: 0.2.0: mpc_config grew (candidates, kept multipliers, hessian_mode), new entry points; 0.2.1: cost variants (off-diagonal weights, trapezoidal rule, hybrid cost)
 
 #ifdef MPC_PROFILE
@@ -186,21 +227,7 @@ int mpc_create(const mpc_config* cfg, int32_t max_batch, int32_t device, mpc_sol
     memset(s, 0, sizeof(*s));
     s->cfg = *cfg;
     s->plan = plan;
-    mpc::fill_problem<double>(*cfg, s->P64);
-    mpc::fill_problem<float>(*cfg, s->P32);
-#ifdef MPC_DEV_SWITCHES      // developer A/B switches read from the environment: compiled out of the shipped library
-    if (const char* e = getenv("MPC_NO_PIT")) { if (e[0] == '1') { s->P64.pit = 0; s->P32.pit = 0; } }      // serial sweeps only
-    if (const char* e = getenv("MPC_PIT_MU")) { char* end = nullptr; const double v = strtod(e, &end); if (end != e && v >= 0) { s->P64.pit_mu_min = v; s->P32.pit_mu_min = (float)v; } }      // threshold of the partitioned sweeps
-#endif
-    if (cfg->precision == MPC_MIXED) {
-        s->P32.tol = 1e-4f; s->P32.pit_mu_min = 1e-4f;        // phase 1 stops where fp32 residuals stop making sense
-        s->P64.n_cand = 1;                                   // phase 2 refines the winner
-        if (!(cfg->mu_init_dual > 0)) s->P64.mu_init_dual = 1e-5;      // phase 1 ended at a barrier of ~1e-5
-        s->P64.mu_init_warm = 1e-3;                          // instances phase 1 did not converge start phase 2 from its last iterate
-        s->P64.mu_strategy = 1;                              // the refinement follows the central path from mu = 1e-5 down: the monotone rule (fewer refinement iterations than
-                                                             // the adaptive one, which re-derives mu from the fp32 iterate's complementarity: CHANGELOG.md)
-        if (s->P64.max_iter > 40) s->P64.max_iter = 40;      // a refinement that needs more than that is a solve of its own (phase-1 failures would hold the launch for 100)
-    }
+    mpc::fill_records(*cfg, s->P64, s->P32);
     s->device = device;
     s->max_batch = max_batch;
     const size_t n = cfg->n;
@@ -222,6 +249,13 @@ int mpc_create(const mpc_config* cfg, int32_t max_batch, int32_t device, mpc_sol
         if (er == hipSuccess) er = hipMalloc((void**)&s->d_out, s->out_cap);
     }
     if (er == hipSuccess) er = hipMalloc((void**)&s->d_ngrid, Bm * 4);
+    if (er == hipSuccess) {      // the record table with the handle's own configuration as entry 0 (the only one until mpc_set_parameter_sets)
+        const TabLayout t(*cfg, 1);
+        std::vector<unsigned char> img(t.bytes, 0);
+        put_entry(*cfg, *cfg, 1, 0, img.data());
+        er = hipMalloc((void**)&s->d_tab, t.bytes);
+        if (er == hipSuccess) { s->tab_cap = 1; point_tables(s); er = hipMemcpy(s->d_tab, img.data(), t.bytes, hipMemcpyHostToDevice); }
+    }
     if (er == hipSuccess) { std::vector<int32_t> full(Bm, cfg->n); er = hipMemcpy(s->d_ngrid, full.data(), Bm * 4, hipMemcpyHostToDevice); }      // never uninitialised
     if (s->P64.n_via > 0) {
         if (er == hipSuccess) er = hipMalloc((void**)&s->d_nvia, Bm * 4);
@@ -311,10 +345,11 @@ void mpc_destroy(mpc_solver* s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
-    void* bufs[] = {s->d_gslots, s->d_gstage, s->d_stage, s->d_iters1, s->d_dual, s->d_rows_dropped, s->d_cwin, s->d_cexited, s->d_citsum, s->d_crec, s->d_winner, s->d_iters_total, s->d_nvia, s->d_via, s->d_ngrid, s->d_in, s->d_out};
+    void* bufs[] = {s->d_tab, s->d_set_of, s->d_gslots, s->d_gstage, s->d_stage, s->d_iters1, s->d_dual, s->d_rows_dropped, s->d_cwin, s->d_cexited, s->d_citsum, s->d_crec, s->d_winner, s->d_iters_total, s->d_nvia, s->d_via, s->d_ngrid, s->d_in, s->d_out};
     for (void* b : bufs) if (b) (void)hipFree(b);
     if (s->h_in) (void)hipHostFree(s->h_in);
     if (s->h_out) (void)hipHostFree(s->h_out);
+    if (s->h_tab) (void)hipHostFree(s->h_tab);
     if (s->ev0) (void)hipEventDestroy(s->ev0);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
     if (s->cev0) (void)hipEventDestroy(s->cev0);
@@ -336,6 +371,9 @@ static hipError_t launch_model(mpc_solver* s, const mpc::Problem<T>& P, int B, c
     a.stream = s->stream;
     a.B = B;
     a.gstage = s->d_gstage; a.gslots = s->d_gslots; a.n_gslots = s->n_gslots;
+    a.rec = &P;
+    if constexpr (sizeof(T) == 8) a.ptab = s->d_tab64; else a.ptab = s->d_tab32;
+    a.set_of = s->p_set_of;
     a.x0 = x0; a.xf = xf; a.u_prev = up; a.dt_prev = dtp; a.x_init = xi; a.u_init = ui; a.dt_init = dti; a.obst = ob;
     a.n_grid = s->use_ngrid ? s->d_ngrid : nullptr; a.n_via = s->p_nvia; a.via = s->p_via;
     // kept multipliers: a launch starts from them under dual_warm_start; in MPC_MIXED without it the block is only the hand-off from the fp32 phase
@@ -344,7 +382,7 @@ static hipError_t launch_model(mpc_solver* s, const mpc::Problem<T>& P, int B, c
     a.cc = {P.n_cand, s->d_cwin, s->d_cexited, s->d_citsum, s->d_crec, s->d_winner, s->d_iters_total, s->d_rows_dropped, s->d_dual, s->dual_words, dual_read};
     a.iters_add = (s->cfg.precision == MPC_MIXED && sizeof(T) == 8) ? s->d_iters1 : nullptr;
     a.x_out = xo; a.u_out = uo; a.dt_out = dto; a.status = st; a.iters = it;
-    return mpc::launch_solve<T, MODEL>(a, P);
+    return mpc::launch_solve<T, MODEL>(a);
 }
 
 template <typename T>
@@ -379,6 +417,7 @@ int mpc_solve_batch_device(mpc_solver* s, int32_t B, const double* d_x0, const d
     if (s->use_ngrid && B > s->ngrid_B) { set_err("mpc_solve_batch: B exceeds the batch the per-instance grid sizes were set for (mpc_set_grid_sizes)"); return MPC_EBATCH; }
     if (s->P64.n_via > 0 && s->p_nvia == s->d_nvia && s->nvia_B > 0 && B > s->nvia_B) {
         set_err("mpc_solve_batch: B exceeds the batch the via-points were set for (mpc_set_via_points)"); return MPC_EBATCH; }
+    if (s->p_set_of && B > s->sets_B) { set_err("mpc_solve_batch: B exceeds the batch the parameter sets were given for (mpc_set_parameter_sets)"); return MPC_EBATCH; }
     mpc_obstacles ob = {nullptr, nullptr, nullptr, nullptr, nullptr};
     if (s->cfg.max_obstacles > 0) {
         if (!d_obstacles || !d_obstacles->n_obstacles || !d_obstacles->n_vertices || !d_obstacles->vertices) {
@@ -550,6 +589,7 @@ int mpc_grid_update_device(mpc_solver* s, int32_t B, const double* d_x0_new, dou
     if (B <= 0) return MPC_OK;
     if (B > s->max_batch) { set_err("mpc_grid_update_device: B exceeds max_batch"); return MPC_EBATCH; }
     if (s->use_ngrid && B > s->ngrid_B) { set_err("mpc_grid_update_device: B exceeds the batch the per-instance grid sizes were set for (mpc_set_grid_sizes)"); return MPC_EBATCH; }
+    if (s->p_set_of && B > s->sets_B) { set_err("mpc_grid_update_device: B exceeds the batch the parameter sets were given for (mpc_set_parameter_sets)"); return MPC_EBATCH; }
     HIP_TRY(hipSetDevice(s->device));
     mpc::GridUpdateArgs a;
     memset(&a, 0, sizeof(a));
@@ -570,7 +610,7 @@ int mpc_grid_update_device(mpc_solver* s, int32_t B, const double* d_x0_new, dou
             HIP_TRY(hipStreamSynchronize(s->stream));
             s->use_ngrid = 1; s->ngrid_B = s->max_batch;
         }
-        a.mode = 1; a.n_grid = s->d_ngrid; a.n_min = n_min; a.n_max = n_max; a.dt_ref = s->cfg.dt_ref; a.hyst = dt_hyst_ratio;
+        a.mode = 1; a.n_grid = s->d_ngrid; a.n_min = n_min; a.n_max = n_max; a.dt_refs = s->d_dtref; a.set_of = s->p_set_of; a.hyst = dt_hyst_ratio;
     }
     hipLaunchKernelGGL(mpc::grid_update_kernel, dim3(B), dim3(64), (size_t)s->cfg.n * 5 * 8, s->stream, a);
     HIP_TRY(hipGetLastError());
@@ -651,6 +691,60 @@ int mpc_set_grid_sizes(mpc_solver* s, const int32_t* n_grid, int32_t B) {
     HIP_TRY(hipStreamSynchronize(s->stream));
     s->use_ngrid = 1;
     s->ngrid_B = B;
+    return MPC_OK;
+}
+
+int mpc_set_parameter_sets(mpc_solver* s, int32_t n_sets, const mpc_config* sets, int32_t B, const int32_t* set_of) {
+    g_err[0] = 0;
+    if (!s) { set_err("mpc_set_parameter_sets: null handle"); return MPC_EINVAL; }
+    if (!sets) { s->p_set_of = nullptr; s->sets_B = 0; return MPC_OK; }      // every instance: the handle's own configuration (table entry 0)
+    if (n_sets < 1 || n_sets > s->max_batch) { set_err("mpc_set_parameter_sets: n_sets out of range [1, max_batch]"); return MPC_EBATCH; }
+    if (B < 1 || B > s->max_batch) { set_err("mpc_set_parameter_sets: B out of range [1, max_batch]"); return MPC_EBATCH; }
+    if (!set_of) { set_err("mpc_set_parameter_sets: set_of is NULL"); return MPC_EINVAL; }
+    for (int i = 0; i < n_sets; ++i) {
+        const std::string why = mpc::parameter_set_error(s->cfg, sets[i]);
+        if (!why.empty()) { snprintf(g_err, sizeof(g_err), "mpc_set_parameter_sets: set %d: %s", i, why.c_str()); return MPC_EINVAL; }
+    }
+    for (int b = 0; b < B; ++b)
+        if (set_of[b] < 0 || set_of[b] >= n_sets) { snprintf(g_err, sizeof(g_err), "mpc_set_parameter_sets: set_of[%d] = %d is not in [0, n_sets)", b, set_of[b]); return MPC_EINVAL; }
+    HIP_TRY(hipSetDevice(s->device));
+    // nothing is changed before this point.  The pinned image: the table (entry 0 = the handle's own configuration, then the sets), then set_of as table entries
+    const size_t entries = (size_t)n_sets + 1;
+    const bool grow = entries > (size_t)s->tab_cap;
+    const size_t cap = grow ? entries : (size_t)s->tab_cap;
+    const TabLayout t(s->cfg, cap);
+    const size_t so_off = (t.bytes + 255) & ~(size_t)255, img_bytes = so_off + (size_t)B * 4;
+    if (img_bytes > s->h_tab_cap) {
+        unsigned char* h = nullptr;
+        HIP_TRY(hipHostMalloc((void**)&h, img_bytes, hipHostMallocDefault));
+        if (s->h_tab) (void)hipHostFree(s->h_tab);      // (no copy from it is in flight: every call waits for its own)
+        s->h_tab = h; s->h_tab_cap = img_bytes;
+    }
+    memset(s->h_tab, 0, img_bytes);
+    put_entry(s->cfg, s->cfg, cap, 0, s->h_tab);
+    for (int i = 0; i < n_sets; ++i) put_entry(s->cfg, sets[i], cap, (size_t)i + 1, s->h_tab);
+    int32_t* so = reinterpret_cast<int32_t*>(s->h_tab + so_off);
+    for (int b = 0; b < B; ++b) so[b] = set_of[b] + 1;
+    if (!s->d_set_of) HIP_TRY(hipMalloc((void**)&s->d_set_of, (size_t)s->max_batch * 4));
+    if (grow) {
+        // a launch still in flight may read the old table: wait for it before the table is replaced (a new one, then the old one freed)
+        unsigned char* d = nullptr;
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        HIP_TRY(hipMalloc((void**)&d, t.bytes));
+        (void)hipFree(s->d_tab);
+        s->d_tab = d; s->tab_cap = (int)cap;
+        point_tables(s);
+        HIP_TRY(hipMemcpyAsync(s->d_tab, s->h_tab, t.bytes, hipMemcpyHostToDevice, s->stream));
+    } else {
+        // entries 1 .. n_sets of each piece (entry 0, the handle's own record, stays as mpc_create wrote it); ordered behind every launch already enqueued on the stream
+        if (s->d_tab64) HIP_TRY(hipMemcpyAsync(s->d_tab64 + 1, s->h_tab + t.o64 + sizeof(mpc::Problem<double>), (size_t)n_sets * sizeof(mpc::Problem<double>), hipMemcpyHostToDevice, s->stream));
+        if (s->d_tab32) HIP_TRY(hipMemcpyAsync(s->d_tab32 + 1, s->h_tab + t.o32 + sizeof(mpc::Problem<float>), (size_t)n_sets * sizeof(mpc::Problem<float>), hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(hipMemcpyAsync(s->d_dtref + 1, s->h_tab + t.odt + 8, (size_t)n_sets * 8, hipMemcpyHostToDevice, s->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(s->d_set_of, so, (size_t)B * 4, hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    s->p_set_of = s->d_set_of;
+    s->sets_B = B;
     return MPC_OK;
 }
 

@@ -26,7 +26,9 @@ struct GridUpdateArgs {
     int32_t n_stride;
     int32_t mode;          // 0: fixed grid (shift), 1: variable grid (adapt + resample)
     int32_t n_min, n_max;
-    double dt_ref, hyst;
+    const double* dt_refs;    // dt_ref of every entry of the handle's record table (entry 0: its own configuration; mpc_set_parameter_sets)
+    const int32_t* set_of;    // [B] table entry of every instance, or NULL: entry 0 for all
+    double hyst;
     double* dual;          // [B][dual_words] kept multipliers or NULL
     int32_t dual_words, dual_ns;
 };
@@ -115,9 +117,10 @@ __global__ __launch_bounds__(64) void grid_update_kernel(GridUpdateArgs a) {
     }
     // ---- variable grid: adaptGridTimeBasedSingleStep + resampleTrajectory
     const double dt_old = a.dt[b];
+    const double dt_ref = a.dt_refs[a.set_of ? a.set_of[b] : 0];      // the instance's own dt_ref
     int n_new = n;
-    if (dt_old > a.dt_ref * (1.0 + a.hyst) && n < a.n_max) n_new = n + 1;
-    else if (dt_old < a.dt_ref * (1.0 - a.hyst) && n > a.n_min) n_new = n - 1;
+    if (dt_old > dt_ref * (1.0 + a.hyst) && n < a.n_max) n_new = n + 1;
+    else if (dt_old < dt_ref * (1.0 - a.hyst) && n > a.n_min) n_new = n - 1;
     if (n_new > ns) n_new = ns;
     if (n_new == n) return;
     const double dt_new = dt_old * (double)(n - 1) / (double)(n_new - 1);

@@ -1,6 +1,10 @@
 // mpc_problem.hpp -- host-side translation of the ABI's mpc_config (the reference's ROS
 // parameter set, src/controller.cpp:225-805) into the device-side Problem<T> record.
 #pragma once
+#include <cstdlib>
+#include <cstring>
+#include <string>
+
 #include "../../include/mpc_hip.h"
 #include "mpc_core.hpp"
 
@@ -143,6 +147,91 @@ inline void fill_problem(const mpc_config& c, mpc::Problem<T>& P) {
     P.line_search = c.line_search == MPC_LS_DEFAULT ? kDefaultLineSearch : (c.line_search == MPC_LS_FILTER ? 1 : 0);
     P.costx = (P.trapz || P.Ro != T(0)) ? 1 : 0;
     for (int i = 0; i < 3; ++i) if (P.Qo[i] != T(0) || P.Qfo[i] != T(0) || (P.ball && P.So[i] != T(0))) P.costx = 1;
+}
+
+// The two records a handle launches with (the fp64 one for MPC_FP64 and the refinement phase of MPC_MIXED, the fp32 one for MPC_FP32 and the main
+// phase of MPC_MIXED), padding zeroed: what mpc_create keeps for the handle's own configuration and mpc_set_parameter_sets builds for every set.
+inline void fill_records(const mpc_config& c, Problem<double>& P64, Problem<float>& P32) {
+    std::memset(&P64, 0, sizeof(P64));
+    std::memset(&P32, 0, sizeof(P32));
+    fill_problem<double>(c, P64);
+    fill_problem<float>(c, P32);
+#ifdef MPC_DEV_SWITCHES      // developer A/B switches read from the environment: compiled out of the shipped library
+    if (const char* e = getenv("MPC_NO_PIT")) { if (e[0] == '1') { P64.pit = 0; P32.pit = 0; } }      // serial sweeps only
+    if (const char* e = getenv("MPC_PIT_MU")) { char* end = nullptr; const double v = strtod(e, &end); if (end != e && v >= 0) { P64.pit_mu_min = v; P32.pit_mu_min = (float)v; } }      // threshold of the partitioned sweeps
+#endif
+    if (c.precision == MPC_MIXED) {
+        P32.tol = 1e-4f; P32.pit_mu_min = 1e-4f;             // phase 1 stops where fp32 residuals stop making sense
+        P64.n_cand = 1;                                      // phase 2 refines the winner
+        if (!(c.mu_init_dual > 0)) P64.mu_init_dual = 1e-5;  // phase 1 ended at a barrier of ~1e-5
+        P64.mu_init_warm = 1e-3;                             // instances phase 1 did not converge start phase 2 from its last iterate
+        P64.mu_strategy = 1;                                 // the refinement follows the central path from mu = 1e-5 down: the monotone rule (fewer refinement iterations than
+                                                             // the adaptive one, which re-derives mu from the fp32 iterate's complementarity: CHANGELOG.md)
+        if (P64.max_iter > 40) P64.max_iter = 40;            // a refinement that needs more than that is a solve of its own (phase-1 failures would hold the launch for 100)
+    }
+}
+
+// the integer fields of a record: what selects rows, terms, iteration caps and the kernel (a parameter set must leave every one of them as the handle has it)
+template <typename T>
+inline bool same_structure(const Problem<T>& a, const Problem<T>& b) {
+    auto eq = [](const auto& x, const auto& y) { return std::memcmp(&x, &y, sizeof(x)) == 0; };
+    return eq(a.model, b.model) && eq(a.n, b.n) && eq(a.dt_free, b.dt_free) && eq(a.xf_fixed, b.xf_fixed) && eq(a.objective, b.objective) &&
+           eq(a.integral_form, b.integral_form) && eq(a.collocation, b.collocation) && eq(a.has_Qf, b.has_Qf) && eq(a.rate_on, b.rate_on) &&
+           eq(a.max_iter, b.max_iter) && eq(a.n_obst, b.n_obst) && eq(a.n_vert, b.n_vert) && eq(a.obst_rows, b.obst_rows) &&
+           eq(a.footprint_kind, b.footprint_kind) && eq(a.dyn_obst, b.dyn_obst) && eq(a.fp_nv, b.fp_nv) && eq(a.ball, b.ball) && eq(a.via, b.via) &&
+           eq(a.n_via, b.n_via) && eq(a.vp_ordered, b.vp_ordered) && eq(a.n_cand, b.n_cand) && eq(a.cand_kind, b.cand_kind) &&
+           eq(a.cand_max_iter, b.cand_max_iter) && eq(a.cand_blend, b.cand_blend) && eq(a.hess_mode, b.hess_mode) && eq(a.trapz, b.trapz) &&
+           eq(a.hybrid, b.hybrid) && eq(a.costx, b.costx) && eq(a.acc_iter, b.acc_iter) && eq(a.line_search, b.line_search) && eq(a.pit, b.pit) &&
+           eq(a.mu_strategy, b.mu_strategy) && eq(a.max_ticks, b.max_ticks);
+}
+
+// The int32_t fields of mpc_config, in declaration order: a parameter set (mpc_set_parameter_sets) has to repeat every one of them.
+#define MPC_CONFIG_INT_FIELDS(X)                                                                                                                                   \
+    X(model) X(n) X(dt_free) X(xf_fixed) X(collocation) X(objective) X(integral_form) X(has_Qf) X(max_iter) X(precision) X(footprint_kind) X(max_obstacles)    \
+    X(max_vertices) X(max_obstacle_rows) X(terminal_ball) X(via_points_ordered) X(max_via_points) X(footprint_n_vertices) X(enable_dynamic_obstacles)          \
+    X(n_candidates) X(candidate_kind) X(candidate_max_iter) X(candidate_blend) X(dual_warm_start) X(hessian_mode) X(hybrid_cost_minimum_time)                 \
+    X(cost_integration) X(mu_strategy) X(stage_data) X(two_wave_min_batch) X(line_search) X(acceptable_iter) X(max_time_us)
+
+// Why a handle created with `handle` cannot solve instances with the parameter set `set` in the same launch (mpc_set_parameter_sets), or "" when it can.
+// A set may change the double fields of mpc_config and nothing that selects the kernel: every int32_t field equals the handle's, and so do the two
+// switches derived from doubles -- which control-rate bounds are finite (they switch rows on) and whether the off-diagonal cost terms are all zero (they
+// select the kernel level).  Then the integer fields of both records and the launch plan come out as the handle's (checked last, as a backstop).
+inline std::string parameter_set_error(const mpc_config& handle, const mpc_config& set) {
+    auto field = [](const char* name, int count, int i) { return count > 1 ? std::string(name) + "[" + std::to_string(i) + "]" : std::string(name); };
+#define MPC_SET_CHECK_INT(f)                                                                                                                                       \
+    {                                                                                                                                                              \
+        const int32_t* a = reinterpret_cast<const int32_t*>(&handle.f);                                                                                        \
+        const int32_t* b = reinterpret_cast<const int32_t*>(&set.f);                                                                                           \
+        const int cnt = (int)(sizeof(handle.f) / sizeof(int32_t));                                                                                             \
+        for (int i = 0; i < cnt; ++i)                                                                                                                             \
+            if (a[i] != b[i])                                                                                                                                     \
+                return field(#f, cnt, i) + " is " + std::to_string(b[i]) + " here and " + std::to_string(a[i]) + " in the handle's configuration";            \
+    }
+    MPC_CONFIG_INT_FIELDS(MPC_SET_CHECK_INT)
+#undef MPC_SET_CHECK_INT
+    if (const char* why = config_error(set)) return std::strncmp(why, "mpc_create: ", 12) == 0 ? std::string(why + 12) : std::string(why);
+    for (int j = 0; j < 2; ++j) {
+        const bool hl = handle.du_lb[j] > -1e29, sl = set.du_lb[j] > -1e29, hu = handle.du_ub[j] < 1e29, su = set.du_ub[j] < 1e29;
+        auto fin = [](bool f) { return f ? "finite" : "infinite"; };
+        if (hl != sl) return field("du_lb", 2, j) + " is " + fin(sl) + " here and " + fin(hl) + " in the handle's configuration";
+        if (hu != su) return field("du_ub", 2, j) + " is " + fin(su) + " here and " + fin(hu) + " in the handle's configuration";
+    }
+    Problem<double> h64, s64;
+    Problem<float> h32, s32;
+    fill_records(handle, h64, h32);
+    fill_records(set, s64, s32);
+    if (h64.costx != s64.costx || h32.costx != s32.costx) {
+        const double* terms[4] = {set.Q_offdiag, &set.R_offdiag, set.Qf_offdiag, set.terminal_ball_S_offdiag};
+        const char* names[4] = {"Q_offdiag", "R_offdiag", "Qf_offdiag", "terminal_ball_S_offdiag"};
+        const int cnt[4] = {3, 1, 3, 3};
+        if (s64.costx)
+            for (int t = 0; t < 4; ++t)
+                for (int i = 0; i < cnt[t]; ++i)
+                    if (terms[t][i] != 0.0) return field(names[t], cnt[t], i) + " is non-zero here and every off-diagonal cost term is zero in the handle's configuration";
+        return "the off-diagonal cost terms are all zero here and not in the handle's configuration (they select the kernel level)";
+    }
+    if (!same_structure(h64, s64) || !same_structure(h32, s32)) return "the integer fields of its problem record differ from the handle's";
+    return std::string();
 }
 
 

@@ -7,7 +7,7 @@
 #endif
 
 namespace mpc {
-template hipError_t launch_solve<MPC_INST_T, MPC_INST_MODEL>(const SolveLaunch&, const Problem<MPC_INST_T>&);
+template hipError_t launch_solve<MPC_INST_T, MPC_INST_MODEL>(const SolveLaunch&);
 template hipError_t solve_occupancy<MPC_INST_T, MPC_INST_MODEL>(const KernelChoice&, int*);
 #ifdef MPC_PROFILE
 template hipError_t solve_profile_add<MPC_INST_T, MPC_INST_MODEL>(long long*, int);

@@ -4,6 +4,7 @@
 // instantiated in the translation unit that includes this header (plain `hipcc mpc_capi.hip`, developer builds).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cstddef>
 #include <vector>
 
 #include "../../include/mpc_hip.h"
@@ -48,7 +49,8 @@ void mpc_ipm_wave_kernel(
     const double* __restrict__ dt_prev, const double* __restrict__ x_init, const double* __restrict__ u_init,
     const double* __restrict__ dt_init, mpc_obstacles obst, const int32_t* __restrict__ n_grid, const int32_t* __restrict__ n_via,
     const double* __restrict__ via, CandCtl cc, const int32_t* __restrict__ iters_add, double* __restrict__ x_out,
-    double* __restrict__ u_out, double* __restrict__ dt_out, int32_t* __restrict__ status, int32_t* __restrict__ iters, void* gstage, int* __restrict__ gslots, int n_gslots) {
+    double* __restrict__ u_out, double* __restrict__ dt_out, int32_t* __restrict__ status, int32_t* __restrict__ iters, void* gstage, int* __restrict__ gslots, int n_gslots,
+    const mpc::Problem<T>* __restrict__ ptab, const int32_t* __restrict__ set_of) {
     extern __shared__ __attribute__((aligned(16))) unsigned char mpc_smem[];
     T* sm = reinterpret_cast<T*>(mpc_smem);
     // problem record at the end of the dynamic LDS block (16-byte aligned); the layout stays in scalar registers
@@ -76,7 +78,22 @@ void mpc_ipm_wave_kernel(
         for (int e = lane; e < L.total; e += mpc::kWave) sm[e] = T(NAN);
         __syncthreads();
 #endif
-        if (lane == 0) { *Ps = P; Ps->n = n; }
+        if (set_of) {
+            // parameter sets in force: the instance's problem record is entry set_of[inst] of the handle's table, copied by the wave in 16-byte pieces; lane 0
+            // puts the instance's grid size into its piece on the way.  Without sets: the by-value record of the handle's own configuration, as before
+            // (profiles/r08_parameter_sets.md has both variants measured)
+            typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+            constexpr int kPieces = (int)(sizeof(mpc::Problem<T>) / 16);
+            static_assert(sizeof(mpc::Problem<T>) % 16 == 0 && kPieces <= mpc::kWave && offsetof(mpc::Problem<T>, n) == 4, "record copy: 16-byte pieces, n in the first one");
+            const u32x4* src = reinterpret_cast<const u32x4*>(ptab + (set_of ? set_of[inst] : 0));
+            if (lane < kPieces) {
+                u32x4 v = src[lane];
+                if (lane == 0) v.y = (unsigned)n;
+                reinterpret_cast<u32x4*>(Ps)[lane] = v;
+            }
+        } else if (lane == 0) {
+            *Ps = P; Ps->n = n;
+        }
         __syncthreads();
         mpc::IpmWave<T, MODEL, EXT, OBST, NSC, GS, W2> S(*Ps, Lv, sm, lane);
         int gslot = -1;
@@ -103,7 +120,6 @@ void mpc_ipm_wave_kernel(
         S.uprev[0] = u_prev ? T(u_prev[2 * inst]) : T(0);
         S.uprev[1] = u_prev ? T(u_prev[2 * inst + 1]) : T(0);
         S.dtprev = dt_prev ? T(dt_prev[inst]) : T(0);
-        // (indexed through the LDS copy: a run-time index into the by-value kernel argument would put the arrays into scratch memory)
         const int kind = NC > 1 ? Ps->cand_kind[cand] : 0;
         if (NC > 1) { S.my_cand = cand; S.iter_cap = Ps->cand_max_iter[cand]; S.win_ptr = cand > 0 ? cc.win + inst : nullptr; }
         if (cc.dual && cc.dual_read && cand == 0) S.dual_in = cc.dual + (long)inst * cc.dual_words;
@@ -205,6 +221,9 @@ void mpc_ipm_wave_kernel(
 // everything one launch needs besides the problem record (plain pointers: device memory of the handle / of the caller)
 struct SolveLaunch {
     KernelChoice k;             // which kernel, on which record (mpc_launch_plan.hpp)
+    const void* rec;            // the handle's own problem record (Problem<T>, host copy): the by-value argument, what every instance solves without parameter sets
+    const void* ptab;           // the handle's table of problem records (Problem<T>; entry 0 = its own configuration, then the parameter sets)
+    const int32_t* set_of;      // [B] table entry of every instance, or NULL: the by-value record for all
     hipStream_t stream;
     int B;
     const double *x0, *xf, *u_prev, *dt_prev, *x_init, *u_init, *dt_init;
@@ -244,7 +263,7 @@ auto select_kernel(const KernelChoice& k) -> decltype(&mpc_ipm_wave_kernel<T, MO
 }
 
 template <typename T, int MODEL>
-hipError_t launch_solve(const SolveLaunch& a, const Problem<T>& P) {
+hipError_t launch_solve(const SolveLaunch& a) {
     if (a.k.L.GSW > 0 && !a.gstage) return hipErrorInvalidConfiguration;
     auto kern = select_kernel<T, MODEL>(a.k);
     if (!kern) return hipErrorInvalidConfiguration;
@@ -252,8 +271,9 @@ hipError_t launch_solve(const SolveLaunch& a, const Problem<T>& P) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.k.lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(kern, dim3((unsigned)a.B * (unsigned)(P.n_cand > 1 ? P.n_cand : 1)), dim3(kWave), a.k.lds, a.stream, P, a.k.L, a.B, a.x0, a.xf, a.u_prev, a.dt_prev,
-                       a.x_init, a.u_init, a.dt_init, a.obst, a.n_grid, a.n_via, a.via, a.cc, a.iters_add, a.x_out, a.u_out, a.dt_out, a.status, a.iters, a.gstage, a.gslots, a.n_gslots);
+    hipLaunchKernelGGL(kern, dim3((unsigned)a.B * (unsigned)(a.cc.n_cand > 1 ? a.cc.n_cand : 1)), dim3(kWave), a.k.lds, a.stream, *static_cast<const Problem<T>*>(a.rec), a.k.L, a.B, a.x0, a.xf, a.u_prev, a.dt_prev,
+                       a.x_init, a.u_init, a.dt_init, a.obst, a.n_grid, a.n_via, a.via, a.cc, a.iters_add, a.x_out, a.u_out, a.dt_out, a.status, a.iters, a.gstage, a.gslots, a.n_gslots,
+                       static_cast<const Problem<T>*>(a.ptab), a.set_of);
     return hipSuccess;
 }
 
@@ -287,7 +307,7 @@ hipError_t solve_profile_add(long long* acc, int rows) {
 #else
 #define MPC_EXTERN_PROFILE(T, M)
 #endif
-#define MPC_EXTERN_LAUNCH(T, M) extern template hipError_t launch_solve<T, M>(const SolveLaunch&, const Problem<T>&); extern template hipError_t solve_occupancy<T, M>(const KernelChoice&, int*); \
+#define MPC_EXTERN_LAUNCH(T, M) extern template hipError_t launch_solve<T, M>(const SolveLaunch&); extern template hipError_t solve_occupancy<T, M>(const KernelChoice&, int*); \
                                 MPC_EXTERN_PROFILE(T, M)
 MPC_EXTERN_LAUNCH(double, 0) MPC_EXTERN_LAUNCH(double, 1) MPC_EXTERN_LAUNCH(double, 2) MPC_EXTERN_LAUNCH(double, 3)
 MPC_EXTERN_LAUNCH(float, 0) MPC_EXTERN_LAUNCH(float, 1) MPC_EXTERN_LAUNCH(float, 2) MPC_EXTERN_LAUNCH(float, 3)

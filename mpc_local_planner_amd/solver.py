@@ -173,6 +173,18 @@ class BatchSolver:
         a = np.ascontiguousarray(n_grid, dtype=np.int32)
         self._check(self._lib.mpc_set_grid_sizes(self._h, C.c_void_p(a.ctypes.data), int(a.shape[0])))
 
+    def set_parameter_sets(self, sets=None, set_of=None):
+        """Per-instance parameter sets for the following solves (mpc_set_parameter_sets): instance b solves with sets[set_of[b]], a complete MpcConfig
+        that differs from the handle's configuration in double fields only.  set_of=None: one set per instance (instance b uses sets[b]); sets=None
+        gives every instance the handle's own configuration again."""
+        if sets is None:
+            self._check(self._lib.mpc_set_parameter_sets(self._h, 0, None, 0, None))
+            return
+        sets = list(sets)
+        arr = (MpcConfig * len(sets))(*sets)
+        so = np.ascontiguousarray(np.arange(len(sets)) if set_of is None else set_of, dtype=np.int32)
+        self._check(self._lib.mpc_set_parameter_sets(self._h, len(sets), C.cast(arr, C.c_void_p), int(so.shape[0]), C.c_void_p(so.ctypes.data)))
+
     def set_via_points(self, n_via=None, via=None):
         """Via-points of the minimum_time_via_points objective for the following solves: n_via[B], via[B][cfg.max_via_points][3]
         (x, y, theta); None clears them."""

@@ -191,10 +191,10 @@ int32_t mpc_version(void) { return 700; }      // 0.7.0: mpc_set_parameter_sets 
 // history: 0.2.0: mpc_config grew (candidates, kept multipliers, hessian_mode), new entry points; 0.2.1: cost variants (off-diagonal weights, trapezoidal rule, hybrid cost)
 
 #ifdef MPC_PROFILE
-// developer build only (-DMPC_PROFILE): per-wave phase cycle counters of the last wave-kernel launch
+// developer build only (-DMPC_PROFILE): per-wave phase cycle counters of the last wave-kernel launch, mpc::kProfCols words per row
 int mpc_debug_profile(long long* out, int rows) {
 #ifdef MPC_SPLIT_BUILD
-    std::memset(out, 0, sizeof(long long) * 16 * (size_t)rows);
+    std::memset(out, 0, sizeof(long long) * mpc::kProfCols * (size_t)rows);
     hipError_t e = hipSuccess;
 #define MPC_PROFILE_ADD(T, M) if (e == hipSuccess) e = mpc::solve_profile_add<T, M>(out, rows);
     MPC_PROFILE_ADD(double, 0) MPC_PROFILE_ADD(double, 1) MPC_PROFILE_ADD(double, 2) MPC_PROFILE_ADD(double, 3)
@@ -202,7 +202,7 @@ int mpc_debug_profile(long long* out, int rows) {
 #undef MPC_PROFILE_ADD
     return (int)e;
 #else
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_mpc_prof), sizeof(long long) * 16 * (size_t)rows, 0, hipMemcpyDeviceToHost);
+    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_mpc_prof), sizeof(long long) * mpc::kProfCols * (size_t)rows, 0, hipMemcpyDeviceToHost);
 #endif
 }
 #endif

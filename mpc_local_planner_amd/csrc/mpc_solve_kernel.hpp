@@ -294,7 +294,7 @@ hipError_t solve_occupancy(const KernelChoice& k, int* out) {
 // mpc_solve_inst.hip: mpc_debug_profile adds up what each of them holds (the counters of the pairs that did not run stay zero)
 template <typename T, int MODEL>
 hipError_t solve_profile_add(long long* acc, int rows) {
-    std::vector<long long> b((size_t)16 * rows);
+    std::vector<long long> b((size_t)kProfCols * rows);
     hipError_t e = hipMemcpyFromSymbol(b.data(), HIP_SYMBOL(g_mpc_prof), sizeof(long long) * b.size(), 0, hipMemcpyDeviceToHost);
     for (size_t i = 0; e == hipSuccess && i < b.size(); ++i) acc[i] += b[i];
     return e;

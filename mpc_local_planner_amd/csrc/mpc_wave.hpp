@@ -37,7 +37,8 @@
 #include "mpc_dpp_blocks.inc"
 
 #ifdef MPC_PROFILE
-__device__ long long g_mpc_prof[4096][16];
+namespace mpc { constexpr int kProfCols = 24, kProfTicks = 14; }      // words per workgroup / phase + glue counters among them (mpc_wave_debug.hpp has the map)
+__device__ long long g_mpc_prof[4096][mpc::kProfCols];
 #endif
 
 #include "mpc_wave_layout.hpp"
@@ -242,9 +243,14 @@ struct IpmWave {
     // pair (which the compiler parks in a lane of a spill register when it runs out: 1/32 of the space), and the phases in between have the vector registers for themselves.
     // The 256-register kernels (W2) do that with the solve loop's scalars -- some sixty of them: barrier parameter, penalty, step data, the KKT error's pieces --, which is where
     // their scratch traffic came from (profiles/r06_wave_kernel_n20_two_waves.md).  Pure copies: results unchanged.
-    static constexpr bool kUniformScalars = W2;
+    // The one-wave kernels of the headline level in the LDS form take the same route for another reason: the solve loop's tests and barrier update branch on these values, and
+    // a value that comes out of a DPP reduction counts as divergent -- the compiler lowers every such branch with exec masks and keeps the loop's state per lane.  Read back
+    // as scalars the tests are scalar branches (profiles/r09_wave_kernel_caps100.md).  The other instantiations keep their code as it was measured.
+    static constexpr bool kUniformScalars = W2 || (EXT == 0 && !OBST && !GS);
     __device__ __forceinline__ static double uni_(double v) { return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v))); }
     __device__ __forceinline__ static float uni_(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+    __device__ __forceinline__ static int uni_(int v) { return __builtin_amdgcn_readfirstlane(v); }
+    __device__ __forceinline__ static long long uni_(long long v) { return ((long long)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)v); }
     // pow() of the device library is some 300 instructions and three dozen fp64 literals; inlined at its two (rarely executed) call sites of the solve loop the compiler
     // materialises those literals ONCE in front of the loop and -- in the 256-register kernels -- spills them to scratch for the whole solve.  There it is a call.
     __device__ __attribute__((noinline)) static T pow_cold(T a, T b) { return t_pow(a, b); }

@@ -13,22 +13,31 @@
 #endif
 
 #ifdef MPC_PROFILE
+// Row of g_mpc_prof (kProfCols words per workgroup): 0 ticks, 1 wall clock (100 MHz), 2 iterations, 3 factorisations, 4 trials, then the counters tk[0 .. kProfTicks):
+//   phases (MPC_TICK)       0 kkt  1 barrier_terms  2 backward  3 forward  4 post  5 logs0 (barrier_logs at the current point)  6 trial  7 accept  8 trial_setup
+//   glue (MPC_GAP_END)      9 kkt -> barrier terms (error, stop tests, barrier update)   10 barrier terms -> a factorisation (pow, delta; between two factorisations)
+//                          11 line-search set-up (post -> trial_setup -> first trial; between two trials)   12 last trial -> accept   13 accept -> kkt (loop back edge)
+// and 19 .. 21 the sweeps' inner counters.  Every tick of the loop lands in exactly one counter: a phase stamps its own begin and end, a glue section runs from the last
+// stamp to its MPC_GAP_END, so that the counters of an iteration add up to `ticks`.
 #define MPC_PROFILE_BEGIN \
-        long long tk[8] = {0, 0, 0, 0, 0, 0, 0, 0}; int nfac = 0, ntrial = 0; \
+        long long tk[mpc::kProfTicks] = {}; int nfac = 0, ntrial = 0; \
         const long long t_begin = __builtin_readcyclecounter(); \
+        long long t_lap = t_begin; \
         const long long w_begin = wall_clock64();
-#define MPC_TICK(i, stmt) { long long t0_ = __builtin_readcyclecounter(); stmt; tk[i] += __builtin_readcyclecounter() - t0_; }
+#define MPC_TICK(i, stmt) { long long t0_ = __builtin_readcyclecounter(); stmt; t_lap = __builtin_readcyclecounter(); tk[i] += t_lap - t0_; }
+#define MPC_GAP_END(i) { const long long t1_ = __builtin_readcyclecounter(); tk[i] += t1_ - t_lap; t_lap = t1_; }
 #define MPC_PROFILE_COUNT(c) ++c
 #define MPC_PROFILE_END \
         if (lane == 0 && blockIdx.x < 4096) { \
             long long* o = g_mpc_prof[blockIdx.x]; \
             o[0] = __builtin_readcyclecounter() - t_begin; o[1] = wall_clock64() - w_begin; o[2] = it; o[3] = nfac; o[4] = ntrial; \
-            for (int i = 0; i < 8; ++i) o[5 + i] = tk[i]; \
-            o[13] = prof_loop; o[14] = prof_setup; o[15] = prof_fwd_loop; if (prof_mult) o[10] = prof_mult;      /* (-DMPC_PROFILE_MULT: the multiplier recurrence instead of logs0) */ \
+            for (int i = 0; i < mpc::kProfTicks; ++i) o[5 + i] = tk[i]; \
+            o[19] = prof_loop; o[20] = prof_setup; o[21] = prof_fwd_loop; if (prof_mult) o[10] = prof_mult;      /* (-DMPC_PROFILE_MULT: the multiplier recurrence instead of logs0) */ \
         }
 #else
 #define MPC_PROFILE_BEGIN
 #define MPC_TICK(i, stmt) { stmt; }
+#define MPC_GAP_END(i) do { } while (0)
 #define MPC_PROFILE_COUNT(c) do { } while (0)
 #define MPC_PROFILE_END
 #endif

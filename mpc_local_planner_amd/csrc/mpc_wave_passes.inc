@@ -122,11 +122,15 @@
         bool stage, on[4], quad, mint, dtf;
         int k;
     };
-    __device__ __forceinline__ bool trial_fast_ok() const { return EXT == 0 && !GS && !W2 && !OBST && !(sizeof(T) == 8 && NTRB > 3) && L.n <= kWave; }      // (a kernel with clearance-row code only runs for handles that have rows)      // (the extended instantiations and the fp64 bicycle / front-wheel models keep those registers for what they add: no scratch memory anywhere)
-    __device__ __forceinline__ void trial_setup(TrialRegs& r, T dd) const {
-        MPC_PHASE_LANE
-        const int n = L.n, k = lane;
-        const T d = SCL(SC_D);
+    // kFusedPasses: the kernels whose launches can qualify (decided at compile time); such a kernel's post_pass() leaves TrialRegs filled from what it holds anyway
+    // (the fused step pass), trial_setup() stays the separate pass of the others
+    static constexpr bool kFusedPasses = EXT == 0 && !GS && !W2 && !OBST && !(sizeof(T) == 8 && NTRB > 3);
+    // (a fixed layout of at most 64 grid points per record decides it at compile time -- no instance of such a handle has more points than the record --: the headline
+    //  instantiation does not carry the generic trial path)
+    __device__ __forceinline__ bool trial_fast_ok() const { if constexpr (NSC > 0 && NSC <= kWave) return kFusedPasses; else return kFusedPasses && L.n <= kWave; }      // (a kernel with clearance-row code only runs for handles that have rows)      // (the extended instantiations and the fp64 bicycle / front-wheel models keep those registers for what they add: no scratch memory anywhere)
+    // the part of the set-up that no other pass holds: the switches, and the lane's interval (x_k, x_k+1 and their steps)
+    __device__ __forceinline__ void trial_setup_states(TrialRegs& r, int k) const {
+        const int n = L.n;
         r.k = k; r.stage = k < n - 1;
         r.quad = quad(); r.mint = mintime(); r.dtf = dtf(); r.nm1 = T(n - 1);
         r.dt_lb = P.dt_lb; r.dt_ub = P.dt_ub;
@@ -138,6 +142,12 @@
                 if (k + 1 < n - 1 || !fx(i)) r.dxn[i] = F(L.DX, i, k + 1);
             }
         }
+    }
+    __device__ __forceinline__ void trial_setup(TrialRegs& r, T dd) const {
+        MPC_PHASE_LANE
+        const int n = L.n, k = lane;
+        const T d = SCL(SC_D);
+        trial_setup_states(r, k);
         for (int j = 0; j < 2; ++j) {
             r.ulb[j] = P.u_lb[j]; r.uub[j] = P.u_ub[j];
             r.u[j] = r.stage ? F(L.U, j, k) : T(0); r.du[j] = r.stage ? F(L.DU, j, k) : T(0);

@@ -54,9 +54,14 @@
         U(theta_c, fobj);
         sync();
         int it = 0, status = ST_MAX_ITER, n_acc = 0;
-        const long long t_start = P.max_ticks > 0 ? (long long)wall_clock64() : 0ll;      // mpc_config.max_time_us: this solve's own clock
-        const T acc_tol = P.acc_tol;
-        const int acc_it = P.acc_iter;
+        // What the loop reads of the problem record, fetched ONCE and kept in scalar registers: P lives in LDS, so every P.x inside the loop is a ds_read the compiler may not
+        // hoist over the passes' LDS stores, waited for on the spot by a lone wave; tol / 10 was an IEEE division of the same two operands in every barrier update.
+        const T tol = uni_(P.tol), tol10 = uni_(P.tol / T(10));
+        const bool mu_monotone = uni_(P.mu_strategy) == 1;
+        const long long max_ticks = uni_(P.max_ticks);
+        const long long t_start = max_ticks > 0 ? (long long)wall_clock64() : 0ll;      // mpc_config.max_time_us: this solve's own clock
+        const T acc_tol = uni_(P.acc_tol);
+        const int acc_it = uni_(P.acc_iter);
         T e0 = T(0), logs_cur = T(0), dc_mu = T(-1), dc_val = T(0);
         T last_alpha = T(0), last_ad = T(0);
         int jam_streak = 0;
@@ -66,13 +71,14 @@
         bool have_logs = false;
         // Ipopt's filter (mpc_config.line_search = MPC_LS_FILTER), all of it in ONE register of the wave: lane f < flt_cap keeps theta of the f-th pair of the current barrier
         // problem, lane flt_cap + f its phi (a ring: the oldest pair is overwritten), lane 32 the infeasibility of the start point, lane 33 the mu the pairs belong to
-        const bool filter = P.line_search == 1;
+        const bool filter = uni_(P.line_search) == 1;
         T fstate = T(-1);
         int nfilt = 0, fpos = 0;
         static_assert(Algo<T>::flt_cap == 16, "the filter's pairs sit in DPP rows 0 and 1");
         MPC_PROFILE_BEGIN
         while (true) {
             Err er;
+            MPC_GAP_END(13);
             MPC_MARK("KKT_BEGIN");
             MPC_TICK(0, er = kkt_pass());
             U(er.rd, er.rp, er.cmin, er.cmax); U(er.csum, er.sum_mult, er.sum_bmult, er.theta); U(inv_cnt_mult, inv_cnt_bmult);
@@ -98,21 +104,21 @@
             e0 = err_value(er, T(0)); U(e0);
             // (t_max / t_min drop a NaN operand: the maxima inside e0 cannot carry one; the sums do -- ADVICE r03)
             if (!t_finite(e0) || !t_finite(er.theta) || !t_finite(er.sum_mult) || !t_finite(er.csum)) { status = ST_NUMERICAL; break; }
-            if (e0 <= P.tol) { status = ST_CONVERGED; break; }
+            if (e0 <= tol) { status = ST_CONVERGED; break; }
             // Ipopt's acceptable-level stop, counting half: acc_iter iterations in a row at the level acc_tol (mpc_config.acceptable_tol / _iter)
             n_acc = (acc_it > 0 && e0 <= acc_tol) ? n_acc + 1 : 0;
             if (acc_it > 0 && n_acc >= acc_it) { status = ST_CONVERGED; break; }
             if (it >= iter_cap) { status = ST_MAX_ITER; break; }
-            if (P.max_ticks > 0 && (long long)wall_clock64() - t_start > P.max_ticks) { status = ST_TIME_LIMIT; break; }
+            if (max_ticks > 0 && (long long)wall_clock64() - t_start > max_ticks) { status = ST_TIME_LIMIT; break; }
             if (win_ptr) {      // hedged candidate: one L2 read per iteration (all lanes, same word)
                 const int w = __builtin_amdgcn_readfirstlane(__hip_atomic_load(win_ptr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
                 if (w < my_cand) { status = ST_SUPERSEDED; break; }
             }
-            if (P.mu_strategy == 1 || endgame) {        // monotone Fiacco-McCormick (Ipopt's own default mu_strategy; the end game of the adaptive one)
+            if (mu_monotone || endgame) {        // monotone Fiacco-McCormick (Ipopt's own default mu_strategy; the end game of the adaptive one)
                 for (int guard = 0; guard < 50; ++guard) {
                     T emu = err_value(er, mu);
-                    if (emu <= Algo<T>::kappa_eps * mu && mu > P.tol / T(10)) {
-                        mu = t_max(P.tol / T(10), t_min(Algo<T>::kappa_mu * mu, pow_(mu, Algo<T>::theta_mu)));
+                    if (emu <= Algo<T>::kappa_eps * mu && mu > tol10) {
+                        mu = t_max(tol10, t_min(Algo<T>::kappa_mu * mu, pow_(mu, Algo<T>::theta_mu)));
                         rho = T(0);
                     } else break;
                 }
@@ -123,12 +129,13 @@
                 const T avg = er.csum * inv_cnt_bmult;
                 const T a_ = T(1) - t_min(last_alpha, last_ad);
                 const T sig = t_min(t_max(a_ * a_ * a_, Algo<T>::sigma_min), T(1));
-                T mu_new = t_min(t_max(sig * avg, P.tol / T(10)), mu_max);
+                T mu_new = t_min(t_max(sig * avg, tol10), mu_max);
                 mu_new = t_max(mu_new, t_min(mu, Algo<T>::mu_err_floor * e0));
-                if (mu_new <= P.tol) { mu_new = P.tol; endgame = true; }      // end game: from mu = tol on the monotone rule takes over (tol -> tol / 10 once the barrier problem is solved to kappa_eps mu): a solve stops at a point of the central path, as with the monotone strategy
+                if (mu_new <= tol) { mu_new = tol; endgame = true; }      // end game: from mu = tol on the monotone rule takes over (tol -> tol / 10 once the barrier problem is solved to kappa_eps mu): a solve stops at a point of the central path, as with the monotone strategy
                 if (mu_new != mu) { mu = mu_new; rho = T(0); }
             }
             U(mu, rho);
+            MPC_GAP_END(9);
             MPC_MARK("BARRIER_BEGIN");
             MPC_TICK(1, stage_barrier_terms(); sync());
             MPC_MARK("BARRIER_END");
@@ -141,25 +148,29 @@
             const bool started_zero = delta == T(0);
             bool ok = false;
             Fwd fw;
+            TrialRegs tregs;
             T dd = T(0), nu[3] = {T(0), T(0), T(0)}, curv = T(0);
             for (int ntry = 0; ntry <= 40; ++ntry) {
                 bool good, used_pit = false;
                 MPC_DBG_PIT_CHECK
+                MPC_GAP_END(10);
                 if (pit && mu > pit_floor()) {        // partitioned sweep; a broken-down combine pivot (or a singular stage pivot) falls back to the serial sweep; below pit_floor() the end game takes the serial sweeps
                     int gp_;
                     MPC_TICK(2, gp_ = backward_pit(delta, dc, dd, nu); sync());
                     good = used_pit = gp_ > 0;
-                    if (gp_ == 0) { MPC_TICK(2, good = backward_dpp(delta, dc, dd, nu); sync()); }
+                    if (gp_ == 0) { MPC_GAP_END(10); MPC_TICK(2, good = backward_dpp(delta, dc, dd, nu); sync()); }
                 } else { MPC_TICK(2, good = backward_dpp(delta, dc, dd, nu); sync()); }
                 MPC_PROFILE_COUNT(nfac);
                 MPC_DBG_NANCHECK_FIELDS
                 U(dd, nu[0], nu[1], nu[2]);
                 if (good) {
+                    MPC_GAP_END(10);
                     if (used_pit) { MPC_TICK(3, forward_pit(dd, nu, delta); sync()); }
                     else { MPC_TICK(3, forward_states(dd, nu, delta); sync()); }
                     MPC_DBG_NANCHECK_STEP
+                    MPC_GAP_END(10);
                     MPC_MARK("POST_BEGIN");
-                    MPC_TICK(4, fw = post_pass(dd, nu, tau));
+                    MPC_TICK(4, fw = post_pass<kFusedPasses>(dd, nu, tau, tregs));
                     U(fw.hdz, fw.clam, fw.dz2, fw.dphi); U(fw.a_p, fw.a_d, fw.dzmax, fw.nunu);
                     MPC_MARK("POST_END");
                     good = fw.finite;
@@ -192,7 +203,7 @@
             }
             T phi0;
             // sum of the barrier logs at the current point: it is the value of the last accepted trial (same point, mu-independent)
-            if (!have_logs) { MPC_TICK(5, logs_cur = barrier_logs(SCL(SC_D), T(0), false, dd)); have_logs = true; U(logs_cur); }
+            if (!have_logs) { MPC_GAP_END(11); MPC_TICK(5, logs_cur = barrier_logs(SCL(SC_D), T(0), false, dd)); have_logs = true; U(logs_cur); }
             const T rho_ls = filter ? T(0) : rho;       // the filter compares the barrier function itself
             phi0 = fobj - mu * logs_cur + rho_ls * theta;
             T Dm = fw.dphi - rho_ls * theta;
@@ -220,14 +231,17 @@
             }
             bool accepted = false, sw_arm = false;
             const bool fast_trials = trial_fast_ok();
-            TrialRegs tregs;
-            if (fast_trials) { MPC_TICK(5, trial_setup(tregs, dd)); }
+            MPC_GAP_END(11);
+            MPC_MARK("TSETUP_BEGIN");
+            if (fast_trials && !kFusedPasses) { MPC_TICK(8, trial_setup(tregs, dd)); }      // (kFusedPasses: post_pass has filled them)
+            MPC_MARK("TSETUP_END");
             T th_t = T(0), f_t = T(0), lg_t = T(0);
             for (int ls = 0; ls < Algo<T>::max_ls; ++ls) {
                 if (ls > 0) { alpha *= T(0.5); U(alpha); }
                 const bool below = filter && ls > 0 && alpha < a_min;      // below the shortest step worth trying: this trial point is the one taken with an emptied filter
                 T phit, tht;
                 T d_t = SCL(SC_D) + (dtf() ? alpha * SCL(SC_DD) : T(0)); U(d_t);
+                MPC_GAP_END(11);
                 MPC_MARK("TRIAL_BEGIN");
                 if (fast_trials) {
                     MPC_TICK(6, trial_eval(tregs, alpha, d_t, th_t, f_t, lg_t);
@@ -280,6 +294,7 @@
             if (acc_tol > T(0) && (!accepted || alpha < T(1e-6) * fw.a_p) && e0 <= acc_tol) { status = ST_CONVERGED; break; }
             if (!accepted && alpha * fw.dzmax < T(1e-14)) { status = ST_LINESEARCH; break; }
             MPC_DBG_NANCHECK_LS
+            MPC_GAP_END(12);
             MPC_MARK("ACCEPT_BEGIN");
             MPC_TICK(7, accept(alpha, fw.a_d); sync());
             MPC_MARK("ACCEPT_END");

@@ -8,11 +8,20 @@
     __device__ __forceinline__ void ftb_ratio(T ival, T dval, T& r) const { r = t_max(r, -dval * ival); }
     __device__ __forceinline__ T ftb_alpha(T r, T tau) const { return r > tau ? tau / r : T(1); }
 
-    __device__ __forceinline__ Fwd post_pass(T dd, const T nu[3], T tau) const {
+    // REC (the fused step pass, kernels with kFusedPasses; meaningful where trial_fast_ok(): one grid point per lane): the pass also leaves in `tr` what trial_setup() would
+    // collect next -- the controls, slacks and their steps it has just loaded and computed (the same expressions: -(row_val + s) - row_jdz), the bounds --, so that the line
+    // search starts without another pass over the same LDS words.
+    template <bool REC>
+    __device__ __forceinline__ Fwd post_pass(T dd, const T nu[3], T tau, TrialRegs& tr) const {
         MPC_PHASE_LANE
         const int n = L.n;
         const T d = SCL(SC_D);
         T hdz = T(0), clam = T(0), dz2 = T(0), dphi = T(0), r_p = T(0), r_d = T(0), dzmax = T(0);
+        if constexpr (REC) {
+            trial_setup_states(tr, lane);
+            for (int j = 0; j < 2; ++j) { tr.ulb[j] = P.u_lb[j]; tr.uub[j] = P.u_ub[j]; tr.u[j] = tr.du[j] = T(0); }
+            for (int q = 0; q < 4; ++q) { tr.on[q] = false; tr.s[q] = T(1); tr.ds[q] = T(0); }
+        }
         if (lane == 0) {
             if (dtf()) {
                 T dl = d - P.dt_lb, du = P.dt_ub - d;
@@ -51,6 +60,7 @@
                     ftb_ratio(t_rcp(pl), mu * idl - pl - (pl * idl) * du_, r_d);
                     ftb_ratio(t_rcp(pu), mu * idu - pu + (pu * idu) * du_, r_d);
                     dz2 += du_ * du_; dzmax = t_max(dzmax, t_abs(du_));
+                    if constexpr (REC) { tr.u[j] = u; tr.du[j] = du_; }
                 }
                 for (int i = 0; i < 3; ++i) {
                     clam += C_(i, k) * F(L.LAMN, i, k);        // (a non-finite multiplier makes this sum non-finite: tested below)
@@ -115,6 +125,7 @@
                 dphi -= (mu * is) * ds;
                 ftb_ratio(is, ds, r_p);
                 ftb_ratio(t_rcp(y), dy, r_d);
+                if constexpr (REC) { tr.on[q] = true; tr.s[q] = s; tr.ds[q] = ds; }
             }
             if (nM() > 0 && k >= 1 && k < n - 1) {
                 for (int m0 = 0; m0 < nM(); m0 += kRowGroup) {

@@ -21,11 +21,12 @@ r = s.solve(*inp, obstacles=obstacles)
 print(what, sys.argv[2:] , "kernel ms", s.last_kernel_ms(), "lds", s.lds_bytes(), "converged", (r.status == 0).mean(), "iters", r.iters.mean())
 lib = _lib.load()
 R = min(B, 4096)
-buf = np.zeros((R, 16), dtype=np.int64)
+buf = np.zeros((R, 24), dtype=np.int64)      # mpc::kProfCols words per workgroup (csrc/mpc_wave_debug.hpp has the map)
 lib.mpc_debug_profile(buf.ctypes.data_as(C.c_void_p), C.c_int(R))
-names = ["ticks", "wall100MHz", "iters", "nfac", "ntrial", "kkt", "barrier_terms", "backward", "forward", "post", "logs0", "trial", "accept", "bwd_loop", "bwd_setup", "fwd_loop"]
+names = ["ticks", "wall100MHz", "iters", "nfac", "ntrial", "kkt", "barrier_terms", "backward", "forward", "post", "logs0", "trial", "accept", "trial_setup", "glue_kkt_to_barrier", "glue_barrier_to_fac", "glue_ls_setup", "glue_trial_to_accept", "glue_back_edge", "bwd_loop", "bwd_setup", "fwd_loop"]
 print("tick rate GHz ~", (buf[:, 0] / (buf[:, 1] / 100e6)).mean() / 1e9)
 tot = buf.sum(0).astype(float)
 print("per iteration (ticks):", {k: round(tot[i] / tot[2]) for i, k in enumerate(names) if i not in (1, 2, 3, 4)})
+print("phases + glue per iteration:", round(tot[5:19].sum() / tot[2]), "of", round(tot[0] / tot[2]), "ticks; glue alone", round(tot[14:19].sum() / tot[2]))
 print("factorisations per iteration", tot[3] / tot[2], "trials per iteration", tot[4] / tot[2])
 print("per-sweep ticks: backward", tot[7] / tot[3], "forward", tot[8] / (tot[2]), "trial", tot[11] / max(1, tot[4]))

@@ -15,9 +15,9 @@ for tag, kw, ob in (("with obstacles", dict(max_obstacles=O, max_vertices=V, max
     r = s.solve(x0, xf, up, dtp, obstacles=ob)
     print(tag, "kernel ms", s.last_kernel_ms(), "iters", r.iters.mean(), "conv", (r.status == 0).mean())
     lib = _lib.load()
-    buf = np.zeros((B, 16), dtype=np.int64)
+    buf = np.zeros((B, 24), dtype=np.int64)      # mpc::kProfCols words per workgroup (csrc/mpc_wave_debug.hpp has the map)
     lib.mpc_debug_profile(buf.ctypes.data_as(C.c_void_p), C.c_int(B))
-    names = ["ticks", "wall100MHz", "iters", "nfac", "ntrial", "kkt", "barrier_terms", "backward", "forward", "post", "logs0", "trial", "accept", "bwd_loop", "bwd_setup", "fwd_loop"]
+    names = ["ticks", "wall100MHz", "iters", "nfac", "ntrial", "kkt", "barrier_terms", "backward", "forward", "post", "logs0", "trial", "accept", "trial_setup", "glue_kkt_to_barrier", "glue_barrier_to_fac", "glue_ls_setup", "glue_trial_to_accept", "glue_back_edge", "bwd_loop", "bwd_setup", "fwd_loop"]
     it = buf[:, 2].sum()
     print("  per iteration ticks:", {k: round(float(buf[:, i].sum() / it)) for i, k in enumerate(names) if i >= 5 or i == 0}, "fac/it", round(buf[:, 3].sum() / it, 3), "trials/it", round(buf[:, 4].sum() / it, 3))
     s.close()

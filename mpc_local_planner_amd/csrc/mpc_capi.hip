@@ -8,6 +8,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/mpc_hip.h"
@@ -37,10 +38,22 @@ void set_err(const char* what) { snprintf(g_err, sizeof(g_err), "%s", what); }
 
 }  // namespace
 
+// One device or pinned allocation of the handle.  Every one of them is in mpc_solver::bufs: mpc_create allocates and fills from that table, mpc_reset refills from
+// it, mpc_destroy frees from it, and a buffer that is allocated or replaced later (buf_alloc) stays in its entry.
+enum { FILL_NONE = -1, FILL_NGRID = 256, FILL_TAB0 = 257 };      // 0 .. 255: that byte in every byte; the uniform grid size in every word; table entry 0
+struct Buf {
+    void** p;           // where the handle keeps the pointer (NULL there: not allocated)
+    size_t bytes;       // what mpc_create allocates (0: nothing), then the size of the allocation
+    int fill;           // the idle contents mpc_create writes
+    bool reset, pinned; // mpc_reset writes them again; host memory (hipHostMalloc)
+};
+enum { BUF_TAB, BUF_SET_OF, BUF_H_TAB, BUF_STAGE, BUF_H_IN };      // the entries other entry points ask for (declare_buffers assigns them by index)
+
 struct mpc_solver {
     mpc_config cfg;
     mpc::Problem<double> P64;   // the handle's own records (host copies: what selects the kernel and sizes the launch)
     mpc::Problem<float> P32;
+    std::vector<Buf> bufs;
     // device table of problem records (mpc_set_parameter_sets): entry 0 is the handle's own configuration, entries 1 .. n_sets the sets in force; a solve
     // kernel copies entry set_of[b] (entry 0 while p_set_of is NULL) into the LDS of instance b.  One allocation: fp64 records | fp32 records | dt_ref per entry
     unsigned char* d_tab;
@@ -51,8 +64,7 @@ struct mpc_solver {
     int32_t* d_set_of;                  // [max_batch] table entry of instance b (1 + its set), allocated by the first mpc_set_parameter_sets
     const int32_t* p_set_of;            // what the kernels read: d_set_of while sets are in force, else NULL
     int sets_B;                         // batch size the sets were given for (solves must not exceed it)
-    unsigned char* h_tab;               // pinned staging of the table uploads
-    size_t h_tab_cap;
+    unsigned char* h_tab;               // pinned staging of the table uploads, grows on demand
     mpc::LaunchPlan plan;       // which kernel each launch runs (mpc_launch_plan.hpp)
     void* d_gstage;             // 8 pools of n_gslots blocks (plan.block_bytes each), NULL when the plan has none
     int* d_gslots;              // [8][n_gslots] claim words of the blocks (0 = free)
@@ -62,10 +74,8 @@ struct mpc_solver {
     int max_batch;
     hipStream_t stream;
     hipEvent_t ev0, ev1;
-    // staging for the host-pointer entry point
-    // staging of the host-pointer entry point: ONE pinned host block and ONE device block each way (one H2D and one D2H per call)
+    // staging of the host-pointer entry point: ONE pinned host block and ONE device block each way (one H2D and one D2H per call; mpc::step_pieces)
     unsigned char *h_in, *h_out, *d_in, *d_out;
-    size_t in_cap, out_cap;
     int32_t* d_ngrid;
     int32_t *d_nvia;            // own copy of the via-point counts / poses (mpc_set_via_points) ...
     double *d_via;
@@ -80,13 +90,26 @@ struct mpc_solver {
     int32_t *d_winner, *d_iters_total;
     int32_t* d_rows_dropped;    // per instance: clearance rows that did not fit (solvers with obstacles)
     double* d_dual;             // per instance: multipliers of the last converged solve (dual_warm_start)
-    void* d_stage = nullptr;    // device staging of the host-pointer helpers (mpc_costmap_to_obstacles, mpc_check_feasibility): kept across calls, grows on demand
-    size_t stage_bytes = 0;
+    void* d_stage;              // device staging of the host-pointer helpers (mpc_costmap_to_obstacles, mpc_check_feasibility): kept across calls, grows on demand
     int dual_words;
     int32_t* last_status;       // device pointers of the most recent solve (mpc_last_candidates without candidates)
     int32_t* last_iters;
     bool timed;
 };
+
+static void buf_free(Buf& b) {
+    if (*b.p) (void)(b.pinned ? hipHostFree(*b.p) : hipFree(*b.p));
+    *b.p = nullptr; b.bytes = 0;
+}
+// a new allocation first, then the one it replaces (if any) freed: a failure leaves the buffer as it was
+static hipError_t buf_alloc(Buf& b, size_t bytes) {
+    void* q = nullptr;
+    const hipError_t e = b.pinned ? hipHostMalloc(&q, bytes, hipHostMallocDefault) : hipMalloc(&q, bytes);
+    if (e != hipSuccess) return e;
+    buf_free(b);
+    *b.p = q; b.bytes = bytes;
+    return hipSuccess;
+}
 
 // which XCC ids the device's workgroups run on (bit i of *mask: some workgroup saw HW_REG_XCC_ID & 7 == i): 8 bits on an MI355X, 1 in a partitioned mode
 namespace mpc {
@@ -94,35 +117,39 @@ __global__ void xcc_probe_kernel(unsigned* mask) {
     if (threadIdx.x == 0) atomicOr(mask, 1u << ((unsigned)__builtin_amdgcn_s_getreg((3 << 11) | 20) & 7u));
 }
 }  // namespace mpc
-// resident workgroups per CU of the solve kernel that serves a kernel choice (per precision and model: the instantiations live in mpc_solve_inst.hip)
-static hipError_t kernel_occupancy(bool f32, int model, const mpc::KernelChoice& k, int* out) {
-#ifdef MPC_DEV_ONE_MODEL
-    (void)model; return f32 ? hipErrorInvalidConfiguration : mpc::solve_occupancy<double, MPC_DEV_ONE_MODEL>(k, out);
+
+// The one place where the precision and mpc_config.model become the template arguments of the solve kernel's host functions (instantiated per pair in
+// mpc_solve_inst.hip): calls f(T(), std::integral_constant<int, MODEL>()).
+template <typename F>
+static hipError_t with_model(bool f32, int model, F f) {
+#ifdef MPC_DEV_ONE_MODEL       // developer builds (fast compile, asm inspection): only the fp64 instantiations of ONE model exist (-DMPC_DEV_ONE_MODEL=<model id>)
+    (void)model; return f32 ? hipErrorInvalidConfiguration : f(double(), std::integral_constant<int, MPC_DEV_ONE_MODEL>());
 #else
-#define MPC_OCC(M) (f32 ? mpc::solve_occupancy<float, M>(k, out) : mpc::solve_occupancy<double, M>(k, out))
+    auto prec = [&](auto m) { return f32 ? f(float(), m) : f(double(), m); };
     switch (model) {
-        case MPC_MODEL_UNICYCLE: return MPC_OCC(mpc::MODEL_UNICYCLE);
-        case MPC_MODEL_SIMPLE_CAR: return MPC_OCC(mpc::MODEL_SIMPLE_CAR);
-        case MPC_MODEL_SIMPLE_CAR_FRONT: return MPC_OCC(mpc::MODEL_SIMPLE_CAR_FRONT);
-        default: return MPC_OCC(mpc::MODEL_KINEMATIC_BICYCLE);
+        case MPC_MODEL_UNICYCLE: return prec(std::integral_constant<int, mpc::MODEL_UNICYCLE>());
+        case MPC_MODEL_SIMPLE_CAR: return prec(std::integral_constant<int, mpc::MODEL_SIMPLE_CAR>());
+        case MPC_MODEL_SIMPLE_CAR_FRONT: return prec(std::integral_constant<int, mpc::MODEL_SIMPLE_CAR_FRONT>());
+        default: return prec(std::integral_constant<int, mpc::MODEL_KINEMATIC_BICYCLE>());
     }
-#undef MPC_OCC
 #endif
+}
+// resident workgroups per CU of the solve kernel that serves a kernel choice
+static hipError_t kernel_occupancy(bool f32, int model, const mpc::KernelChoice& k, int* out) {
+    return with_model(f32, model, [&](auto t, auto m) { return mpc::solve_occupancy<decltype(t), decltype(m)::value>(k, out); });
 }
 
 // Device staging of the host-pointer helpers: ONE allocation kept in the handle and carved into 256-byte aligned pieces (these calls sit in a B = 1 control
 // loop next to a sub-millisecond solve; a hipMalloc / hipFree pair per temporary per call cost more than the kernels they feed).  Grows on demand, freed by mpc_destroy.
 static hipError_t stage_carve(mpc_solver* s, const size_t* sz, int count, void** out) {
-    size_t total = 0;
-    for (int i = 0; i < count; ++i) total += (sz[i] + 255) & ~(size_t)255;
-    if (total > s->stage_bytes) {
-        if (s->d_stage) { (void)hipStreamSynchronize(s->stream); (void)hipFree(s->d_stage); s->d_stage = nullptr; s->stage_bytes = 0; }
-        const hipError_t er = hipMalloc(&s->d_stage, total);
-        if (er != hipSuccess) return er;
-        s->stage_bytes = total;
+    mpc::Packer total, p;
+    for (int i = 0; i < count; ++i) total.take(sz[i]);
+    Buf& b = s->bufs[BUF_STAGE];
+    if (total.off > b.bytes) {
+        if (s->d_stage) { (void)hipStreamSynchronize(s->stream); buf_free(b); }
+        if (const hipError_t er = buf_alloc(b, total.off)) return er;
     }
-    size_t off = 0;
-    for (int i = 0; i < count; ++i) { out[i] = (char*)s->d_stage + off; off += (sz[i] + 255) & ~(size_t)255; }
+    for (int i = 0; i < count; ++i) out[i] = (char*)s->d_stage + p.take(sz[i]);
     return hipSuccess;
 }
 
@@ -130,9 +157,10 @@ static hipError_t stage_carve(mpc_solver* s, const size_t* sz, int count, void**
 struct TabLayout {
     size_t o64, o32, odt, bytes;
     TabLayout(const mpc_config& c, size_t entries) {
-        auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-        const size_t b64 = c.precision != MPC_FP32 ? entries * sizeof(mpc::Problem<double>) : 0, b32 = c.precision != MPC_FP64 ? entries * sizeof(mpc::Problem<float>) : 0;
-        o64 = 0; o32 = up(b64); odt = o32 + up(b32); bytes = odt + up(entries * 8);
+        mpc::Packer p;
+        o64 = p.take(c.precision != MPC_FP32 ? entries * sizeof(mpc::Problem<double>) : 0);
+        o32 = p.take(c.precision != MPC_FP64 ? entries * sizeof(mpc::Problem<float>) : 0);
+        odt = p.take(entries * 8); bytes = p.off;
     }
 };
 
@@ -152,6 +180,54 @@ static void point_tables(mpc_solver* s) {
     s->d_tab64 = s->cfg.precision != MPC_FP32 ? reinterpret_cast<mpc::Problem<double>*>(s->d_tab + t.o64) : nullptr;
     s->d_tab32 = s->cfg.precision != MPC_FP64 ? reinterpret_cast<mpc::Problem<float>*>(s->d_tab + t.o32) : nullptr;
     s->d_dtref = reinterpret_cast<double*>(s->d_tab + t.odt);
+}
+
+// The handle's buffers: which of them its configuration gets at mpc_create (the others stay at 0 bytes), their sizes, the idle contents and whether mpc_reset
+// restores those -- the multipliers (forgotten) and the words that restore themselves unless a launch was aborted: the claim words of the blocks and the
+// candidate bookkeeping.  Parameter sets, grid sizes and via-points are kept by mpc_reset.
+static void declare_buffers(mpc_solver* s) {
+    const mpc_config& c = s->cfg;
+    const size_t Bm = (size_t)s->max_batch, n = (size_t)c.n, slots = 8 * (size_t)s->n_gslots, dual = Bm * (size_t)s->dual_words * 8;
+    const bool pool = s->plan.block_bytes > 0, cand = s->P32.n_cand > 1, via = s->P64.n_via > 0;
+    const mpc::StepPieces cap = mpc::step_pieces(c, Bm, true, true, true, true, true);
+    int gstage_fill = FILL_NONE;
+#ifdef MPC_DEV_SWITCHES
+    // developer check (scripts/dev/gs_sweep.py under MPC_POISON_GSTAGE=1): every word of the pool starts as a NaN pattern, so a word that some path consumes before writing it shows up in the results
+    if (const char* e = getenv("MPC_POISON_GSTAGE")) { if (e[0] == '1') gstage_fill = 0xFF; }
+#endif
+    auto add = [s](auto* where, size_t bytes, int fill = FILL_NONE, bool reset = false, bool pinned = false) { s->bufs.push_back({(void**)where, bytes, fill, reset, pinned}); };
+    s->bufs.resize(BUF_H_IN + 1);      // the entries other entry points ask for by index, then the rest
+    s->bufs[BUF_TAB] = {(void**)&s->d_tab, TabLayout(c, 1).bytes, FILL_TAB0, false, false};      // replaced by a larger one when mpc_set_parameter_sets needs more entries
+    s->bufs[BUF_SET_OF] = {(void**)&s->d_set_of, 0, FILL_NONE, false, false};                    // [max_batch], allocated by the first mpc_set_parameter_sets
+    s->bufs[BUF_H_TAB] = {(void**)&s->h_tab, 0, FILL_NONE, false, true};
+    s->bufs[BUF_STAGE] = {(void**)&s->d_stage, 0, FILL_NONE, false, false};
+    s->bufs[BUF_H_IN] = {(void**)&s->h_in, cap.in_bytes, FILL_NONE, false, true};
+    add(&s->h_out, cap.out_bytes, FILL_NONE, false, true);
+    add(&s->d_in, cap.in_bytes);
+    add(&s->d_out, cap.out_bytes);
+    add(&s->d_ngrid, Bm * 4, FILL_NGRID);                  // never uninitialised
+    add(&s->d_nvia, via ? Bm * 4 : 0, 0);
+    add(&s->d_via, via ? Bm * (size_t)s->P64.n_via * 3 * 8 : 0);
+    add(&s->d_rows_dropped, c.max_obstacles > 0 ? Bm * 4 : 0, 0);
+    add(&s->d_iters1, c.precision == MPC_MIXED ? Bm * 4 : 0);
+    add(&s->d_gstage, pool ? slots * s->plan.block_bytes + (size_t)mpc::GlobalStage::kPrefetchPad * 8 : 0, gstage_fill);
+    add(&s->d_gslots, pool ? slots * 4 : 0, 0, true);
+    add(&s->d_dual, dual, 0, true);
+    add(&s->d_cwin, cand ? Bm * 4 : 0, 0x7f, true);
+    add(&s->d_cexited, cand ? Bm * 4 : 0, 0, true);
+    add(&s->d_citsum, cand ? Bm * 4 : 0, 0, true);
+    add(&s->d_crec, cand ? (size_t)s->P32.n_cand * Bm * (5 * n + 3 + (size_t)s->dual_words) * 8 : 0);
+    add(&s->d_winner, cand ? Bm * 4 : 0);
+    add(&s->d_iters_total, cand ? Bm * 4 : 0);
+}
+
+static hipError_t buf_fill(const mpc_solver* s, const Buf& b) {
+    if (b.fill == FILL_NONE) return hipSuccess;
+    if (b.fill < 256) return hipMemset(*b.p, b.fill, b.bytes);
+    std::vector<unsigned char> img(b.bytes, 0);
+    if (b.fill == FILL_TAB0) put_entry(s->cfg, s->cfg, 1, 0, img.data());
+    else for (size_t i = 0; i < b.bytes / 4; ++i) reinterpret_cast<int32_t*>(img.data())[i] = s->cfg.n;
+    return hipMemcpy(*b.p, img.data(), b.bytes, hipMemcpyHostToDevice);
 }
 
 extern "C" {
@@ -187,8 +263,7 @@ void mpc_config_defaults(mpc_config* c) {
 }
 
 const char* mpc_last_error(void) { return g_err; }
-int32_t mpc_version(void) { return 700; }      // 0.7.0: mpc_set_parameter_sets (per-instance double parameters of mpc_config, one launch).  0.6.0: mpc_config.two_wave_min_batch and mpc_config.line_search took the last reserved words (same size).  0.5.0: mpc_config.stage_data took a reserved word (same size); a solve restores clearance rows that jam.  0.4.0: mpc_config.mu_strategy / max_time_us took reserved words (same size), MPC_TIME_LIMIT; a solve accepts factorisations on their inertia
-// history: 0.2.0: mpc_config grew (candidates, kept multipliers, hessian_mode), new entry points; 0.2.1: cost variants (off-diagonal weights, trapezoidal rule, hybrid cost)
+int32_t mpc_version(void) { return 700; }      // 0.7.0 (CHANGELOG.md has what each version brought)
 
 #ifdef MPC_PROFILE
 // developer build only (-DMPC_PROFILE): per-wave phase cycle counters of the last wave-kernel launch, mpc::kProfCols words per row
@@ -196,10 +271,9 @@ int mpc_debug_profile(long long* out, int rows) {
 #ifdef MPC_SPLIT_BUILD
     std::memset(out, 0, sizeof(long long) * mpc::kProfCols * (size_t)rows);
     hipError_t e = hipSuccess;
-#define MPC_PROFILE_ADD(T, M) if (e == hipSuccess) e = mpc::solve_profile_add<T, M>(out, rows);
-    MPC_PROFILE_ADD(double, 0) MPC_PROFILE_ADD(double, 1) MPC_PROFILE_ADD(double, 2) MPC_PROFILE_ADD(double, 3)
-    MPC_PROFILE_ADD(float, 0) MPC_PROFILE_ADD(float, 1) MPC_PROFILE_ADD(float, 2) MPC_PROFILE_ADD(float, 3)
-#undef MPC_PROFILE_ADD
+    for (int f32 = 0; f32 < 2; ++f32)      // every pair of the split build (a -DMPC_DEV_ONE_MODEL build is a single translation unit: the other branch)
+        for (int model = 0; model < 4 && e == hipSuccess; ++model)
+            e = with_model(f32 != 0, model, [&](auto t, auto m) { return mpc::solve_profile_add<decltype(t), decltype(m)::value>(out, rows); });
     return (int)e;
 #else
     return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_mpc_prof), sizeof(long long) * mpc::kProfCols * (size_t)rows, 0, hipMemcpyDeviceToHost);
@@ -222,52 +296,15 @@ int mpc_create(const mpc_config* cfg, int32_t max_batch, int32_t device, mpc_sol
     HIP_TRY(hipSetDevice(device));
     const mpc::LaunchPlan plan = mpc::make_launch_plan(*cfg);
     if (const char* why = mpc::plan_error(plan)) { set_err(why); return MPC_EINVAL; }
-    mpc_solver* s = new (std::nothrow) mpc_solver;
+    mpc_solver* s = new (std::nothrow) mpc_solver();      // (every field zero)
     if (!s) return MPC_ENOMEM;
-    memset(s, 0, sizeof(*s));
     s->cfg = *cfg;
     s->plan = plan;
     mpc::fill_records(*cfg, s->P64, s->P32);
     s->device = device;
     s->max_batch = max_batch;
-    const size_t n = cfg->n;
     hipError_t er = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
-    if (er == hipSuccess) er = hipEventCreate(&s->ev0);
-    if (er == hipSuccess) er = hipEventCreate(&s->ev1);
-    if (er == hipSuccess) er = hipEventCreate(&s->cev0);
-    if (er == hipSuccess) er = hipEventCreate(&s->cev1);
-    const size_t Bm = max_batch;
-    {
-        const size_t O = cfg->max_obstacles > 0 ? cfg->max_obstacles : 0, V = cfg->max_vertices > 0 ? cfg->max_vertices : 1;
-        // inputs: x0 xf u_prev dt_prev | x_init u_init dt_init | n_obstacles n_vertices vertices radius velocity (each piece 256-byte aligned)
-        s->in_cap = Bm * (3 + 3 + 2 + 1) * 8 + Bm * (5 * n + 1) * 8 + (O ? Bm * 4 + Bm * O * 4 + Bm * O * V * 2 * 8 + Bm * O * 8 + Bm * O * 2 * 8 : 0) + 16 * 256;
-        // outputs: x_out u_out dt_out status iters
-        s->out_cap = Bm * (5 * n + 1) * 8 + Bm * 12 + 10 * 256;
-        if (er == hipSuccess) er = hipHostMalloc((void**)&s->h_in, s->in_cap, hipHostMallocDefault);
-        if (er == hipSuccess) er = hipHostMalloc((void**)&s->h_out, s->out_cap, hipHostMallocDefault);
-        if (er == hipSuccess) er = hipMalloc((void**)&s->d_in, s->in_cap);
-        if (er == hipSuccess) er = hipMalloc((void**)&s->d_out, s->out_cap);
-    }
-    if (er == hipSuccess) er = hipMalloc((void**)&s->d_ngrid, Bm * 4);
-    if (er == hipSuccess) {      // the record table with the handle's own configuration as entry 0 (the only one until mpc_set_parameter_sets)
-        const TabLayout t(*cfg, 1);
-        std::vector<unsigned char> img(t.bytes, 0);
-        put_entry(*cfg, *cfg, 1, 0, img.data());
-        er = hipMalloc((void**)&s->d_tab, t.bytes);
-        if (er == hipSuccess) { s->tab_cap = 1; point_tables(s); er = hipMemcpy(s->d_tab, img.data(), t.bytes, hipMemcpyHostToDevice); }
-    }
-    if (er == hipSuccess) { std::vector<int32_t> full(Bm, cfg->n); er = hipMemcpy(s->d_ngrid, full.data(), Bm * 4, hipMemcpyHostToDevice); }      // never uninitialised
-    if (s->P64.n_via > 0) {
-        if (er == hipSuccess) er = hipMalloc((void**)&s->d_nvia, Bm * 4);
-        if (er == hipSuccess) er = hipMalloc((void**)&s->d_via, Bm * (size_t)s->P64.n_via * 3 * 8);
-        if (er == hipSuccess) er = hipMemset(s->d_nvia, 0, Bm * 4);
-        s->p_nvia = s->d_nvia; s->p_via = s->d_via;
-    }
-    if (cfg->max_obstacles > 0) {
-        if (er == hipSuccess) er = hipMalloc((void**)&s->d_rows_dropped, Bm * 4);
-        if (er == hipSuccess) er = hipMemset(s->d_rows_dropped, 0, Bm * 4);
-    }
-    if (cfg->precision == MPC_MIXED && er == hipSuccess) er = hipMalloc((void**)&s->d_iters1, Bm * 4);
+    for (hipEvent_t* ev : {&s->ev0, &s->ev1, &s->cev0, &s->cev1}) if (er == hipSuccess) er = hipEventCreate(ev);
     if (plan.block_bytes > 0) {
         // the per-XCD pools of blocks (mpc_solve_kernel.hpp), sized by mpc::pool_blocks_per_xcd from the device: the resident workgroups per CU of the kernel that claims
         // the blocks (occupancy API: registers, LDS, one-wave workgroups) and the CUs of an XCD (the device's CUs over the distinct XCC ids a probe launch sees).  Stale
@@ -288,32 +325,15 @@ int mpc_create(const mpc_config* cfg, int32_t max_batch, int32_t device, mpc_sol
             }
             s->n_gslots = mpc::pool_blocks_per_xcd(plan, occ, prop.multiProcessorCount, n_xcc);
         }
-        const size_t pool_bytes = 8 * (size_t)s->n_gslots * plan.block_bytes + (size_t)mpc::GlobalStage::kPrefetchPad * 8;
-        if (er == hipSuccess) er = hipMalloc(&s->d_gstage, pool_bytes);
-#ifdef MPC_DEV_SWITCHES
-        // developer check (scripts/dev/gs_sweep.py under MPC_POISON_GSTAGE=1): every word of the pool starts as a NaN pattern, so a word that some path consumes before writing it shows up in the results
-        if (er == hipSuccess) { if (const char* e = getenv("MPC_POISON_GSTAGE")) { if (e[0] == '1') er = hipMemset(s->d_gstage, 0xFF, pool_bytes); } }
-#endif
-        if (er == hipSuccess) er = hipMalloc((void**)&s->d_gslots, 8 * (size_t)s->n_gslots * 4);
-        if (er == hipSuccess) er = hipMemset(s->d_gslots, 0, 8 * (size_t)s->n_gslots * 4);
     }
-    if (cfg->dual_warm_start || cfg->precision == MPC_MIXED) {
-        s->dual_words = mpc::dual_words(plan.WL.NS);
-        if (er == hipSuccess) er = hipMalloc((void**)&s->d_dual, Bm * (size_t)s->dual_words * 8);
-        if (er == hipSuccess) er = hipMemset(s->d_dual, 0, Bm * (size_t)s->dual_words * 8);
+    if (cfg->dual_warm_start || cfg->precision == MPC_MIXED) s->dual_words = mpc::dual_words(plan.WL.NS);
+    declare_buffers(s);
+    for (Buf& b : s->bufs) {
+        if (er == hipSuccess && b.bytes) er = buf_alloc(b, b.bytes);
+        if (er == hipSuccess && b.bytes) er = buf_fill(s, b);
     }
-    if (s->P32.n_cand > 1) {
-        const size_t C_ = s->P32.n_cand;
-        if (er == hipSuccess) er = hipMalloc((void**)&s->d_cwin, Bm * 4);
-        if (er == hipSuccess) er = hipMalloc((void**)&s->d_cexited, Bm * 4);
-        if (er == hipSuccess) er = hipMalloc((void**)&s->d_citsum, Bm * 4);
-        if (er == hipSuccess) er = hipMalloc((void**)&s->d_crec, C_ * Bm * (5 * n + 3 + (size_t)s->dual_words) * 8);
-        if (er == hipSuccess) er = hipMalloc((void**)&s->d_winner, Bm * 4);
-        if (er == hipSuccess) er = hipMalloc((void**)&s->d_iters_total, Bm * 4);
-        if (er == hipSuccess) er = hipMemset(s->d_cwin, 0x7f, Bm * 4);
-        if (er == hipSuccess) er = hipMemset(s->d_cexited, 0, Bm * 4);
-        if (er == hipSuccess) er = hipMemset(s->d_citsum, 0, Bm * 4);
-    }
+    if (er == hipSuccess) { s->tab_cap = 1; point_tables(s); }      // the handle's own configuration as entry 0, the only one until mpc_set_parameter_sets
+    s->p_nvia = s->d_nvia; s->p_via = s->d_via;
     // the fills above run on the null stream, the solves on the handle's own non-blocking stream: nothing orders the two, so wait here
     if (er == hipSuccess) er = hipDeviceSynchronize();
     if (er != hipSuccess) {
@@ -330,13 +350,7 @@ int mpc_reset(mpc_solver* s) {
     g_err[0] = 0;
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipStreamSynchronize(s->stream));
-    if (s->d_dual) HIP_TRY(hipMemset(s->d_dual, 0, (size_t)s->max_batch * s->dual_words * 8));      // forget the multipliers
-    if (s->d_gslots) HIP_TRY(hipMemset(s->d_gslots, 0, 8 * (size_t)s->n_gslots * 4));                      // claim words of the factorisation-data blocks (self-restoring unless a launch was aborted)
-    if (s->d_cwin) {      // candidate bookkeeping back to idle (it is self-restoring unless a launch was aborted)
-        HIP_TRY(hipMemset(s->d_cwin, 0x7f, (size_t)s->max_batch * 4));
-        HIP_TRY(hipMemset(s->d_cexited, 0, (size_t)s->max_batch * 4));
-        HIP_TRY(hipMemset(s->d_citsum, 0, (size_t)s->max_batch * 4));
-    }
+    for (const Buf& b : s->bufs) if (b.reset && *b.p) HIP_TRY(buf_fill(s, b));
     HIP_TRY(hipDeviceSynchronize());      // null-stream fills vs the handle's non-blocking stream (see mpc_create)
     return MPC_OK;
 }
@@ -345,61 +359,32 @@ void mpc_destroy(mpc_solver* s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
-    void* bufs[] = {s->d_tab, s->d_set_of, s->d_gslots, s->d_gstage, s->d_stage, s->d_iters1, s->d_dual, s->d_rows_dropped, s->d_cwin, s->d_cexited, s->d_citsum, s->d_crec, s->d_winner, s->d_iters_total, s->d_nvia, s->d_via, s->d_ngrid, s->d_in, s->d_out};
-    for (void* b : bufs) if (b) (void)hipFree(b);
-    if (s->h_in) (void)hipHostFree(s->h_in);
-    if (s->h_out) (void)hipHostFree(s->h_out);
-    if (s->h_tab) (void)hipHostFree(s->h_tab);
-    if (s->ev0) (void)hipEventDestroy(s->ev0);
-    if (s->ev1) (void)hipEventDestroy(s->ev1);
-    if (s->cev0) (void)hipEventDestroy(s->cev0);
-    if (s->cev1) (void)hipEventDestroy(s->cev1);
+    for (Buf& b : s->bufs) buf_free(b);
+    for (hipEvent_t ev : {s->ev0, s->ev1, s->cev0, s->cev1}) if (ev) (void)hipEventDestroy(ev);
     if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
 }
 
 }  // extern "C"
 
-// fills the launch record of mpc_solve_kernel.hpp from the handle; the kernels themselves are instantiated per (precision, model) in
-// mpc_solve_inst.hip (split build: one object each, compiled in parallel) or right here (single translation unit)
-template <typename T, int MODEL>
-static hipError_t launch_model(mpc_solver* s, const mpc::Problem<T>& P, int B, const double* x0, const double* xf, const double* up,
-                               const double* dtp, const double* xi, const double* ui, const double* dti, const mpc_obstacles& ob, double* xo, double* uo,
-                               double* dto, int32_t* st, int32_t* it) {
-    mpc::SolveLaunch a;
-    a.k = mpc::plan_launch(s->plan, sizeof(T) == 4, B);
+// A solve launch: the caller's part of the record (inputs, initial guess, obstacles, outputs, B: mpc_solve_batch_device) gets the handle's part for one precision
+// and goes to the kernels, which are instantiated per (precision, model) in mpc_solve_inst.hip (split build: one object each, compiled in parallel) or right
+// here (single translation unit).
+static hipError_t launch(const mpc_solver* s, bool f32, mpc::SolveLaunch a) {
+    const bool refine = s->cfg.precision == MPC_MIXED && !f32;      // the fp64 phase of MPC_MIXED
+    a.k = mpc::plan_launch(s->plan, f32, a.B);
     a.stream = s->stream;
-    a.B = B;
     a.gstage = s->d_gstage; a.gslots = s->d_gslots; a.n_gslots = s->n_gslots;
-    a.rec = &P;
-    if constexpr (sizeof(T) == 8) a.ptab = s->d_tab64; else a.ptab = s->d_tab32;
+    a.rec = f32 ? (const void*)&s->P32 : (const void*)&s->P64;
+    a.ptab = f32 ? (const void*)s->d_tab32 : (const void*)s->d_tab64;
     a.set_of = s->p_set_of;
-    a.x0 = x0; a.xf = xf; a.u_prev = up; a.dt_prev = dtp; a.x_init = xi; a.u_init = ui; a.dt_init = dti; a.obst = ob;
     a.n_grid = s->use_ngrid ? s->d_ngrid : nullptr; a.n_via = s->p_nvia; a.via = s->p_via;
     // kept multipliers: a launch starts from them under dual_warm_start; in MPC_MIXED without it the block is only the hand-off from the fp32 phase
     // (which leaves its multipliers) to the fp64 phase (which starts from them) -- nothing is carried from the slot's previous control cycle
-    const int dual_read = (s->cfg.dual_warm_start || (s->cfg.precision == MPC_MIXED && sizeof(T) == 8)) ? 1 : 0;
-    a.cc = {P.n_cand, s->d_cwin, s->d_cexited, s->d_citsum, s->d_crec, s->d_winner, s->d_iters_total, s->d_rows_dropped, s->d_dual, s->dual_words, dual_read};
-    a.iters_add = (s->cfg.precision == MPC_MIXED && sizeof(T) == 8) ? s->d_iters1 : nullptr;
-    a.x_out = xo; a.u_out = uo; a.dt_out = dto; a.status = st; a.iters = it;
-    return mpc::launch_solve<T, MODEL>(a);
-}
-
-template <typename T>
-static hipError_t launch_prec(mpc_solver* s, const mpc::Problem<T>& P, int B, const double* x0, const double* xf, const double* up,
-                        const double* dtp, const double* xi, const double* ui, const double* dti, const mpc_obstacles& ob, double* xo, double* uo,
-                        double* dto, int32_t* st, int32_t* it) {
-#ifdef MPC_DEV_ONE_MODEL       // developer builds (fast compile, asm inspection): only the fp64 instantiations of ONE model exist (-DMPC_DEV_ONE_MODEL=<model id>)
-    if (sizeof(T) == 8) return launch_model<double, MPC_DEV_ONE_MODEL>(s, s->P64, B, x0, xf, up, dtp, xi, ui, dti, ob, xo, uo, dto, st, it);
-    return hipErrorInvalidConfiguration;
-#else
-    switch (s->cfg.model) {
-        case MPC_MODEL_UNICYCLE: return launch_model<T, mpc::MODEL_UNICYCLE>(s, P, B, x0, xf, up, dtp, xi, ui, dti, ob, xo, uo, dto, st, it);
-        case MPC_MODEL_SIMPLE_CAR: return launch_model<T, mpc::MODEL_SIMPLE_CAR>(s, P, B, x0, xf, up, dtp, xi, ui, dti, ob, xo, uo, dto, st, it);
-        case MPC_MODEL_SIMPLE_CAR_FRONT: return launch_model<T, mpc::MODEL_SIMPLE_CAR_FRONT>(s, P, B, x0, xf, up, dtp, xi, ui, dti, ob, xo, uo, dto, st, it);
-        default: return launch_model<T, mpc::MODEL_KINEMATIC_BICYCLE>(s, P, B, x0, xf, up, dtp, xi, ui, dti, ob, xo, uo, dto, st, it);
-    }
-#endif
+    const int dual_read = (s->cfg.dual_warm_start || refine) ? 1 : 0;
+    a.cc = {f32 ? s->P32.n_cand : s->P64.n_cand, s->d_cwin, s->d_cexited, s->d_citsum, s->d_crec, s->d_winner, s->d_iters_total, s->d_rows_dropped, s->d_dual, s->dual_words, dual_read};
+    a.iters_add = refine ? s->d_iters1 : nullptr;
+    return with_model(f32, s->cfg.model, [&](auto t, auto m) { return mpc::launch_solve<decltype(t), decltype(m)::value>(a); });
 }
 
 extern "C" {
@@ -428,16 +413,22 @@ int mpc_solve_batch_device(mpc_solver* s, int32_t B, const double* d_x0, const d
     }
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipEventRecord(s->ev0, s->stream));
+    mpc::SolveLaunch a{};
+    a.B = B;
+    a.x0 = d_x0; a.xf = d_xf; a.u_prev = d_u_prev; a.dt_prev = d_dt_prev; a.x_init = d_x_init; a.u_init = d_u_init; a.dt_init = d_dt_init; a.obst = ob;
+    a.x_out = d_x_out; a.u_out = d_u_out; a.dt_out = d_dt_out; a.status = d_status; a.iters = d_iters;
     hipError_t le;
     if (s->cfg.precision == MPC_MIXED) {
         // phase 1 (fp32, candidates, tol 1e-4) leaves iterate + multipliers; phase 2 (fp64, one candidate) refines them in place
-        le = launch_prec<float>(s, s->P32, B, d_x0, d_xf, d_u_prev, d_dt_prev, d_x_init, d_u_init, d_dt_init, ob, d_x_out, d_u_out, d_dt_out, d_status, s->d_iters1);
-        if (le == hipSuccess)
-            le = launch_prec<double>(s, s->P64, B, d_x0, d_xf, d_u_prev, d_dt_prev, d_x_out, d_u_out, d_dt_out, ob, d_x_out, d_u_out, d_dt_out, d_status, d_iters);
-    } else if (s->cfg.precision == MPC_FP32)
-        le = launch_prec<float>(s, s->P32, B, d_x0, d_xf, d_u_prev, d_dt_prev, d_x_init, d_u_init, d_dt_init, ob, d_x_out, d_u_out, d_dt_out, d_status, d_iters);
-    else
-        le = launch_prec<double>(s, s->P64, B, d_x0, d_xf, d_u_prev, d_dt_prev, d_x_init, d_u_init, d_dt_init, ob, d_x_out, d_u_out, d_dt_out, d_status, d_iters);
+        mpc::SolveLaunch first = a;
+        first.iters = s->d_iters1;
+        le = launch(s, true, first);
+        mpc::SolveLaunch second = first;
+        second.x_init = d_x_out; second.u_init = d_u_out; second.dt_init = d_dt_out; second.iters = d_iters;
+        if (le == hipSuccess) le = launch(s, false, second);
+    } else {
+        le = launch(s, s->cfg.precision == MPC_FP32, a);
+    }
     HIP_TRY(le);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(s->ev1, s->stream));
@@ -713,26 +704,19 @@ int mpc_set_parameter_sets(mpc_solver* s, int32_t n_sets, const mpc_config* sets
     const bool grow = entries > (size_t)s->tab_cap;
     const size_t cap = grow ? entries : (size_t)s->tab_cap;
     const TabLayout t(s->cfg, cap);
-    const size_t so_off = (t.bytes + 255) & ~(size_t)255, img_bytes = so_off + (size_t)B * 4;
-    if (img_bytes > s->h_tab_cap) {
-        unsigned char* h = nullptr;
-        HIP_TRY(hipHostMalloc((void**)&h, img_bytes, hipHostMallocDefault));
-        if (s->h_tab) (void)hipHostFree(s->h_tab);      // (no copy from it is in flight: every call waits for its own)
-        s->h_tab = h; s->h_tab_cap = img_bytes;
-    }
+    const size_t so_off = t.bytes, img_bytes = so_off + (size_t)B * 4;
+    if (img_bytes > s->bufs[BUF_H_TAB].bytes) HIP_TRY(buf_alloc(s->bufs[BUF_H_TAB], img_bytes));      // (no copy from the old one is in flight: every call waits for its own)
     memset(s->h_tab, 0, img_bytes);
     put_entry(s->cfg, s->cfg, cap, 0, s->h_tab);
     for (int i = 0; i < n_sets; ++i) put_entry(s->cfg, sets[i], cap, (size_t)i + 1, s->h_tab);
     int32_t* so = reinterpret_cast<int32_t*>(s->h_tab + so_off);
     for (int b = 0; b < B; ++b) so[b] = set_of[b] + 1;
-    if (!s->d_set_of) HIP_TRY(hipMalloc((void**)&s->d_set_of, (size_t)s->max_batch * 4));
+    if (!s->d_set_of) HIP_TRY(buf_alloc(s->bufs[BUF_SET_OF], (size_t)s->max_batch * 4));
     if (grow) {
         // a launch still in flight may read the old table: wait for it before the table is replaced (a new one, then the old one freed)
-        unsigned char* d = nullptr;
         HIP_TRY(hipStreamSynchronize(s->stream));
-        HIP_TRY(hipMalloc((void**)&d, t.bytes));
-        (void)hipFree(s->d_tab);
-        s->d_tab = d; s->tab_cap = (int)cap;
+        HIP_TRY(buf_alloc(s->bufs[BUF_TAB], t.bytes));
+        s->tab_cap = (int)cap;
         point_tables(s);
         HIP_TRY(hipMemcpyAsync(s->d_tab, s->h_tab, t.bytes, hipMemcpyHostToDevice, s->stream));
     } else {
@@ -793,7 +777,7 @@ static int step_host(mpc_solver* s, int32_t B, const double* x0, const double* x
     if ((x_init != nullptr) != (u_init != nullptr) || (x_init != nullptr) != (dt_init != nullptr)) {
         set_err("mpc_solve_batch: x_init, u_init and dt_init must be given together (all three or none)"); return MPC_EINVAL; }
     HIP_TRY(hipSetDevice(s->device));
-    const size_t n = s->cfg.n, b = B;
+    const size_t b = B;
     hipStream_t q = s->stream;
     const bool warm = x_init != nullptr;
     if (s->cfg.max_obstacles > 0 && (!obstacles || !obstacles->n_obstacles || !obstacles->n_vertices || !obstacles->vertices)) {
@@ -801,49 +785,30 @@ static int step_host(mpc_solver* s, int32_t B, const double* x0, const double* x
         return MPC_EINVAL;
     }
     // ---- pack every input into the pinned block (256-byte aligned pieces), ONE host-to-device copy
-    size_t off = 0;
-    auto put = [&](const void* src, size_t bytes) -> const unsigned char* {
-        const unsigned char* dptr = s->d_in + off;
-        memcpy(s->h_in + off, src, bytes);
-        off = (off + bytes + 255) & ~(size_t)255;
-        return dptr;
-    };
-    const double* dx0 = (const double*)put(x0, b * 3 * 8);
-    const double* dxf = (const double*)put(xf, b * 3 * 8);
-    const double* dup = u_prev ? (const double*)put(u_prev, b * 2 * 8) : nullptr;
-    const double* ddtp = dt_prev ? (const double*)put(dt_prev, b * 8) : nullptr;
-    const double *dxi = nullptr, *dui = nullptr, *ddti = nullptr;
-    if (warm) {
-        dxi = (const double*)put(x_init, b * n * 3 * 8);
-        dui = (const double*)put(u_init, b * n * 2 * 8);
-        ddti = (const double*)put(dt_init, b * 8);
+    typedef mpc::StepPieces SP;
+    const bool obst = s->cfg.max_obstacles > 0;
+    const void* src[SP::N_IN] = {x0, xf, u_prev, dt_prev, x_init, u_init, dt_init, obst ? obstacles->n_obstacles : nullptr, obst ? obstacles->n_vertices : nullptr,
+                                 obst ? obstacles->vertices : nullptr, obst ? obstacles->radius : nullptr, obst ? obstacles->velocity : nullptr};
+    const SP pc = mpc::step_pieces(s->cfg, b, u_prev != nullptr, dt_prev != nullptr, warm, src[SP::RADIUS] != nullptr, src[SP::VELOCITY] != nullptr);
+    if (pc.in_bytes > s->bufs[BUF_H_IN].bytes) { set_err("mpc_solve_batch: internal staging overflow"); return MPC_EINVAL; }
+    const void* d[SP::N_IN];      // device address of every input piece, NULL for one this call does not have
+    for (int i = 0; i < SP::N_IN; ++i) {
+        d[i] = pc.bytes[i] ? s->d_in + pc.off[i] : nullptr;
+        if (pc.bytes[i]) memcpy(s->h_in + pc.off[i], src[i], pc.bytes[i]);
     }
-    mpc_obstacles dob = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (s->cfg.max_obstacles > 0) {
-        const size_t O = s->cfg.max_obstacles, V = s->cfg.max_vertices > 0 ? s->cfg.max_vertices : 1;
-        dob.n_obstacles = (const int32_t*)put(obstacles->n_obstacles, b * 4);
-        dob.n_vertices = (const int32_t*)put(obstacles->n_vertices, b * O * 4);
-        dob.vertices = (const double*)put(obstacles->vertices, b * O * V * 2 * 8);
-        if (obstacles->radius) dob.radius = (const double*)put(obstacles->radius, b * O * 8);
-        if (obstacles->velocity && s->cfg.enable_dynamic_obstacles) dob.velocity = (const double*)put(obstacles->velocity, b * O * 2 * 8);
-    }
-    if (off > s->in_cap) { set_err("mpc_solve_batch: internal staging overflow"); return MPC_EINVAL; }
-    HIP_TRY(hipMemcpyAsync(s->d_in, s->h_in, off, hipMemcpyHostToDevice, q));
+    const mpc_obstacles dob = {(const int32_t*)d[SP::N_OBSTACLES], (const int32_t*)d[SP::N_VERTICES], (const double*)d[SP::VERTICES], (const double*)d[SP::RADIUS], (const double*)d[SP::VELOCITY]};
+    HIP_TRY(hipMemcpyAsync(s->d_in, s->h_in, pc.in_bytes, hipMemcpyHostToDevice, q));
     // ---- outputs: one device block, ONE device-to-host copy
-    size_t oo = 0;
-    auto take = [&](size_t bytes) { size_t at = oo; oo = (oo + bytes + 255) & ~(size_t)255; return at; };
-    const size_t o_x = take(b * n * 3 * 8), o_u = take(b * n * 2 * 8), o_dt = take(b * 8), o_st = take(b * 4), o_it = take(b * 4), o_ng = take(b * 4);
-    int rc = mpc_step_batch_device(s, B, dx0, dxf, dup, ddtp, dxi, dui, ddti, &dob, outer, adapt, n_min, n_max, dt_hyst_ratio, (double*)(s->d_out + o_x),
+    const size_t o_x = pc.off[SP::X_OUT], o_u = pc.off[SP::U_OUT], o_dt = pc.off[SP::DT_OUT], o_st = pc.off[SP::STATUS], o_it = pc.off[SP::ITERS], o_ng = pc.off[SP::N_GRID];
+    int rc = mpc_step_batch_device(s, B, (const double*)d[SP::X0], (const double*)d[SP::XF], (const double*)d[SP::U_PREV], (const double*)d[SP::DT_PREV], (const double*)d[SP::X_INIT],
+                                   (const double*)d[SP::U_INIT], (const double*)d[SP::DT_INIT], &dob, outer, adapt, n_min, n_max, dt_hyst_ratio, (double*)(s->d_out + o_x),
                                    (double*)(s->d_out + o_u), (double*)(s->d_out + o_dt), (int32_t*)(s->d_out + o_st), (int32_t*)(s->d_out + o_it));
     if (rc != MPC_OK) return rc;
     if (n_grid_out && s->use_ngrid) HIP_TRY(hipMemcpyAsync(s->d_out + o_ng, s->d_ngrid, b * 4, hipMemcpyDeviceToDevice, q));
-    HIP_TRY(hipMemcpyAsync(s->h_out, s->d_out, oo, hipMemcpyDeviceToHost, q));
+    HIP_TRY(hipMemcpyAsync(s->h_out, s->d_out, pc.out_bytes, hipMemcpyDeviceToHost, q));
     HIP_TRY(hipStreamSynchronize(q));
-    memcpy(x_out, s->h_out + o_x, b * n * 3 * 8);
-    memcpy(u_out, s->h_out + o_u, b * n * 2 * 8);
-    memcpy(dt_out, s->h_out + o_dt, b * 8);
-    if (status) memcpy(status, s->h_out + o_st, b * 4);
-    if (iters) memcpy(iters, s->h_out + o_it, b * 4);
+    void* dst[5] = {x_out, u_out, dt_out, status, iters};      // (status and iters may be NULL)
+    for (int i = 0; i < 5; ++i) if (dst[i]) memcpy(dst[i], s->h_out + pc.off[SP::X_OUT + i], pc.bytes[SP::X_OUT + i]);
     if (n_grid_out) { if (s->use_ngrid) memcpy(n_grid_out, s->h_out + o_ng, b * 4); else for (size_t i = 0; i < b; ++i) n_grid_out[i] = s->cfg.n; }
     return MPC_OK;
 }

@@ -2,7 +2,7 @@
 //
 // A solve launch is served by one kernel instantiation, picked by the kernel level, the form (factorisation data in LDS, or in a block of global memory:
 // GlobalStage), one or two waves per SIMD, the fixed n = 50 layout and the dynamic LDS.  mpc_create computes the LaunchPlan; plan_launch() is the one place
-// that combines its fields into the answer for one launch (launch_model, mpc_occupancy and the pool sizing of mpc_capi.hip ask it); select_kernel
+// that combines its fields into the answer for one launch (launch, mpc_occupancy and the pool sizing of mpc_capi.hip ask it); select_kernel
 // (mpc_solve_kernel.hpp) maps that answer to an instantiation and picks the fixed layout, which is a question of the template parameters.
 #pragma once
 #include <cstddef>

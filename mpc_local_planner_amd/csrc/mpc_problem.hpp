@@ -234,5 +234,37 @@ inline std::string parameter_set_error(const mpc_config& handle, const mpc_confi
     return std::string();
 }
 
+// Consecutive pieces of one block at 256-byte aligned offsets: take(bytes) is where the next piece starts, `off` the bytes taken so far (a multiple of 256).
+struct Packer {
+    size_t off = 0;
+    size_t take(size_t bytes) { const size_t at = off; off = (off + bytes + 255) & ~(size_t)255; return at; }
+};
+
+// The pieces of one host-pointer call (mpc_solve_batch / mpc_step_batch) in the handle's two staging blocks: the inputs up to N_IN in the block that goes to the
+// device in one copy, the outputs behind them in the block that comes back in one copy.  bytes[i] = 0: the call has no such piece (an optional array the caller
+// left out, obstacle arrays of a handle without obstacles, velocities without enable_dynamic_obstacles).  mpc_create sizes the blocks with the same function, at
+// max_batch and every optional piece present: a piece only grows with B, so no call packs more (tests/test_step_pieces.py).
+struct StepPieces {
+    enum { X0, XF, U_PREV, DT_PREV, X_INIT, U_INIT, DT_INIT, N_OBSTACLES, N_VERTICES, VERTICES, RADIUS, VELOCITY, N_IN,
+           X_OUT = N_IN, U_OUT, DT_OUT, STATUS, ITERS, N_GRID, N_PIECES };
+    size_t bytes[N_PIECES], off[N_PIECES];
+    size_t in_bytes, out_bytes;      // what the two copies move
+};
+inline StepPieces step_pieces(const mpc_config& c, size_t B, bool u_prev, bool dt_prev, bool init, bool radius, bool velocity) {
+    const size_t n = (size_t)c.n, O = c.max_obstacles > 0 ? (size_t)c.max_obstacles : 0, V = c.max_vertices > 0 ? (size_t)c.max_vertices : 1;
+    const size_t per_instance[StepPieces::N_PIECES] = {
+        24, 24, u_prev ? 16u : 0u, dt_prev ? 8u : 0u, init ? n * 24 : 0, init ? n * 16 : 0, init ? 8u : 0u,                                      // x0 xf u_prev dt_prev | x_init u_init dt_init
+        O ? 4u : 0u, O * 4, O * V * 16, radius ? O * 8 : 0, velocity && c.enable_dynamic_obstacles ? O * 16 : 0,                             // n_obstacles n_vertices vertices radius velocity
+        n * 24, n * 16, 8, 4, 4, 4};                                                                                                           // x_out u_out dt_out status iters n_grid
+    StepPieces p{};
+    Packer in, out;
+    for (int i = 0; i < StepPieces::N_PIECES; ++i) {
+        p.bytes[i] = B * per_instance[i];
+        p.off[i] = p.bytes[i] ? (i < StepPieces::N_IN ? in : out).take(p.bytes[i]) : 0;
+    }
+    p.in_bytes = in.off; p.out_bytes = out.off;
+    return p;
+}
+
 
 }  // namespace mpc

@@ -275,7 +275,8 @@ int mpc_create(const mpc_config* cfg, int32_t max_batch, int32_t device, mpc_sol
 
 /* Replaces Controller::reset (controller.h:104): waits for the stream and returns the handle's per-instance state (candidate
  * bookkeeping, the duals kept for warm starts, the claim words of the factorisation-data blocks of mpc_config.stage_data) to its initial values -- all of it restores
- * itself at the end of every launch, so this only matters after a launch that was aborted. */
+ * itself at the end of every launch, so this only matters after a launch that was aborted.  A handle driven by mpc_controller_step_batch* additionally has
+ * every slot marked empty (the next cycle re-initialises it); step counts and last goals stay, as in the reference's reset(). */
 int mpc_reset(mpc_solver* s);
 
 void mpc_destroy(mpc_solver* s);
@@ -329,6 +330,69 @@ int mpc_step_batch_device(mpc_solver* s, int32_t B,
                           const double* d_x_init, const double* d_u_init, const double* d_dt_init, const mpc_obstacles* d_obstacles,
                           int32_t outer_iterations, int32_t adapt, int32_t n_min, int32_t n_max, double dt_hyst_ratio,
                           double* d_x_out, double* d_u_out, double* d_dt_out, int32_t* d_status, int32_t* d_iters);
+
+/* ---- Whole Controller::step cycles for a batch (src/controller.cpp:111-179): what the reference runs AROUND the solve -- state estimate, re-initialisation
+ * decision, initial trajectory from the plan, warm-start bookkeeping -- per instance on the device, then the solves of mpc_step_batch_device, in one call.
+ * The handle owns the slot state of instance b: its step count (_ocp_seq), whether it is empty, its last goal and its previous solution (x, u, dt, grid size);
+ * the state is allocated by the first controller call (a handle that never makes one pays nothing).  include/mpc_controller.hpp is the same cycle for ONE
+ * robot on the host; this call returns, bit for bit, what B such controllers return. */
+typedef struct mpc_cycle_params {          /* controller/..., grid/..., grid/variable_grid/grid_adaptation/... of the reference's parameter tree */
+    int32_t n_ref;                         /* grid/grid_size_ref: the size a re-initialised slot starts at; 0 -> cfg.n (cfg.n is the stride / capacity of every array) */
+    int32_t outer_iterations;              /* controller/outer_ocp_iterations (:70-72) */
+    int32_t adapt, n_min, n_max;           /* grid/variable_grid/grid_adaptation/{enable, min_grid_size (clamped to 3), max_grid_size (clamped to cfg.n)} */
+    double  dt_hyst_ratio;                 /* .../dt_hyst_ratio */
+    int32_t warm_start;                    /* grid/warm_start (:294-296): warmStartShifting on the fixed grid */
+    int32_t force_reinit_num_steps;        /* controller/force_reinit_num_steps (:78); 0 = never */
+    double  force_reinit_new_goal_dist;    /* controller/force_reinit_new_goal_dist (:74) */
+    double  force_reinit_new_goal_angular; /* controller/force_reinit_new_goal_angular (:76) */
+    int32_t initial_plan_estimate_orientation;   /* yaw of the intermediate plan poses from the direction to the next pose (:838-840) */
+    int32_t prefer_x_feedback;             /* controller/prefer_x_feedback (:82) */
+    int32_t reference_reinit_sampling;     /* a re-initialised slot samples its plan at its last optimised dt, as the reference does (mpc_controller.hpp: setReferenceReinitSampling) */
+    double  period;                        /* the dt of Controller::step: a state measurement older than 2 periods is stale (:131-137) */
+} mpc_cycle_params;
+/* the reference's in-code defaults: n_ref 0 (= cfg.n), 1 outer iteration, grid adaptation on (n_min 2 -> 3, n_max 50 -> at most cfg.n, hysteresis 0.1; ignored on the fixed grid), warm_start 1, force_reinit_num_steps 0,
+ * new-goal distance 1.0 and angle pi / 2, orientation estimate on, prefer_x_feedback 0, reference re-initialisation sampling on, period 0.1 */
+void mpc_cycle_params_defaults(mpc_cycle_params* p);
+
+/* what reinit_out[b] reports: 0 = the instance started warm from its slot's previous solution (after its grid update); otherwise the causes of the re-initialisation */
+enum mpc_reinit_cause {
+    MPC_REINIT_FIRST = 1,          /* the slot was empty: its first step, or the first after mpc_reset */
+    MPC_REINIT_NUM_STEPS = 2,      /* force_reinit_num_steps > 0 and the slot's step count is a multiple of it */
+    MPC_REINIT_GOAL_DIST = 4,      /* the goal moved more than force_reinit_new_goal_dist since the slot's last step (tested on a slot that is not empty) */
+    MPC_REINIT_GOAL_ANGULAR = 8,   /* ... or turned more than force_reinit_new_goal_angular */
+    MPC_REINIT_RESET = 16,         /* reset[b] != 0: Controller::reset() since the slot's last step (also drops the slot's kept multipliers) */
+    MPC_REINIT_PLAN_GUESS = 32     /* the start is the guess sampled from the plan; without this bit a re-initialised instance took the device cold start (2-pose plan at dt_ref) */
+};
+
+/* One control cycle of B controllers.  DEVICE pointers; everything is enqueued on the solver's stream with no host round trip: the prepare kernel (per instance:
+ * x0 = x_feedback[b] when prefer_x_feedback and feedback_age[b] < 2 period, else the plan's first pose; goal = the plan's last pose; the re-initialisation
+ * decision; then either the guess from the plan -- poses equally spaced in time over (n_ref - 1) dt_ref, sampled at k * dt_sample with the SE2-aware linear
+ * interpolation, u = 0, dt = dt_ref, grid size n_ref; a 2-pose plan sampled at dt_ref is the cold start of mpc_solve_batch -- or the grid update of
+ * mpc_grid_update_device on the slot's previous solution: the fixed grid's shift when warm_start, the variable grid's adaptation when adapt), the solve, in place
+ * on the slot's arrays, with cold, plan-guess and warm instances mixed in the one launch, (grid update, solve) x (outer_iterations - 1) as mpc_step_batch_device, and
+ * three device-to-device copies into d_x_out / d_u_out / d_dt_out, which are outputs only.  d_plan [B][plan_stride][3] with d_n_plan[b] in [2, plan_stride] poses
+ * (values outside are clamped); d_x_feedback [B][3] and d_feedback_age [B] both or neither; d_reset [B] or NULL; d_u_prev / d_dt_prev / d_obstacles / d_status /
+ * d_iters as mpc_solve_batch_device; d_reinit_out [B] (nullable): MPC_REINIT_* bits.  The fixed grid's shift leaves the multipliers kept by dual_warm_start where they
+ * are, as a controller of mpc_controller.hpp does (mpc_grid_update_device, called directly, moves them along).
+ * Grid sizes of a handle driven this way belong to the controller (mpc_get_grid_sizes reads them); mpc_reset marks every slot empty and keeps step counts and last
+ * goals, as Controller::reset does.  Parameter sets (each instance re-initialises and adapts against its own dt_ref), via-points, candidates, dual_warm_start and every
+ * precision compose as with mpc_step_batch.  MPC_EINVAL: n_ref outside [3, cfg.n], a feedback pointer without its partner, a null required pointer; MPC_EBATCH: B above
+ * max_batch (or above the batch parameter sets / via-points were given for). */
+int mpc_controller_step_batch_device(mpc_solver* s, int32_t B, const mpc_cycle_params* p,
+                                     const double* d_plan, const int32_t* d_n_plan, int32_t plan_stride,
+                                     const double* d_x_feedback, const double* d_feedback_age, const int32_t* d_reset,
+                                     const double* d_u_prev, const double* d_dt_prev, const mpc_obstacles* d_obstacles,
+                                     double* d_x_out, double* d_u_out, double* d_dt_out, int32_t* d_status, int32_t* d_iters, int32_t* d_reinit_out);
+/* Same with HOST pointers (staged through buffers of the handle; blocking); n_grid_out (nullable): the grid sizes after the call.  Additionally MPC_EINVAL for
+ * an n_plan[b] outside [2, plan_stride]. */
+int mpc_controller_step_batch(mpc_solver* s, int32_t B, const mpc_cycle_params* p,
+                              const double* plan, const int32_t* n_plan, int32_t plan_stride,
+                              const double* x_feedback, const double* feedback_age, const int32_t* reset,
+                              const double* u_prev, const double* dt_prev, const mpc_obstacles* obstacles,
+                              double* x_out, double* u_out, double* dt_out, int32_t* status, int32_t* iters, int32_t* reinit_out, int32_t* n_grid_out);
+/* The slot state of the first B instances (HOST pointers, each nullable): step counts, empty flags (1 before the first step and after mpc_reset), last goals [B][3].
+ * A handle that made no controller call yet reports 0 / 1 / (0, 0, 0). */
+int mpc_controller_state(mpc_solver* s, int32_t B, int32_t* seq, int32_t* empty, double* last_goal);
 
 /* Per-instance grid sizes for the following mpc_solve_batch* calls (grid adaptation of the variable grid,
  * src/optimal_control/finite_differences_variable_grid_se2.cpp:99-121): instance b uses n_grid[b] grid points

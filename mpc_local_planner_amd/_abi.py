@@ -127,6 +127,30 @@ class MpcObstacles(C.Structure):
     ]
 
 
+class MpcCycleParams(C.Structure):
+    """struct mpc_cycle_params (include/mpc_hip.h): the controller / grid options of mpc_controller_step_batch*; field-for-field."""
+    _fields_ = [
+        ("n_ref", C.c_int32),
+        ("outer_iterations", C.c_int32),
+        ("adapt", C.c_int32),
+        ("n_min", C.c_int32),
+        ("n_max", C.c_int32),
+        ("dt_hyst_ratio", C.c_double),
+        ("warm_start", C.c_int32),
+        ("force_reinit_num_steps", C.c_int32),
+        ("force_reinit_new_goal_dist", C.c_double),
+        ("force_reinit_new_goal_angular", C.c_double),
+        ("initial_plan_estimate_orientation", C.c_int32),
+        ("prefer_x_feedback", C.c_int32),
+        ("reference_reinit_sampling", C.c_int32),
+        ("period", C.c_double),
+    ]
+
+
+# enum mpc_reinit_cause: the bits of reinit_out[b] (0 = warm start from the slot's previous solution)
+REINIT_FIRST, REINIT_NUM_STEPS, REINIT_GOAL_DIST, REINIT_GOAL_ANGULAR, REINIT_RESET, REINIT_PLAN_GUESS = 1, 2, 4, 8, 16, 32
+
+
 def _diag_offdiag(w, dim):
     """a weight given as its diagonal or as a full dim x dim matrix -> (diagonal, off-diagonal terms (0,1)[, (0,2), (1,2)] of the symmetric part)"""
     rows = [list(r) if hasattr(r, "__len__") else None for r in w]

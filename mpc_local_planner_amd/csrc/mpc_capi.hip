@@ -20,6 +20,7 @@
 #include "mpc_costmap.hpp"
 #include "mpc_feasibility.hpp"
 #include "mpc_grid_update.hpp"
+#include "mpc_controller_cycle.hpp"
 
 namespace {
 
@@ -47,7 +48,7 @@ struct Buf {
     int fill;           // the idle contents mpc_create writes
     bool reset, pinned; // mpc_reset writes them again; host memory (hipHostMalloc)
 };
-enum { BUF_TAB, BUF_SET_OF, BUF_H_TAB, BUF_STAGE, BUF_H_IN };      // the entries other entry points ask for (declare_buffers assigns them by index)
+enum { BUF_TAB, BUF_SET_OF, BUF_H_TAB, BUF_STAGE, BUF_H_IN, BUF_CYC_LIVE, BUF_CYC, BUF_CYC_HSTAGE, BUF_CYC_DSTAGE, BUF_NAMED };      // the entries other entry points ask for (declare_buffers assigns them by index)
 
 struct mpc_solver {
     mpc_config cfg;
@@ -95,6 +96,21 @@ struct mpc_solver {
     int32_t* last_status;       // device pointers of the most recent solve (mpc_last_candidates without candidates)
     int32_t* last_iters;
     bool timed;
+    // slot state of mpc_controller_step_batch* (mpc_controller_cycle.hpp), allocated by the first such call: the flags mpc_reset clears (0 = the slot is empty), and one
+    // block with everything else -- step counts, has-solution flags, start modes, last goals, the x0 / xf the solves read and the slots' previous solutions x / u / dt
+    int32_t* d_cyc_live;
+    unsigned char* d_cyc;
+    unsigned char *h_cyc_stage, *d_cyc_stage;      // staging of the host variant's own inputs (plans, feedback, reset) and of reinit_out, grows on demand
+};
+
+// the pieces of the slot-state block
+struct CycLayout {
+    size_t seq, has, mode, goal, x0, xf, x, u, dt, bytes;
+    CycLayout(size_t Bm, size_t n) {
+        mpc::Packer p;
+        seq = p.take(Bm * 4); has = p.take(Bm * 4); mode = p.take(Bm * 4); goal = p.take(Bm * 24); x0 = p.take(Bm * 24); xf = p.take(Bm * 24);
+        x = p.take(Bm * n * 24); u = p.take(Bm * n * 16); dt = p.take(Bm * 8); bytes = p.off;
+    }
 };
 
 static void buf_free(Buf& b) {
@@ -196,12 +212,16 @@ static void declare_buffers(mpc_solver* s) {
     if (const char* e = getenv("MPC_POISON_GSTAGE")) { if (e[0] == '1') gstage_fill = 0xFF; }
 #endif
     auto add = [s](auto* where, size_t bytes, int fill = FILL_NONE, bool reset = false, bool pinned = false) { s->bufs.push_back({(void**)where, bytes, fill, reset, pinned}); };
-    s->bufs.resize(BUF_H_IN + 1);      // the entries other entry points ask for by index, then the rest
+    s->bufs.resize(BUF_NAMED);         // the entries other entry points ask for by index, then the rest
     s->bufs[BUF_TAB] = {(void**)&s->d_tab, TabLayout(c, 1).bytes, FILL_TAB0, false, false};      // replaced by a larger one when mpc_set_parameter_sets needs more entries
     s->bufs[BUF_SET_OF] = {(void**)&s->d_set_of, 0, FILL_NONE, false, false};                    // [max_batch], allocated by the first mpc_set_parameter_sets
     s->bufs[BUF_H_TAB] = {(void**)&s->h_tab, 0, FILL_NONE, false, true};
     s->bufs[BUF_STAGE] = {(void**)&s->d_stage, 0, FILL_NONE, false, false};
     s->bufs[BUF_H_IN] = {(void**)&s->h_in, cap.in_bytes, FILL_NONE, false, true};
+    s->bufs[BUF_CYC_LIVE] = {(void**)&s->d_cyc_live, 0, 0, true, false};                        // the four of the controller cycle: allocated by the first mpc_controller_step_batch*
+    s->bufs[BUF_CYC] = {(void**)&s->d_cyc, 0, 0, false, false};
+    s->bufs[BUF_CYC_HSTAGE] = {(void**)&s->h_cyc_stage, 0, FILL_NONE, false, true};
+    s->bufs[BUF_CYC_DSTAGE] = {(void**)&s->d_cyc_stage, 0, FILL_NONE, false, false};
     add(&s->h_out, cap.out_bytes, FILL_NONE, false, true);
     add(&s->d_in, cap.in_bytes);
     add(&s->d_out, cap.out_bytes);
@@ -262,8 +282,25 @@ void mpc_config_defaults(mpc_config* c) {
     c->max_obstacle_rows = 4;
 }
 
+void mpc_cycle_params_defaults(mpc_cycle_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->n_ref = 0;                               // grid/grid_size_ref = the handle's n
+    p->outer_iterations = 1;                    // src/controller.cpp:70-72
+    p->adapt = 1; p->n_min = 2; p->n_max = 50;  // :248-261 (the variable grid adapts by default; n_min is clamped to 3, n_max to cfg.n)
+    p->dt_hyst_ratio = 0.1;
+    p->warm_start = 1;                          // :294-296
+    p->force_reinit_num_steps = 0;              // :78
+    p->force_reinit_new_goal_dist = 1.0;        // :74
+    p->force_reinit_new_goal_angular = 1.5707963267948966;      // :76 (0.5 pi)
+    p->initial_plan_estimate_orientation = 1;
+    p->prefer_x_feedback = 0;                   // :82
+    p->reference_reinit_sampling = 1;
+    p->period = 0.1;
+}
+
 const char* mpc_last_error(void) { return g_err; }
-int32_t mpc_version(void) { return 700; }      // 0.7.0 (CHANGELOG.md has what each version brought)
+int32_t mpc_version(void) { return 800; }      // 0.8.0 (CHANGELOG.md has what each version brought)
 
 #ifdef MPC_PROFILE
 // developer build only (-DMPC_PROFILE): per-wave phase cycle counters of the last wave-kernel launch, mpc::kProfCols words per row
@@ -389,10 +426,13 @@ static hipError_t launch(const mpc_solver* s, bool f32, mpc::SolveLaunch a) {
 
 extern "C" {
 
-int mpc_solve_batch_device(mpc_solver* s, int32_t B, const double* d_x0, const double* d_xf, const double* d_u_prev,
-                           const double* d_dt_prev, const double* d_x_init, const double* d_u_init, const double* d_dt_init,
-                           const mpc_obstacles* d_obstacles, double* d_x_out, double* d_u_out, double* d_dt_out, int32_t* d_status,
-                           int32_t* d_iters) {
+}  // extern "C"
+
+// mpc_solve_batch_device with the per-instance start mode of the controller cycle (d_init_mode: NULL everywhere else)
+static int solve_device(mpc_solver* s, int32_t B, const double* d_x0, const double* d_xf, const double* d_u_prev,
+                        const double* d_dt_prev, const double* d_x_init, const double* d_u_init, const double* d_dt_init,
+                        const mpc_obstacles* d_obstacles, double* d_x_out, double* d_u_out, double* d_dt_out, int32_t* d_status,
+                        int32_t* d_iters, const int32_t* d_init_mode) {
     g_err[0] = 0;
     if (!s || !d_x0 || !d_xf || !d_x_out || !d_u_out || !d_dt_out) { set_err("mpc_solve_batch_device: null argument"); return MPC_EINVAL; }
     if (B <= 0) return MPC_OK;
@@ -417,6 +457,7 @@ int mpc_solve_batch_device(mpc_solver* s, int32_t B, const double* d_x0, const d
     a.B = B;
     a.x0 = d_x0; a.xf = d_xf; a.u_prev = d_u_prev; a.dt_prev = d_dt_prev; a.x_init = d_x_init; a.u_init = d_u_init; a.dt_init = d_dt_init; a.obst = ob;
     a.x_out = d_x_out; a.u_out = d_u_out; a.dt_out = d_dt_out; a.status = d_status; a.iters = d_iters;
+    a.init_mode = d_init_mode;      // (MPC_MIXED: the fp32 phase; the fp64 refinement always starts from phase 1's iterate)
     hipError_t le;
     if (s->cfg.precision == MPC_MIXED) {
         // phase 1 (fp32, candidates, tol 1e-4) leaves iterate + multipliers; phase 2 (fp64, one candidate) refines them in place
@@ -424,7 +465,7 @@ int mpc_solve_batch_device(mpc_solver* s, int32_t B, const double* d_x0, const d
         first.iters = s->d_iters1;
         le = launch(s, true, first);
         mpc::SolveLaunch second = first;
-        second.x_init = d_x_out; second.u_init = d_u_out; second.dt_init = d_dt_out; second.iters = d_iters;
+        second.x_init = d_x_out; second.u_init = d_u_out; second.dt_init = d_dt_out; second.iters = d_iters; second.init_mode = nullptr;
         if (le == hipSuccess) le = launch(s, false, second);
     } else {
         le = launch(s, s->cfg.precision == MPC_FP32, a);
@@ -435,6 +476,15 @@ int mpc_solve_batch_device(mpc_solver* s, int32_t B, const double* d_x0, const d
     s->timed = true;
     s->last_status = d_status; s->last_iters = d_iters;
     return MPC_OK;
+}
+
+extern "C" {
+
+int mpc_solve_batch_device(mpc_solver* s, int32_t B, const double* d_x0, const double* d_xf, const double* d_u_prev,
+                           const double* d_dt_prev, const double* d_x_init, const double* d_u_init, const double* d_dt_init,
+                           const mpc_obstacles* d_obstacles, double* d_x_out, double* d_u_out, double* d_dt_out, int32_t* d_status,
+                           int32_t* d_iters) {
+    return solve_device(s, B, d_x0, d_xf, d_u_prev, d_dt_prev, d_x_init, d_u_init, d_dt_init, d_obstacles, d_x_out, d_u_out, d_dt_out, d_status, d_iters, nullptr);
 }
 
 int mpc_step_batch_device(mpc_solver* s, int32_t B, const double* d_x0, const double* d_xf, const double* d_u_prev, const double* d_dt_prev,
@@ -825,6 +875,169 @@ int mpc_step_batch(mpc_solver* s, int32_t B, const double* x0, const double* xf,
                    double* x_out, double* u_out, double* dt_out, int32_t* status, int32_t* iters, int32_t* n_grid_out) {
     return step_host(s, B, x0, xf, u_prev, dt_prev, x_init, u_init, dt_init, obstacles, outer_iterations, adapt, n_min, n_max, dt_hyst_ratio, x_out, u_out, dt_out, status,
                      iters, n_grid_out);
+}
+
+}  // extern "C"
+
+// ---- whole Controller::step cycles for a batch (mpc_controller_cycle.hpp)
+
+// the slot state, allocated and zeroed by the first controller call (all zero = every slot empty, no step made, no solution)
+static int cycle_state(mpc_solver* s) {
+    if (s->d_cyc) return MPC_OK;
+    const CycLayout L((size_t)s->max_batch, (size_t)s->cfg.n);
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(buf_alloc(s->bufs[BUF_CYC_LIVE], (size_t)s->max_batch * 4));
+    HIP_TRY(buf_alloc(s->bufs[BUF_CYC], L.bytes));
+    HIP_TRY(buf_fill(s, s->bufs[BUF_CYC_LIVE]));
+    HIP_TRY(buf_fill(s, s->bufs[BUF_CYC]));
+    HIP_TRY(hipDeviceSynchronize());      // null-stream fills vs the handle's non-blocking stream (see mpc_create)
+    return MPC_OK;
+}
+
+static const char* cycle_params_error(const mpc_solver* s, const mpc_cycle_params* p, const void* fb, const void* age) {
+    if (!p) return "mpc_controller_step_batch: null mpc_cycle_params";
+    const int n_ref = p->n_ref == 0 ? s->cfg.n : p->n_ref;
+    if (n_ref < 3 || n_ref > s->cfg.n) return "mpc_controller_step_batch: n_ref must be in [3, cfg.n] (0 = cfg.n)";
+    if ((fb != nullptr) != (age != nullptr)) return "mpc_controller_step_batch: x_feedback and feedback_age must be given together (both or neither)";
+    return nullptr;
+}
+
+extern "C" {
+
+int mpc_controller_step_batch_device(mpc_solver* s, int32_t B, const mpc_cycle_params* p, const double* d_plan, const int32_t* d_n_plan, int32_t plan_stride,
+                                     const double* d_x_feedback, const double* d_feedback_age, const int32_t* d_reset, const double* d_u_prev, const double* d_dt_prev,
+                                     const mpc_obstacles* d_obstacles, double* d_x_out, double* d_u_out, double* d_dt_out, int32_t* d_status, int32_t* d_iters,
+                                     int32_t* d_reinit_out) {
+    g_err[0] = 0;
+    if (!s || !d_plan || !d_n_plan || !d_x_out || !d_u_out || !d_dt_out || plan_stride < 2) { set_err("mpc_controller_step_batch_device: null argument or plan_stride < 2"); return MPC_EINVAL; }
+    if (const char* why = cycle_params_error(s, p, d_x_feedback, d_feedback_age)) { set_err(why); return MPC_EINVAL; }
+    if (B <= 0) return MPC_OK;
+    if (B > s->max_batch) { set_err("mpc_controller_step_batch: B exceeds max_batch"); return MPC_EBATCH; }
+    if (s->P64.n_via > 0 && s->p_nvia == s->d_nvia && s->nvia_B > 0 && B > s->nvia_B) {
+        set_err("mpc_controller_step_batch: B exceeds the batch the via-points were set for (mpc_set_via_points)"); return MPC_EBATCH; }
+    if (s->p_set_of && B > s->sets_B) { set_err("mpc_controller_step_batch: B exceeds the batch the parameter sets were given for (mpc_set_parameter_sets)"); return MPC_EBATCH; }
+    if (s->cfg.max_obstacles > 0 && (!d_obstacles || !d_obstacles->n_obstacles || !d_obstacles->n_vertices || !d_obstacles->vertices)) {
+        set_err("mpc_controller_step_batch: the solver was created with max_obstacles > 0 but no obstacles were passed"); return MPC_EINVAL; }
+    HIP_TRY(hipSetDevice(s->device));
+    if (const int rc = cycle_state(s)) return rc;
+    s->use_ngrid = 1; s->ngrid_B = s->max_batch;      // the grid sizes belong to the controller from here on (never uninitialised: mpc_create filled them with cfg.n)
+    const CycLayout L((size_t)s->max_batch, (size_t)s->cfg.n);
+    const size_t n = (size_t)s->cfg.n, nb = (size_t)B;
+    double *x0 = (double*)(s->d_cyc + L.x0), *xf = (double*)(s->d_cyc + L.xf), *x = (double*)(s->d_cyc + L.x), *u = (double*)(s->d_cyc + L.u), *dt = (double*)(s->d_cyc + L.dt);
+    int32_t* mode = (int32_t*)(s->d_cyc + L.mode);
+    int n_min = p->n_min < 3 ? 3 : p->n_min, n_max = p->n_max > s->cfg.n ? s->cfg.n : p->n_max;      // as mpc_grid_update_device
+    mpc::CycleArgs a;
+    memset(&a, 0, sizeof(a));
+    a.plan = d_plan; a.n_plan = d_n_plan; a.plan_stride = plan_stride; a.x_feedback = d_x_feedback; a.feedback_age = d_feedback_age; a.reset = d_reset;
+    a.n_ref = p->n_ref == 0 ? s->cfg.n : p->n_ref; a.warm_start = p->warm_start; a.force_reinit_num_steps = p->force_reinit_num_steps;
+    a.estimate_orientation = p->initial_plan_estimate_orientation; a.prefer_x_feedback = p->prefer_x_feedback; a.reference_reinit_sampling = p->reference_reinit_sampling;
+    a.dt_free = s->cfg.dt_free; a.update = s->cfg.dt_free ? (p->adapt != 0) : (p->warm_start != 0);
+    a.new_goal_dist = p->force_reinit_new_goal_dist; a.new_goal_angular = p->force_reinit_new_goal_angular; a.period = p->period;
+    a.seq = (int32_t*)(s->d_cyc + L.seq); a.live = s->d_cyc_live; a.has_solution = (int32_t*)(s->d_cyc + L.has); a.last_goal = (double*)(s->d_cyc + L.goal);
+    a.x0 = x0; a.xf = xf; a.init_mode = mode; a.reinit_out = d_reinit_out;
+    a.g.x0 = x0; a.g.x = x; a.g.u = u; a.g.dt = dt; a.g.n_grid = s->d_ngrid; a.g.n_stride = s->cfg.n; a.g.mode = s->cfg.dt_free ? 1 : 0;
+    a.g.n_min = n_min; a.g.n_max = n_max; a.g.dt_refs = s->d_dtref; a.g.set_of = s->p_set_of; a.g.hyst = p->dt_hyst_ratio;
+    // kept multipliers: dropped per slot on reset[b]; the variable grid drops them when the grid size changes (mpc_grid_update.hpp); the fixed grid's shift leaves them
+    // where they are (the prepare kernel hides them from it), as the facade's host-side shift does (include/mpc_controller.hpp)
+    a.g.dual = s->d_dual; a.g.dual_words = s->dual_words; a.g.dual_ns = s->plan.WL.NS;
+    const size_t lds = (n * 5 + (size_t)plan_stride * 4) * 8;
+    if (lds > 64u * 1024u) { set_err("mpc_controller_step_batch: 5 cfg.n + 4 plan_stride doubles exceed the 64 KB of LDS of the prepare kernel"); return MPC_EINVAL; }
+    if (lds > 48u * 1024u) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(mpc::controller_prepare_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(mpc::controller_prepare_kernel, dim3(B), dim3(64), lds, s->stream, a);
+    HIP_TRY(hipGetLastError());
+    // the solve with cold, plan-guess and warm instances in one launch, in place on the slots' arrays; then the remaining outer iterations with every instance warm
+    int rc = solve_device(s, B, x0, xf, d_u_prev, d_dt_prev, x, u, dt, d_obstacles, x, u, dt, d_status, d_iters, mode);
+    for (int it = 1; it < p->outer_iterations && rc == MPC_OK; ++it) {
+        if (s->cfg.dt_free) rc = mpc_grid_update_device(s, B, x0, x, u, dt, p->adapt, p->n_min, p->n_max, p->dt_hyst_ratio);
+        if (rc == MPC_OK) rc = solve_device(s, B, x0, xf, d_u_prev, d_dt_prev, x, u, dt, d_obstacles, x, u, dt, d_status, d_iters, nullptr);
+    }
+    if (rc != MPC_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(d_x_out, x, nb * n * 24, hipMemcpyDeviceToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(d_u_out, u, nb * n * 16, hipMemcpyDeviceToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(d_dt_out, dt, nb * 8, hipMemcpyDeviceToDevice, s->stream));
+    return MPC_OK;
+}
+
+int mpc_controller_step_batch(mpc_solver* s, int32_t B, const mpc_cycle_params* p, const double* plan, const int32_t* n_plan, int32_t plan_stride,
+                              const double* x_feedback, const double* feedback_age, const int32_t* reset, const double* u_prev, const double* dt_prev,
+                              const mpc_obstacles* obstacles, double* x_out, double* u_out, double* dt_out, int32_t* status, int32_t* iters, int32_t* reinit_out,
+                              int32_t* n_grid_out) {
+    g_err[0] = 0;
+    if (!s || !plan || !n_plan || !x_out || !u_out || !dt_out || plan_stride < 2) { set_err("mpc_controller_step_batch: null argument or plan_stride < 2"); return MPC_EINVAL; }
+    if (const char* why = cycle_params_error(s, p, x_feedback, feedback_age)) { set_err(why); return MPC_EINVAL; }
+    if (B <= 0) return MPC_OK;
+    if (B > s->max_batch) { set_err("mpc_controller_step_batch: B exceeds max_batch"); return MPC_EBATCH; }
+    for (int b = 0; b < B; ++b)
+        if (n_plan[b] < 2 || n_plan[b] > plan_stride) { snprintf(g_err, sizeof(g_err), "mpc_controller_step_batch: n_plan[%d] = %d is not in [2, plan_stride]", b, n_plan[b]); return MPC_EINVAL; }
+    const bool obst = s->cfg.max_obstacles > 0;
+    if (obst && (!obstacles || !obstacles->n_obstacles || !obstacles->n_vertices || !obstacles->vertices)) {
+        set_err("mpc_controller_step_batch: the solver was created with max_obstacles > 0 but no obstacles were passed"); return MPC_EINVAL; }
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t q = s->stream;
+    const size_t nb = (size_t)B;
+    // ---- the cycle's own inputs (plans, feedback, reset) and reinit_out through a staging pair of their own; u_prev / dt_prev / obstacles and the solve's outputs
+    // through the blocks of mpc_solve_batch (mpc::step_pieces)
+    mpc::Packer pk;
+    const size_t sz[6] = {nb * (size_t)plan_stride * 24, nb * 4, x_feedback ? nb * 24 : 0, feedback_age ? nb * 8 : 0, reset ? nb * 4 : 0, nb * 4};
+    const void* src[5] = {plan, n_plan, x_feedback, feedback_age, reset};
+    size_t off[6];
+    for (int i = 0; i < 6; ++i) off[i] = pk.take(sz[i]);
+    const size_t in_bytes = off[5];      // (the last piece is reinit_out: it only comes back)
+    for (Buf* bf : {&s->bufs[BUF_CYC_HSTAGE], &s->bufs[BUF_CYC_DSTAGE]})
+        if (pk.off > bf->bytes) { HIP_TRY(hipStreamSynchronize(q)); HIP_TRY(buf_alloc(*bf, pk.off)); }
+    for (int i = 0; i < 5; ++i) if (sz[i]) memcpy(s->h_cyc_stage + off[i], src[i], sz[i]);
+    auto dv = [&](int i) -> void* { return sz[i] ? (void*)(s->d_cyc_stage + off[i]) : nullptr; };
+    typedef mpc::StepPieces SP;
+    const void* ssrc[SP::N_IN] = {nullptr, nullptr, u_prev, dt_prev, nullptr, nullptr, nullptr, obst ? obstacles->n_obstacles : nullptr, obst ? obstacles->n_vertices : nullptr,
+                                  obst ? obstacles->vertices : nullptr, obst ? obstacles->radius : nullptr, obst ? obstacles->velocity : nullptr};
+    const SP pc = mpc::step_pieces(s->cfg, nb, u_prev != nullptr, dt_prev != nullptr, false, ssrc[SP::RADIUS] != nullptr, ssrc[SP::VELOCITY] != nullptr);
+    if (pc.in_bytes > s->bufs[BUF_H_IN].bytes) { set_err("mpc_controller_step_batch: internal staging overflow"); return MPC_EINVAL; }
+    const void* d[SP::N_IN];
+    for (int i = 0; i < SP::N_IN; ++i) {
+        d[i] = pc.bytes[i] && ssrc[i] ? s->d_in + pc.off[i] : nullptr;
+        if (pc.bytes[i] && ssrc[i]) memcpy(s->h_in + pc.off[i], ssrc[i], pc.bytes[i]);
+    }
+    const mpc_obstacles dob = {(const int32_t*)d[SP::N_OBSTACLES], (const int32_t*)d[SP::N_VERTICES], (const double*)d[SP::VERTICES], (const double*)d[SP::RADIUS], (const double*)d[SP::VELOCITY]};
+    HIP_TRY(hipMemcpyAsync(s->d_cyc_stage, s->h_cyc_stage, in_bytes, hipMemcpyHostToDevice, q));
+    HIP_TRY(hipMemcpyAsync(s->d_in, s->h_in, pc.in_bytes, hipMemcpyHostToDevice, q));
+    const size_t o_x = pc.off[SP::X_OUT], o_u = pc.off[SP::U_OUT], o_dt = pc.off[SP::DT_OUT], o_st = pc.off[SP::STATUS], o_it = pc.off[SP::ITERS], o_ng = pc.off[SP::N_GRID];
+    const int rc = mpc_controller_step_batch_device(s, B, p, (const double*)dv(0), (const int32_t*)dv(1), plan_stride, (const double*)dv(2), (const double*)dv(3), (const int32_t*)dv(4),
+                                                    (const double*)d[SP::U_PREV], (const double*)d[SP::DT_PREV], &dob, (double*)(s->d_out + o_x), (double*)(s->d_out + o_u),
+                                                    (double*)(s->d_out + o_dt), (int32_t*)(s->d_out + o_st), (int32_t*)(s->d_out + o_it), (int32_t*)dv(5));
+    if (rc != MPC_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(s->d_out + o_ng, s->d_ngrid, nb * 4, hipMemcpyDeviceToDevice, q));
+    HIP_TRY(hipMemcpyAsync(s->h_out, s->d_out, pc.out_bytes, hipMemcpyDeviceToHost, q));
+    HIP_TRY(hipMemcpyAsync(s->h_cyc_stage + off[5], s->d_cyc_stage + off[5], sz[5], hipMemcpyDeviceToHost, q));
+    HIP_TRY(hipStreamSynchronize(q));
+    void* dst[5] = {x_out, u_out, dt_out, status, iters};      // (status and iters may be NULL)
+    for (int i = 0; i < 5; ++i) if (dst[i]) memcpy(dst[i], s->h_out + pc.off[SP::X_OUT + i], pc.bytes[SP::X_OUT + i]);
+    if (n_grid_out) memcpy(n_grid_out, s->h_out + o_ng, nb * 4);
+    if (reinit_out) memcpy(reinit_out, s->h_cyc_stage + off[5], nb * 4);
+    return MPC_OK;
+}
+
+int mpc_controller_state(mpc_solver* s, int32_t B, int32_t* seq, int32_t* empty, double* last_goal) {
+    g_err[0] = 0;
+    if (!s) return MPC_EINVAL;
+    if (B <= 0) return MPC_OK;
+    if (B > s->max_batch) { set_err("mpc_controller_state: B exceeds max_batch"); return MPC_EBATCH; }
+    const size_t nb = (size_t)B;
+    if (!s->d_cyc) {      // no controller call yet
+        if (seq) memset(seq, 0, nb * 4);
+        if (empty) for (size_t b = 0; b < nb; ++b) empty[b] = 1;
+        if (last_goal) memset(last_goal, 0, nb * 24);
+        return MPC_OK;
+    }
+    const CycLayout L((size_t)s->max_batch, (size_t)s->cfg.n);
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (seq) HIP_TRY(hipMemcpy(seq, s->d_cyc + L.seq, nb * 4, hipMemcpyDeviceToHost));
+    if (last_goal) HIP_TRY(hipMemcpy(last_goal, s->d_cyc + L.goal, nb * 24, hipMemcpyDeviceToHost));
+    if (empty) {
+        HIP_TRY(hipMemcpy(empty, s->d_cyc_live, nb * 4, hipMemcpyDeviceToHost));
+        for (size_t b = 0; b < nb; ++b) empty[b] = empty[b] ? 0 : 1;
+    }
+    return MPC_OK;
 }
 
 }  // extern "C"

@@ -44,10 +44,11 @@ __device__ __forceinline__ double gu_normalize_theta(double th) {
     return th;
 }
 
-__global__ __launch_bounds__(64) void grid_update_kernel(GridUpdateArgs a) {
+// the grid update of instance b by its 64-lane workgroup; gsm: 5 n_stride doubles of LDS (xo [n][3] | uo [n][2]).  Every return is taken by the whole workgroup.
+// Called by grid_update_kernel and by controller_prepare_kernel (mpc_controller_cycle.hpp).
+__device__ __forceinline__ void grid_update_instance(const GridUpdateArgs& a, const int b, double* gsm) {
 #pragma clang fp contract(off)
-    extern __shared__ double gsm[];          // xo [n][3] | uo [n][2]
-    const int b = blockIdx.x, lane = threadIdx.x, ns = a.n_stride;
+    const int lane = threadIdx.x, ns = a.n_stride;
     int n = a.n_grid ? a.n_grid[b] : ns;
     n = n < 3 ? 3 : (n > ns ? ns : n);
     double* x = a.x + (size_t)b * ns * 3;
@@ -144,6 +145,11 @@ __global__ __launch_bounds__(64) void grid_update_kernel(GridUpdateArgs a) {
         if (a.n_grid) a.n_grid[b] = n_new;
         if (a.dual) a.dual[(size_t)b * a.dual_words] = 0.0;      // the kept multipliers belong to another grid
     }
+}
+
+__global__ __launch_bounds__(64) void grid_update_kernel(GridUpdateArgs a) {
+    extern __shared__ double gu_smem[];
+    grid_update_instance(a, blockIdx.x, gu_smem);
 }
 
 }  // namespace mpc

@@ -50,7 +50,7 @@ void mpc_ipm_wave_kernel(
     const double* __restrict__ dt_init, mpc_obstacles obst, const int32_t* __restrict__ n_grid, const int32_t* __restrict__ n_via,
     const double* __restrict__ via, CandCtl cc, const int32_t* __restrict__ iters_add, double* __restrict__ x_out,
     double* __restrict__ u_out, double* __restrict__ dt_out, int32_t* __restrict__ status, int32_t* __restrict__ iters, void* gstage, int* __restrict__ gslots, int n_gslots,
-    const mpc::Problem<T>* __restrict__ ptab, const int32_t* __restrict__ set_of) {
+    const mpc::Problem<T>* __restrict__ ptab, const int32_t* __restrict__ set_of, const int32_t* __restrict__ init_mode) {
     extern __shared__ __attribute__((aligned(16))) unsigned char mpc_smem[];
     T* sm = reinterpret_cast<T*>(mpc_smem);
     // problem record at the end of the dynamic LDS block (16-byte aligned); the layout stays in scalar registers
@@ -123,7 +123,11 @@ void mpc_ipm_wave_kernel(
         const int kind = NC > 1 ? Ps->cand_kind[cand] : 0;
         if (NC > 1) { S.my_cand = cand; S.iter_cap = Ps->cand_max_iter[cand]; S.win_ptr = cand > 0 ? cc.win + inst : nullptr; }
         if (cc.dual && cc.dual_read && cand == 0) S.dual_in = cc.dual + (long)inst * cc.dual_words;
-        if (kind == 0 && x_init && u_init && dt_init) {
+        // per-instance start mode (mpc_controller_step_batch*: the instances of one launch re-initialise in different cycles): init_mode[inst] == 0 makes candidate 0
+        // cold-start although the launch carries a guess; NULL: the launch decides, as everywhere else.  Wave-uniform: read once into a scalar register
+        bool guess = kind == 0 && x_init && u_init && dt_init;
+        if (guess && init_mode) guess = __builtin_amdgcn_readfirstlane(init_mode[inst]) != 0;
+        if (guess) {
             // coalesced read of this instance's contiguous [n][3] / [n][2] blocks
             const double* xi = x_init + (long)inst * nmax * 3;
             const double* ui = u_init + (long)inst * nmax * 2;
@@ -224,6 +228,7 @@ struct SolveLaunch {
     const void* rec;            // the handle's own problem record (Problem<T>, host copy): the by-value argument, what every instance solves without parameter sets
     const void* ptab;           // the handle's table of problem records (Problem<T>; entry 0 = its own configuration, then the parameter sets)
     const int32_t* set_of;      // [B] table entry of every instance, or NULL: the by-value record for all
+    const int32_t* init_mode;   // [B] 0: candidate 0 of the instance cold-starts whatever x_init is, else it loads the guess; NULL: x_init decides for the whole launch
     hipStream_t stream;
     int B;
     const double *x0, *xf, *u_prev, *dt_prev, *x_init, *u_init, *dt_init;
@@ -273,7 +278,7 @@ hipError_t launch_solve(const SolveLaunch& a) {
     }
     hipLaunchKernelGGL(kern, dim3((unsigned)a.B * (unsigned)(a.cc.n_cand > 1 ? a.cc.n_cand : 1)), dim3(kWave), a.k.lds, a.stream, *static_cast<const Problem<T>*>(a.rec), a.k.L, a.B, a.x0, a.xf, a.u_prev, a.dt_prev,
                        a.x_init, a.u_init, a.dt_init, a.obst, a.n_grid, a.n_via, a.via, a.cc, a.iters_add, a.x_out, a.u_out, a.dt_out, a.status, a.iters, a.gstage, a.gslots, a.n_gslots,
-                       static_cast<const Problem<T>*>(a.ptab), a.set_of);
+                       static_cast<const Problem<T>*>(a.ptab), a.set_of, a.init_mode);
     return hipSuccess;
 }
 

@@ -333,6 +333,30 @@ def config_from_params(params: dict, costmap_footprint=None, **sizing):
     return A.make_config(**kw), ctrl, notes
 
 
+def cycle_params_from_dict(params: dict, period: float = 0.1, reference_reinit_sampling: bool = True) -> "A.MpcCycleParams":
+    """struct mpc_cycle_params (mpc_controller_step_batch*) from the plugin's parameter namespace: the controller/ and grid/ keys config_from_params reports as facade
+    options, with the reference's in-code defaults (src/controller.cpp:70-84, 248-296).  period: the dt the caller passes to Controller::step (the plugin's
+    controller_frequency); n_ref = grid/grid_size_ref -- create the handle with cfg.n = max(n_ref, max_grid_size), as BatchSolver.from_yaml does."""
+    p = _Reader(params)
+    c = A.MpcCycleParams()
+    c.n_ref = p.get("grid/grid_size_ref", 20)
+    c.outer_iterations = p.get("controller/outer_ocp_iterations", 1)
+    variable = p.get("grid/variable_grid/enable", True)
+    c.adapt = int(variable and p.get("grid/variable_grid/grid_adaptation/enable", True))
+    c.n_min = p.get("grid/variable_grid/grid_adaptation/min_grid_size", 2)
+    c.n_max = p.get("grid/variable_grid/grid_adaptation/max_grid_size", 50)
+    c.dt_hyst_ratio = p.get("grid/variable_grid/grid_adaptation/dt_hyst_ratio", 0.1)
+    c.warm_start = int(p.get("grid/warm_start", True))
+    c.force_reinit_num_steps = p.get("controller/force_reinit_num_steps", 0)
+    c.force_reinit_new_goal_dist = p.get("controller/force_reinit_new_goal_dist", 1.0)
+    c.force_reinit_new_goal_angular = p.get("controller/force_reinit_new_goal_angular", 0.5 * math.pi)
+    c.initial_plan_estimate_orientation = 1          # Controller::_initial_plan_estimate_orientation (controller.h:140): no parameter, set by the plugin
+    c.prefer_x_feedback = int(p.get("controller/prefer_x_feedback", False))
+    c.reference_reinit_sampling = int(bool(reference_reinit_sampling))
+    c.period = float(period)
+    return c
+
+
 def plugin_options_from_params(params: dict, move_base_params: dict | None = None) -> dict:
     """The parameters that MpcLocalPlannerROS::initialize reads for ITSELF (src/mpc_local_planner_ros.cpp:96-125, :220), with the in-code defaults of
     include/mpc_local_planner/mpc_local_planner_ros.h:369-391 -- what a binding needs around the solve: goal tolerances, plan pruning / look-ahead, via-point separation

@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._abi import MpcConfig, MpcObstacles, MPC_OK
+from ._abi import MpcConfig, MpcCycleParams, MpcObstacles, MPC_OK
 
 
 class MpcError(RuntimeError):
@@ -152,6 +152,56 @@ class BatchSolver:
                                       float(dt_hyst_ratio), _addr(xo), _addr(uo), _addr(do), _addr(st), _addr(it), _addr(ng))
         self._check(rc)
         return BatchResult(xo, uo, do, st, it), ng
+
+    def cycle_params(self, **fields) -> MpcCycleParams:
+        """mpc_cycle_params with the reference's in-code defaults (mpc_cycle_params_defaults), then the given fields"""
+        p = MpcCycleParams()
+        self._lib.mpc_cycle_params_defaults(C.byref(p))
+        for k, v in fields.items():
+            if k not in dict(MpcCycleParams._fields_):
+                raise ValueError(f"mpc_cycle_params has no field {k}")
+            setattr(p, k, v)
+        return p
+
+    def controller_step(self, params: MpcCycleParams, plan, n_plan, x_feedback=None, feedback_age=None, reset=None, u_prev=None, dt_prev=None, obstacles=None):
+        """One whole Controller::step cycle for B robots (mpc_controller_step_batch; src/controller.cpp:111-179): state estimate, re-initialisation decision, initial
+        trajectory from the plan or grid update of the slot's previous solution, the solves.  plan (B, plan_stride, 3) with n_plan (B,) poses each (first = the
+        odometry pose, last = the goal); x_feedback (B, 3) with feedback_age (B,) seconds, both or neither; reset (B,) non-zero where Controller::reset() was called.
+        Returns (BatchResult, reinit (B,) MPC_REINIT_* bits, grid sizes (B,))."""
+        plan = np.ascontiguousarray(plan, dtype=np.float64)
+        B, stride = int(plan.shape[0]), int(plan.shape[1])
+        plan = _as_f64(plan, (B, stride, 3))
+        n = self.n
+        npl = np.ascontiguousarray(n_plan, dtype=np.int32)
+        if npl.shape != (B,):
+            raise ValueError("n_plan must have shape (B,)")
+        fb, age = _as_f64(x_feedback, (B, 3)), _as_f64(feedback_age, (B,))
+        rs = np.ascontiguousarray(reset, dtype=np.int32) if reset is not None else None
+        u_prev = _as_f64(u_prev, (B, 2)); dt_prev = _as_f64(dt_prev, (B,))
+        ob, keep = self._pack_obstacles(obstacles, B) if obstacles is not None else (None, None)
+        xo = np.zeros((B, n, 3)); uo = np.zeros((B, n, 2)); do = np.zeros(B); st = np.zeros(B, np.int32); it = np.zeros(B, np.int32)
+        ri = np.zeros(B, np.int32); ng = np.zeros(B, np.int32)
+        rc = self._lib.mpc_controller_step_batch(self._h, B, C.byref(params), _addr(plan), _addr(npl), stride, _addr(fb), _addr(age), _addr(rs), _addr(u_prev), _addr(dt_prev),
+                                                 C.byref(ob) if ob is not None else None, _addr(xo), _addr(uo), _addr(do), _addr(st), _addr(it), _addr(ri), _addr(ng))
+        self._check(rc)
+        return BatchResult(xo, uo, do, st, it), ri, ng
+
+    def controller_step_device(self, B: int, params: MpcCycleParams, plan: int, n_plan: int, plan_stride: int, x_feedback: Optional[int], feedback_age: Optional[int],
+                               reset: Optional[int], u_prev: Optional[int], dt_prev: Optional[int], x_out: int, u_out: int, dt_out: int, status: Optional[int],
+                               iters: Optional[int], reinit_out: Optional[int] = None, obstacles=None) -> None:
+        """mpc_controller_step_batch_device: the same cycle with device addresses (ints), asynchronous on the solver's stream, no host round trip"""
+        v = lambda p: C.c_void_p(p) if p else None
+        ob = MpcObstacles(*(tuple(obstacles) + (None,) * (5 - len(obstacles)))) if obstacles is not None else None
+        rc = self._lib.mpc_controller_step_batch_device(self._h, int(B), C.byref(params), v(plan), v(n_plan), int(plan_stride), v(x_feedback), v(feedback_age), v(reset),
+                                                        v(u_prev), v(dt_prev), C.byref(ob) if ob is not None else None, v(x_out), v(u_out), v(dt_out), v(status), v(iters),
+                                                        v(reinit_out))
+        self._check(rc)
+
+    def controller_state(self, B: int):
+        """(seq (B,), empty (B,), last_goal (B, 3)) of the controller slots (mpc_controller_state)"""
+        seq = np.zeros(B, np.int32); empty = np.zeros(B, np.int32); goal = np.zeros((B, 3))
+        self._check(self._lib.mpc_controller_state(self._h, int(B), C.c_void_p(seq.ctypes.data), C.c_void_p(empty.ctypes.data), C.c_void_p(goal.ctypes.data)))
+        return seq, empty, goal
 
     # ---- device buffers (raw HBM addresses, e.g. torch tensors' data_ptr()) -----
     def solve_device(self, B: int, x0: int, xf: int, u_prev: Optional[int], dt_prev: Optional[int], x_init: Optional[int],

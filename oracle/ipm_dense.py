@@ -570,10 +570,10 @@ class SolverNlp:
             if want_hess and y is not None:
                 W[np.ix_(self.ix[k], self.ix[k])] += y[r] * Hm
                 if self.idt >= 0:
-                    hxd = Hm[:2, :2] @ (-k * vel)
-                    W[self.ix[k][:2], self.idt] += y[r] * hxd
-                    W[self.idt, self.ix[k][:2]] += y[r] * hxd
-                    W[self.idt, self.idt] += y[r] * float((-k * vel) @ hxd)
+                    hxd = Hm[:, :2] @ (-k * vel)          # (x, y, theta)-dt: a footprint that turns with the pose has a heading-dt term too
+                    W[self.ix[k], self.idt] += y[r] * hxd
+                    W[self.idt, self.ix[k]] += y[r] * hxd
+                    W[self.idt, self.idt] += y[r] * float((-k * vel) @ hxd[:2])
             r += 1
         if self.ball_row:
             S = R.weight_matrix(cfg.terminal_ball_S)
@@ -648,6 +648,10 @@ class IpmOptions:
     elastic_ap: float = 5e-2
     elastic_prog: float = 0.8
     elastic_trigger: int = 5
+    # Iterative refinement of every dense KKT solve (the reference iterate of tests/_truncated.py): `refine_steps` rounds of residual rhs - K sol in np.longdouble (x87
+    # extended precision, 64-bit mantissa: required, see refine_solution), correction solved in fp64, update accumulated in np.longdouble and rounded once at the end.
+    # 0 (the default, every golden fixture): the plain np.linalg.solve, nothing else runs.
+    refine_steps: int = 0
     verbose: bool = False
 
 
@@ -685,6 +689,21 @@ def kkt_inertia(K: np.ndarray):
             elif d[i, i] < 0: neg += 1
             i += 1
     return pos, neg
+
+
+def refine_solution(K: np.ndarray, rhs: np.ndarray, sol: np.ndarray, steps: int):
+    """`steps` rounds of iterative refinement of sol ~ K^-1 rhs: residual in np.longdouble, correction by an fp64 solve, the sum kept in np.longdouble and rounded to fp64
+    once at the end.  Fails loudly where np.longdouble is not wider than fp64 (the residual would then carry the very rounding it is meant to remove).
+    Returns (refined sol, (max |K sol - rhs| in fp64 arithmetic before, after))."""
+    if not np.finfo(np.longdouble).eps < 2e-19:
+        raise RuntimeError(f"IpmOptions.refine_steps needs an extended-precision np.longdouble (eps < 2e-19), this platform has eps = {np.finfo(np.longdouble).eps}")
+    Kl, rl = K.astype(np.longdouble), rhs.astype(np.longdouble)
+    acc = sol.astype(np.longdouble)
+    for _ in range(steps):
+        res = rl - Kl @ acc
+        acc = acc + np.linalg.solve(K, res.astype(np.float64)).astype(np.longdouble)
+    out = acc.astype(np.float64)
+    return out, (float(np.abs(K @ sol - rhs).max()), float(np.abs(K @ out - rhs).max()))
 
 
 def controls_from_states(cfg: R.OcpConfig, init: R.Trajectory) -> R.Trajectory:
@@ -922,6 +941,7 @@ def solve(cfg: R.OcpConfig, inp: R.CycleInputs, init: R.Trajectory, relevant=Non
         started_zero = delta == 0.0
         ok = False
         ntry = 0
+        lin_res = []          # refine_steps > 0: (fp64 residual before, after) of every factorisation of this iteration
         while True:
             K = np.zeros((nv + mc, nv + mc))
             K[:nv, :nv] = Hc + delta * np.eye(nv)
@@ -935,6 +955,10 @@ def solve(cfg: R.OcpConfig, inp: R.CycleInputs, init: R.Trajectory, relevant=Non
             try:
                 sol = np.linalg.solve(K, rhs)
                 good = np.all(np.isfinite(sol))
+                if good and opt.refine_steps > 0:
+                    sol, lr = refine_solution(K, rhs, sol, opt.refine_steps)
+                    lin_res.append(lr)
+                    good = np.all(np.isfinite(sol))
             except np.linalg.LinAlgError:
                 good = False
             if good:
@@ -1131,7 +1155,8 @@ def solve(cfg: R.OcpConfig, inp: R.CycleInputs, init: R.Trajectory, relevant=Non
         piL = np.where(hasL, np.minimum(np.maximum(piL, mu / (kS * dLn)), kS * mu / dLn), 0.0)
         piU = np.where(hasU, np.minimum(np.maximum(piU, mu / (kS * dUn)), kS * mu / dUn), 0.0)
         it += 1
-        history.append(dict(it=it, mu=mu, e0=e0, theta=theta, alpha=alpha, a_d=a_d, delta=delta, rho=rho, ls=ls, f=ev["f"]))
+        tj = nlp.to_traj(v)          # the iterate after this step: what a solve capped at max_iter = it returns
+        history.append(dict(it=it, mu=mu, e0=e0, theta=theta, alpha=alpha, a_d=a_d, delta=delta, rho=rho, ls=ls, f=ev["f"], a_p=a_p, lin_res=lin_res, x=tj.x, u=tj.u, dt=tj.dt))
         if opt.verbose:
             print(f"{it:3d} f={ev['f']:.6f} e0={e0:.2e} mu={mu:.1e} th={theta:.2e} a={alpha:.3f} ad={a_d:.3f} dl={delta:.1e} ls={ls} rho={rho:.2e}")
 

@@ -1,0 +1,313 @@
+"""Truncated solves: the iterate after `cap` interior-point iterations (mpc_config.max_iter = cap, status max_iter), on the CPU side.
+
+Shared by tests/test_truncated_reference.py (CPU) and tests/test_gpu_truncated_solves.py (-m gpu).  Holds
+  * the case table (CASES): a configuration for the ABI and for oracle/se2_nlp.py, an inputs generator, optional obstacles;
+  * the REFERENCE iterate of a case and cap: the numpy dense interior-point method with every KKT solve refined in extended precision
+    (oracle/ipm_dense.py, IpmOptions.refine_steps = REFINE);
+  * the CPU SOLVERS' iterates for the same cap -- the unrefined numpy solve (LAPACK LU of the dense KKT matrix), the C oracle (banded LU, oracle/mpc_oracle.c) and, where the
+    harness has the case's features, the host build of the kernel core (Riccati sweeps, tests/host_harness); they share no linear algebra;
+  * the oracle's history of the case (delta, alpha, a_p, ls per iteration);
+  * the distance used everywhere (dist): max over x, u and dt of the absolute difference, headings modulo 2 pi.
+Everything is cached per process: a reference is computed once and handed out read-only."""
+import ctypes as C
+import dataclasses
+import functools
+import os
+import subprocess
+from typing import Callable, Optional
+
+import numpy as np
+
+from oracle import c_oracle as CO
+from oracle import ipm_dense as I
+from oracle import kkt_check as KC
+from oracle import se2_nlp as R
+from mpc_local_planner_amd import _abi as A
+from mpc_local_planner_amd import workloads as W
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+B = 12                      # instances per case (one launch on the device)
+REFINE = 2                  # rounds of iterative refinement of the reference's KKT solves
+FLOOR = 1e-13               # floor of the fp64 yardstick e_cpu: below it the distance is the rounding of the outputs themselves
+FLOOR32 = 1e-6              # the same for fp32
+E_CPU_MAX = 1e-10           # section (b) of tests/test_truncated_reference.py: a condition on the inputs, not a tolerance of the device
+
+LINE_FOOTPRINT = (R.FOOTPRINT_LINE, (0.0, 0.0, 0.4, 0.0), 0.27)          # the car-like example's line footprint and its min_obstacle_dist
+FQ = [[2.0, 0.3, -0.1], [0.3, 1.5, 0.2], [-0.1, 0.2, 0.4]]
+FR = [[0.1, 0.02], [0.02, 0.05]]
+FQF = [[8.0, 1.0, 0.0], [1.0, 9.0, 0.5], [0.0, 0.5, 0.6]]
+FS = [[1.0, 0.2, 0.0], [0.2, 1.0, 0.1], [0.0, 0.1, 0.5]]
+
+MODELS = {
+    # model -> (ABI config builder, se2_nlp config builder, inputs(B) -> x0, xf, u_prev, dt_prev)
+    "carlike": (A.config_carlike_min_time, R.config_carlike_min_time, lambda b: W.carlike_min_time_inputs(b, seed=11, goal_range=(1.0, 4.0))),
+    "unicycle": (A.config_unicycle_quadratic, R.config_unicycle_quadratic, lambda b: W.unicycle_quadratic_inputs(b, seed=12)),
+    "bicycle": (A.config_bicycle_min_time, R.config_bicycle_min_time, lambda b: W.bicycle_min_time_inputs(b, seed=53, goal_range=(1.5, 2.5))),      # (seed 13 with goals of 1 .. 5 m regularises 2 of 12 instances at n = 43: too few for section (c))
+}
+
+
+@dataclasses.dataclass(frozen=True)
+class Case:
+    family: str
+    model: str
+    n: int
+    caps: tuple = (1, 2, 4)
+    abi: tuple = ()                      # ((keyword, value), ...) of the ABI config builder
+    ocfg: tuple = ()                     # ((field, value), ...) set on the se2_nlp.OcpConfig
+    ipm: tuple = ()                      # IpmOptions keywords of the numpy solves
+    c: tuple = ()                        # c_oracle.from_nlp_config keywords
+    inputs: Optional[Callable] = None    # B -> (x0, xf, u_prev, dt_prev[, obstacles]); None: the model's generator
+    max_rows: int = 4
+    host: bool = True                    # the host build of the kernel core has the case's features
+    fp32: bool = False
+    n_grid: Optional[tuple] = None       # per-instance grid sizes (mpc_set_grid_sizes); n is then the handle's capacity
+    dt_prev0: bool = False               # dt_prev = 0: the rate rows of stage 0 are dropped
+
+
+def _points_beside_the_path(x0, xf, seed, n_obst, lo, hi):
+    rng = np.random.default_rng(seed)
+    b = x0.shape[0]
+    d = xf[:, None, :2] - x0[:, None, :2]
+    nrm = np.stack([-d[..., 1], d[..., 0]], -1) / np.linalg.norm(d, axis=-1, keepdims=True)
+    pts = x0[:, None, :2] + rng.uniform(0.25, 0.75, (b, n_obst, 1)) * d + rng.uniform(lo, hi, (b, n_obst, 1)) * rng.choice([-1.0, 1.0], (b, n_obst, 1)) * nrm
+    return np.full(b, n_obst, np.int32), np.ones((b, n_obst), np.int32), pts.reshape(b, n_obst, 1, 2)
+
+
+def _unicycle_points(b):
+    """three point obstacles 0.05 .. 0.35 m beside the start-goal line, d_min = 0.2: rows start violated or close to active (the placement of
+    test_active_clearance_rows_vs_c_oracle scaled down to points and a 2 .. 4 m goal)"""
+    x0, xf, up, dtp = W.unicycle_quadratic_inputs(b, seed=14, goal_range=(2.0, 4.0))
+    return x0, xf, up, dtp, _points_beside_the_path(x0, xf, 15, 3, 0.05, 0.35)
+
+
+def _unicycle_polygons(b):
+    return W.unicycle_obstacle_inputs(b, seed=16, n_obst=4, max_vertices=5, goal_range=(2.0, 4.0), lateral=(0.15, 0.8))
+
+
+def _carlike_moving(b):
+    return W.carlike_moving_obstacle_inputs(b, seed=17, goal_range=(2.0, 5.0))
+
+
+_OBST_UNI = (("max_obstacles", 3), ("max_vertices", 1), ("max_obstacle_rows", 4))
+_L1 = dict(footprint_kind=LINE_FOOTPRINT[0], footprint_params=LINE_FOOTPRINT[1], enable_dynamic_obstacles=True, min_obstacle_dist=LINE_FOOTPRINT[2], force_inclusion_dist=0.5, cutoff_dist=2.5)
+_L2 = dict(Q=FQ, R=FR, Qf=FQF, terminal_ball_S=FS, terminal_ball_gamma=0.3)
+
+CASES = {}
+for _n in (3, 4, 8, 39):
+    CASES[f"serial_carlike_n{_n}"] = Case("serial", "carlike", _n)
+CASES["serial_unicycle_n8"] = Case("serial", "unicycle", 8)
+CASES["serial_bicycle_n8"] = Case("serial", "bicycle", 8)
+for _n in (40, 41, 42, 43, 65):
+    CASES[f"pit_carlike_n{_n}"] = Case("partitioned", "carlike", _n)
+CASES["pit_unicycle_n43"] = Case("partitioned", "unicycle", 43)
+CASES["pit_bicycle_n43"] = Case("partitioned", "bicycle", 43)
+CASES["fixed_carlike_n50"] = Case("fixed_layout", "carlike", 50)
+CASES["fixed_carlike_n50_dt_prev0"] = Case("fixed_layout", "carlike", 50, dt_prev0=True)
+for _n in (8, 43, 50):
+    CASES[f"global_carlike_n{_n}"] = Case("forms", "carlike", _n, abi=(("stage_data", A.STAGE_GLOBAL),))
+for _n in (8, 24):
+    CASES[f"two_wave_carlike_n{_n}"] = Case("forms", "carlike", _n, abi=(("two_wave_min_batch", 1),))
+CASES["ragged_carlike_39_40_43_50"] = Case("forms", "carlike", 50, n_grid=(39, 40, 43, 50) * 3)
+CASES["obst_unicycle_points_n43"] = Case("clearance", "unicycle", 43, abi=_OBST_UNI, inputs=_unicycle_points, host=False)
+CASES["obst_unicycle_polygons_n43"] = Case("clearance", "unicycle", 43, abi=(("max_obstacles", 4), ("max_vertices", 5), ("max_obstacle_rows", 4)), inputs=_unicycle_polygons, host=False)
+CASES["level1_carlike_line_moving_n43"] = Case("level1", "carlike", 43, abi=tuple(_L1.items()) + _OBST_UNI,
+                                               ocfg=tuple((k, v) for k, v in _L1.items()), inputs=_carlike_moving, host=False)
+# (the unicycle's quadratic form on the fixed grid never backtracks within four iterations; this one does, and half of its instances are regularised)
+_L1U = dict(dt_free=True, dt_lb=0.01, dt_ub=2.0, xf_fixed=(True, True, True), Qf=None, integral_form=True, R=(1.0, 0.5))
+CASES["level1_unicycle_integral_free_dt_n43"] = Case("level1", "unicycle", 43, abi=tuple(_L1U.items()),
+                                                     ocfg=tuple((k, np.array(v) if k == "R" else v) for k, v in _L1U.items()), host=False)
+CASES["level2_unicycle_full_weights_ball_n43"] = Case("level2", "unicycle", 43, abi=tuple((k, v) for k, v in _L2.items()),
+                                                      ocfg=tuple((k, np.array(v) if isinstance(v, list) else v) for k, v in _L2.items()), host=False)
+CASES["colloc_carlike_midpoint_n43"] = Case("collocation", "carlike", 43, abi=(("collocation", A.COLLOC_MIDPOINT),), ocfg=(("collocation", R.COLLOC_MIDPOINT),), host=False)
+CASES["colloc_carlike_crank_nicolson_n43"] = Case("collocation", "carlike", 43, abi=(("collocation", A.COLLOC_CRANK_NICOLSON),), ocfg=(("collocation", R.COLLOC_CRANK_NICOLSON),), host=False)
+CASES["algo_mu_monotone_carlike_n43"] = Case("algorithm", "carlike", 43, caps=(2, 4), abi=(("mu_strategy", A.MU_MONOTONE),), ipm=(("mu_strategy", "monotone"),), c=(("mu_strategy", 1),))
+CASES["algo_ls_merit_carlike_n43"] = Case("algorithm", "carlike", 43, caps=(2, 4), abi=(("line_search", A.LS_MERIT),), ipm=(("globalization", "merit"),), c=(("line_search", 0),))
+for _n in (8, 43):
+    CASES[f"fp32_carlike_n{_n}"] = Case("fp32", "carlike", _n, abi=(("precision", A.FP32), ("tol", 1e-4)), ipm=(("tol", 1e-4),), c=(("tol", 1e-4),), fp32=True)
+
+CASE_CAPS = [(name, cap) for name, cs in CASES.items() for cap in cs.caps]
+
+
+def abi_config(name, cap, n=None):
+    cs = CASES[name]
+    return MODELS[cs.model][0](cs.n if n is None else n, max_iter=cap, **dict(cs.abi))
+
+
+def nlp_config(name, n=None):
+    cs = CASES[name]
+    cfg = MODELS[cs.model][1](cs.n if n is None else n)
+    for k, v in cs.ocfg:
+        setattr(cfg, k, tuple(v) if k == "footprint_params" else v)
+    return cfg
+
+
+@functools.lru_cache(maxsize=None)
+def inputs(name):
+    """(x0, xf, u_prev, dt_prev, obstacles or None, grid sizes (B,)) of a case; read-only"""
+    cs = CASES[name]
+    out = (cs.inputs or MODELS[cs.model][2])(B)
+    x0, xf, up, dtp = out[:4]
+    if cs.dt_prev0:
+        dtp = np.zeros_like(dtp)
+    obstacles = out[4] if len(out) > 4 else None
+    ng = np.asarray(cs.n_grid if cs.n_grid is not None else [cs.n] * B, np.int32)
+    for a in (x0, xf, up, dtp, ng) + tuple(obstacles or ()):
+        a.setflags(write=False)
+    return x0, xf, up, dtp, obstacles, ng
+
+
+def dist(a, b, n=None):
+    """a, b: (x (n', 3), u (>= n - 1, 2), dt) of ONE instance; the first n grid points count.  max |difference| over x, u and dt, headings modulo 2 pi."""
+    xa, ua, da = a
+    xb, ub, db = b
+    n = xa.shape[0] if n is None else n
+    dx = np.abs(xa[:n] - xb[:n])
+    dx[:, 2] = np.abs(np.arctan2(np.sin(xa[:n, 2] - xb[:n, 2]), np.cos(xa[:n, 2] - xb[:n, 2])))
+    return float(max(dx.max(), np.abs(ua[:n - 1] - ub[:n - 1]).max(), abs(float(da) - float(db))))
+
+
+def dist_batch(a, b, ng):
+    """a, b: (x (B, n, 3), u (B, n, 2), dt (B,)) -> (B,) distances over each instance's own grid"""
+    return np.array([dist((a[0][i], a[1][i], a[2][i]), (b[0][i], b[1][i], b[2][i]), int(ng[i])) for i in range(len(ng))])
+
+
+# ---- numpy: the reference (refined) and the unrefined solve -----------------------------------------------------------------------------------------------------------
+def _same_problem(name):
+    """the first case of the table that poses the same problems to the CPU solvers (cases that differ only in how the device runs them share one reference)"""
+    sig = lambda cs: (cs.model, cs.n, repr(cs.ocfg), cs.ipm, cs.c, cs.inputs, cs.max_rows, cs.n_grid, cs.dt_prev0, max(cs.caps))
+    return next(k for k, cs in CASES.items() if sig(cs) == sig(CASES[name]))
+
+
+def numpy_run(name, refine):
+    return _numpy_run(_same_problem(name), refine)
+
+
+@functools.lru_cache(maxsize=None)
+def _numpy_run(name, refine):
+    """One run per instance to the case's largest cap; the iterates of the smaller caps are read off history (the same statements ran: max_iter only bounds the loop).
+    Returns {cap: (x (B, n, 3), u (B, n, 2), dt (B,), status (B,), iters (B,))} and the histories [B][iteration]."""
+    cs = CASES[name]
+    x0, xf, up, dtp, obstacles, ng = inputs(name)
+    top = max(cs.caps)
+    out = {cap: (np.zeros((B, cs.n, 3)), np.zeros((B, cs.n, 2)), np.zeros(B), np.full(B, -1, np.int32), np.zeros(B, np.int32)) for cap in cs.caps}
+    hist = []
+    for i in range(B):
+        n = int(ng[i])
+        cfg = nlp_config(name, n)
+        obs = KC.obstacle_list(*(a[i] for a in obstacles)) if obstacles is not None else []
+        inp = R.CycleInputs(x0=x0[i], xf=xf[i], u_prev=up[i], dt_prev=float(dtp[i]), obstacles=obs)
+        init = R.cold_start(cfg, x0[i], xf[i])
+        rel, reld = R.associate_obstacles(cfg, init, obs, max_rows=cs.max_rows) if obs else (None, None)
+        res = I.solve(cfg, inp, init, relevant=rel, relevant_dyn=reld, opt=I.IpmOptions(max_iter=top, refine_steps=refine, **dict(cs.ipm)))
+        hist.append(res.history)
+        for cap in cs.caps:
+            x, u, dt, st, it = out[cap]
+            if len(res.history) >= cap:          # the run with max_iter = cap ends here: status max_iter unless it is the last iterate of a run that stopped by itself
+                h = res.history[cap - 1]
+                x[i, :n], u[i, :n - 1], dt[i] = h["x"], h["u"], h["dt"]
+                u[i, n - 1] = u[i, n - 2]
+                st[i], it[i] = (res.status if cap == top else 1), cap
+            else:
+                st[i], it[i] = res.status, res.iters
+    for arrs in out.values():
+        for a in arrs:
+            a.setflags(write=False)
+    return out, hist
+
+
+def reference(name, cap):
+    return numpy_run(name, REFINE)[0][cap]
+
+
+def history(name):
+    return numpy_run(name, REFINE)[1]
+
+
+# ---- the C oracle and the host build of the kernel core ---------------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _host_lib():
+    src = os.path.join(HERE, "host_harness", "host_solver.cpp")
+    out = os.path.join(HERE, "host_harness", "_build", "libmpc_hostdbg.so")
+    csrc = os.path.join(HERE, "..", "mpc_local_planner_amd", "csrc")
+    deps = [src, os.path.join(HERE, "host_harness", "ipm_serial.hpp"), os.path.join(csrc, "mpc_core.hpp"), os.path.join(csrc, "mpc_problem.hpp"), os.path.join(HERE, "..", "include", "mpc_hip.h")]
+    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in deps):          # the rule of tests/test_host_core.py: one library for both
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", src, "-o", out], check=True)
+    return C.CDLL(out)
+
+
+def _groups(ng):
+    return [(int(n), np.flatnonzero(ng == n)) for n in sorted(set(int(v) for v in ng))]
+
+
+def _batched(name, solve_group):
+    """runs solve_group(n, idx) -> (x, u, dt, status, iters) for every grid size of the case and scatters into capacity-sized arrays"""
+    cs = CASES[name]
+    ng = inputs(name)[5]
+    x, u, dt, st, it = np.zeros((B, cs.n, 3)), np.zeros((B, cs.n, 2)), np.zeros(B), np.zeros(B, np.int32), np.zeros(B, np.int32)
+    for n, idx in _groups(ng):
+        r = solve_group(n, idx)
+        x[idx, :n], u[idx, :n], dt[idx], st[idx], it[idx] = r[0], r[1], r[2], r[3], r[4]
+    return x, u, dt, st, it
+
+
+def c_oracle_iterate(name, cap):
+    return _c_oracle_iterate(_same_problem(name), cap)
+
+
+@functools.lru_cache(maxsize=None)
+def _c_oracle_iterate(name, cap):
+    cs = CASES[name]
+    x0, xf, up, dtp, obstacles, _ = inputs(name)
+    CO.build()
+
+    def run(n, idx):
+        cfg = nlp_config(name, n)
+        oc = CO.from_nlp_config(cfg, max_iter=cap, **dict(cs.c))
+        kw = {}
+        if obstacles is not None:
+            kw = dict(obstacles=tuple(np.ascontiguousarray(a[idx]) for a in obstacles), obst=CO.obst_from_nlp_config(cfg, obstacles[1].shape[1], obstacles[2].shape[2], cs.max_rows))
+        return CO.solve_batch(oc, x0[idx], xf[idx], up[idx], dtp[idx], **kw)
+    return _batched(name, run)
+
+
+@functools.lru_cache(maxsize=None)
+def host_iterate(name, cap, fp32=False):
+    """the host build of the kernel core (Riccati sweeps of tests/host_harness/ipm_serial.hpp); fp32 = the whole solve in float"""
+    cs = CASES[name]
+    x0, xf, up, dtp, obstacles, _ = inputs(name)
+    assert obstacles is None and cs.host
+    lib = _host_lib()
+
+    def run(n, idx):
+        cfg = abi_config(name, cap, n)
+        cfg.precision = A.FP32 if fp32 else A.FP64
+        a = [np.ascontiguousarray(v[idx]) for v in (x0, xf, up, dtp)]
+        k = len(idx)
+        xo = np.zeros((k, n, 3)); uo = np.zeros((k, n, 2)); do = np.zeros(k); st = np.zeros(k, np.int32); it = np.zeros(k, np.int32); kkt = np.zeros(k)
+        p = lambda v: v.ctypes.data_as(C.c_void_p)
+        lib.hostdbg_solve(C.byref(cfg), C.c_int(k), p(a[0]), p(a[1]), p(a[2]), p(a[3]), None, None, None, p(xo), p(uo), p(do), p(st), p(it), p(kkt))
+        return xo, uo, do, st, it
+    return _batched(name, run)
+
+
+def cpu_solvers(name, cap):
+    """{solver: (x, u, dt, status, iters)} of the fp64 CPU solvers of a case"""
+    cs = CASES[name]
+    out = {"numpy": numpy_run(name, 0)[0][cap], "c_oracle": c_oracle_iterate(name, cap)}
+    if cs.host:
+        out["host_core"] = host_iterate(name, cap)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def e_cpu(name, cap):
+    """(B,) the largest distance of an fp64 CPU solver to the reference: what linear algebra alone moves the iterate by"""
+    ref, ng = reference(name, cap), inputs(name)[5]
+    return np.max([dist_batch(s, ref, ng) for s in cpu_solvers(name, cap).values()], axis=0)
+
+
+@functools.lru_cache(maxsize=None)
+def e_cpu32(name, cap):
+    """(B,) the fp32 yardstick: the host build of the kernel core in float against the reference"""
+    return dist_batch(host_iterate(name, cap, fp32=True), reference(name, cap), inputs(name)[5])

@@ -482,6 +482,45 @@ int mpc_check_feasibility(mpc_solver* s, int32_t B, const double* x, const uint8
                           const double* origin, const double* footprint_spec, int32_t n_spec, double inscribed_radius,
                           double min_resolution_collision_check_angular, int32_t look_ahead_idx, int32_t* feasible);
 
+/* ---- What a trajectory is worth under the handle's NLP: any trajectory -- a solve's output, a warm start, a plan guess, one from outside -- evaluated by a kernel
+ * of its own (one wavefront per instance, csrc/mpc_evaluate.hpp; the solve kernels are not involved).  Everything is computed in fp64 whatever mpc_config.precision
+ * is, in the REFERENCE's form of the rows (not the solver's rescaled one), so the numbers compare with a host-side restatement of the NLP directly.
+ *   The trajectory is read as a solve would start from it: x_0 := x0 and the fixed goal components := xf (full_discretization_grid_base_se2.cpp:101-110), the
+ *   headings of x0 and xf normalised (math_utils.h:81-91) as the solve kernel does; d_x0 == NULL takes x[b][0], d_xf == NULL the last grid point -- a solver output
+ *   evaluates as itself.  Layouts: those of x_out / u_out / dt_out, stride cfg.n; per-instance grid sizes (mpc_set_grid_sizes, the controller's) are honoured and
+ *   rows at and beyond n_b are never read; on the fixed grid dt is cfg.dt_ref and d_dt is not read (may be NULL).  Parameter sets apply (instance b: sets[set_of[b]]);
+ *   the handle's via-points attach to the closest grid point of THIS trajectory (MinTimeViaPointsCost::update, min_time_via_points_cost.cpp:39-117).
+ *   objective: (n_b - 1) dt for minimum time (min_time_via_points_cost.cpp:52-56,120-124) plus, with via-points, position_weight |vp - p_k|^2 + orientation_weight
+ *     normalize_theta(theta_vp - theta_k) (linear, as coded: :125-145); the quadratic form as a sum over k = 0..n_b-2 (quadratic_cost_se2.cpp:31-52), as left sum dt l_k or
+ *     trapezoid 0.5 dt (l(x_k, u_k) + l(x_{k+1}, u_k)) with integral_form (:54-83, finite_differences_grid_se2.cpp:61-75), plus (n_b - 1) dt with
+ *     hybrid_cost_minimum_time; off-diagonal weights included; plus the terminal cost on a goal that is not completely fixed (final_state_conditions_se2.cpp:30-52,
+ *     finite_differences_grid_se2.cpp:128-133).  No barrier and no elastic terms.
+ *   eq_violation: max over intervals and components of |f - (x_{k+1} - x_k) / dt| (heading difference normalised), forward differences (fd_collocation_se2.h:54-69),
+ *     midpoint (f at interpolate_angle(theta_k, theta_{k+1}, 0.5), :91-108) or Crank-Nicolson as coded (1.5 f(x_{k+1}, u_k) + 0.5 f(x_k, u_k), :130-147).
+ *   ineq_violation: max(0, row) over the control box and the dt box (src/controller.cpp:511-543, :242-244), the control-rate rows du_lb - (u_k - u_{k-1}) / dt and
+ *     (u_k - u_{k-1}) / dt - du_ub (stage_inequality_se2.cpp:191-222) -- the first against u_prev / dt_prev when dt_prev != 0 (:197-201), the final one against u_ref = 0
+ *     (finite_differences_grid_se2.cpp:150) --, and the terminal ball xd' S xd - gamma (final_state_conditions_se2.cpp:54-64).  Clearance rows are NOT part of it:
+ *   clearance: geometry only -- min over k = 1..n_b-2 and ALL valid obstacles of the instance (o < n_obstacles[b] with n_vertices[b][o] >= 1; an empty slot is skipped, as in the solve) of teb's footprint-to-obstacle distance (every footprint x point / circle /
+ *     line / polygon; a given radius is subtracted, as in the solve), the obstacle moved by k dt velocity with enable_dynamic_obstacles
+ *     (stage_inequality_se2.cpp:164-189); independent of the association and of max_obstacle_rows; the caller compares it with min_obstacle_dist.  +inf and
+ *     closest = (-1, -1) for an instance without obstacles (or d_obstacles == NULL).
+ * Results do not depend on B, on the position in the batch or on the run (every reduction has a fixed order).  A non-finite input of an instance gives NaN outputs
+ * (closest -1, -1) for that instance only.  DEVICE pointers; runs on the solver's stream without a host round trip, so it composes behind mpc_step_batch_device /
+ * mpc_controller_step_batch_device.  MPC_EINVAL: d_x, d_u or d_out NULL (d_dt on the variable grid); MPC_EBATCH: B above max_batch, or above the batch that grid sizes,
+ * parameter sets or via-points were given for. */
+typedef struct mpc_eval_out {     /* every pointer nullable; [B] unless noted */
+    double*  objective;           /* the NLP's objective at the trajectory (no barrier, no elastic terms) */
+    double*  eq_violation;        /* max |collocation residual| over intervals and components */
+    double*  ineq_violation;      /* max(0, row) over control box, dt box, control-rate rows (first row against u_prev / dt_prev included, when dt_prev != 0; final row against u_ref = 0 included), terminal ball */
+    double*  clearance;           /* min over k = 1..n_b-2 and ALL valid obstacles o of dist(footprint(x_k), obstacle o [moved by k dt v_o when enable_dynamic_obstacles]); +inf without obstacles */
+    int32_t* closest;             /* [B][2]: (k, o) of that minimum, lowest (k, o) on ties; (-1, -1) without obstacles */
+} mpc_eval_out;
+int mpc_evaluate_batch_device(mpc_solver* s, int32_t B, const double* d_x0, const double* d_xf, const double* d_u_prev, const double* d_dt_prev,
+                              const double* d_x, const double* d_u, const double* d_dt, const mpc_obstacles* d_obstacles, const mpc_eval_out* d_out);
+/* Same with HOST pointers, in *obstacles and *out too (staged through buffers of the handle that the first call allocates; blocking). */
+int mpc_evaluate_batch(mpc_solver* s, int32_t B, const double* x0, const double* xf, const double* u_prev, const double* dt_prev,
+                       const double* x, const double* u, const double* dt, const mpc_obstacles* obstacles, const mpc_eval_out* out);
+
 int mpc_synchronize(mpc_solver* s);
 
 /* Duration (ms) of the solve kernel of the most recent mpc_solve_batch* call, measured with
@@ -503,7 +542,7 @@ int mpc_occupancy(mpc_solver* s, int32_t B, int32_t* workgroups_per_cu, int64_t*
 /* Human-readable text of the last HIP/runtime error on this thread ("" if none). */
 const char* mpc_last_error(void);
 
-/* Library/ABI version: major*10000 + minor*100 + patch. */
+/* Library/ABI version: major*10000 + minor*100 + patch.  900 = 0.9.0: mpc_evaluate_batch* and struct mpc_eval_out are new, nothing else changed. */
 int32_t mpc_version(void);
 
 #ifdef __cplusplus

@@ -127,6 +127,17 @@ class MpcObstacles(C.Structure):
     ]
 
 
+class MpcEvalOut(C.Structure):
+    """struct mpc_eval_out (include/mpc_hip.h): raw addresses (host or device), each nullable."""
+    _fields_ = [
+        ("objective", C.c_void_p),
+        ("eq_violation", C.c_void_p),
+        ("ineq_violation", C.c_void_p),
+        ("clearance", C.c_void_p),
+        ("closest", C.c_void_p),
+    ]
+
+
 class MpcCycleParams(C.Structure):
     """struct mpc_cycle_params (include/mpc_hip.h): the controller / grid options of mpc_controller_step_batch*; field-for-field."""
     _fields_ = [

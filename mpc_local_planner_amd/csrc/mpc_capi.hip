@@ -21,6 +21,7 @@
 #include "mpc_feasibility.hpp"
 #include "mpc_grid_update.hpp"
 #include "mpc_controller_cycle.hpp"
+#include "mpc_evaluate.hpp"
 
 namespace {
 
@@ -48,7 +49,7 @@ struct Buf {
     int fill;           // the idle contents mpc_create writes
     bool reset, pinned; // mpc_reset writes them again; host memory (hipHostMalloc)
 };
-enum { BUF_TAB, BUF_SET_OF, BUF_H_TAB, BUF_STAGE, BUF_H_IN, BUF_CYC_LIVE, BUF_CYC, BUF_CYC_HSTAGE, BUF_CYC_DSTAGE, BUF_NAMED };      // the entries other entry points ask for (declare_buffers assigns them by index)
+enum { BUF_TAB, BUF_SET_OF, BUF_H_TAB, BUF_STAGE, BUF_H_IN, BUF_CYC_LIVE, BUF_CYC, BUF_CYC_HSTAGE, BUF_CYC_DSTAGE, BUF_EVAL_HSTAGE, BUF_EVAL_DSTAGE, BUF_NAMED };      // the entries other entry points ask for (declare_buffers assigns them by index)
 
 struct mpc_solver {
     mpc_config cfg;
@@ -56,11 +57,13 @@ struct mpc_solver {
     mpc::Problem<float> P32;
     std::vector<Buf> bufs;
     // device table of problem records (mpc_set_parameter_sets): entry 0 is the handle's own configuration, entries 1 .. n_sets the sets in force; a solve
-    // kernel copies entry set_of[b] (entry 0 while p_set_of is NULL) into the LDS of instance b.  One allocation: fp64 records | fp32 records | dt_ref per entry
+    // kernel copies entry set_of[b] (entry 0 while p_set_of is NULL) into the LDS of instance b.  One allocation: fp64 records | fp32 records | dt_ref per entry |
+    // the fp64 records of mpc_evaluate_batch* (mpc_evaluate.hpp) per entry
     unsigned char* d_tab;
     mpc::Problem<double>* d_tab64;      // NULL for a handle without fp64 launches
     mpc::Problem<float>* d_tab32;       // NULL for a handle without fp32 launches
     double* d_dtref;                    // dt_ref of every entry (single-step grid adaptation of mpc_grid_update_device)
+    mpc::EvalParams* d_tabev;           // the evaluation's record of every entry (every precision: mpc_evaluate_batch* works in fp64)
     int tab_cap;                        // entries the table has room for
     int32_t* d_set_of;                  // [max_batch] table entry of instance b (1 + its set), allocated by the first mpc_set_parameter_sets
     const int32_t* p_set_of;            // what the kernels read: d_set_of while sets are in force, else NULL
@@ -101,6 +104,7 @@ struct mpc_solver {
     int32_t* d_cyc_live;
     unsigned char* d_cyc;
     unsigned char *h_cyc_stage, *d_cyc_stage;      // staging of the host variant's own inputs (plans, feedback, reset) and of reinit_out, grows on demand
+    unsigned char *h_eval_stage, *d_eval_stage;    // staging of mpc_evaluate_batch (inputs, then the five outputs), allocated by its first call, grows on demand
 };
 
 // the pieces of the slot-state block
@@ -171,12 +175,12 @@ static hipError_t stage_carve(mpc_solver* s, const size_t* sz, int count, void**
 
 // byte offsets of the three pieces of a record table of `entries` entries (256-byte aligned), and its size
 struct TabLayout {
-    size_t o64, o32, odt, bytes;
+    size_t o64, o32, odt, oev, bytes;
     TabLayout(const mpc_config& c, size_t entries) {
         mpc::Packer p;
         o64 = p.take(c.precision != MPC_FP32 ? entries * sizeof(mpc::Problem<double>) : 0);
         o32 = p.take(c.precision != MPC_FP64 ? entries * sizeof(mpc::Problem<float>) : 0);
-        odt = p.take(entries * 8); bytes = p.off;
+        odt = p.take(entries * 8); oev = p.take(entries * sizeof(mpc::EvalParams)); bytes = p.off;
     }
 };
 
@@ -189,6 +193,9 @@ static void put_entry(const mpc_config& hcfg, const mpc_config& c, size_t entrie
     if (hcfg.precision != MPC_FP32) memcpy(img + t.o64 + e * sizeof(P64), &P64, sizeof(P64));
     if (hcfg.precision != MPC_FP64) memcpy(img + t.o32 + e * sizeof(P32), &P32, sizeof(P32));
     memcpy(img + t.odt + e * 8, &c.dt_ref, 8);
+    mpc::EvalParams ev;
+    mpc::fill_eval_params(c, ev);
+    memcpy(img + t.oev + e * sizeof(ev), &ev, sizeof(ev));
 }
 
 static void point_tables(mpc_solver* s) {
@@ -196,6 +203,7 @@ static void point_tables(mpc_solver* s) {
     s->d_tab64 = s->cfg.precision != MPC_FP32 ? reinterpret_cast<mpc::Problem<double>*>(s->d_tab + t.o64) : nullptr;
     s->d_tab32 = s->cfg.precision != MPC_FP64 ? reinterpret_cast<mpc::Problem<float>*>(s->d_tab + t.o32) : nullptr;
     s->d_dtref = reinterpret_cast<double*>(s->d_tab + t.odt);
+    s->d_tabev = reinterpret_cast<mpc::EvalParams*>(s->d_tab + t.oev);
 }
 
 // The handle's buffers: which of them its configuration gets at mpc_create (the others stay at 0 bytes), their sizes, the idle contents and whether mpc_reset
@@ -222,6 +230,8 @@ static void declare_buffers(mpc_solver* s) {
     s->bufs[BUF_CYC] = {(void**)&s->d_cyc, 0, 0, false, false};
     s->bufs[BUF_CYC_HSTAGE] = {(void**)&s->h_cyc_stage, 0, FILL_NONE, false, true};
     s->bufs[BUF_CYC_DSTAGE] = {(void**)&s->d_cyc_stage, 0, FILL_NONE, false, false};
+    s->bufs[BUF_EVAL_HSTAGE] = {(void**)&s->h_eval_stage, 0, FILL_NONE, false, true};       // the two of mpc_evaluate_batch: allocated by its first call
+    s->bufs[BUF_EVAL_DSTAGE] = {(void**)&s->d_eval_stage, 0, FILL_NONE, false, false};
     add(&s->h_out, cap.out_bytes, FILL_NONE, false, true);
     add(&s->d_in, cap.in_bytes);
     add(&s->d_out, cap.out_bytes);
@@ -300,7 +310,7 @@ void mpc_cycle_params_defaults(mpc_cycle_params* p) {
 }
 
 const char* mpc_last_error(void) { return g_err; }
-int32_t mpc_version(void) { return 800; }      // 0.8.0 (CHANGELOG.md has what each version brought)
+int32_t mpc_version(void) { return 900; }      // 0.9.0: mpc_evaluate_batch* (CHANGELOG.md has what each version brought)
 
 #ifdef MPC_PROFILE
 // developer build only (-DMPC_PROFILE): per-wave phase cycle counters of the last wave-kernel launch, mpc::kProfCols words per row
@@ -774,6 +784,7 @@ int mpc_set_parameter_sets(mpc_solver* s, int32_t n_sets, const mpc_config* sets
         if (s->d_tab64) HIP_TRY(hipMemcpyAsync(s->d_tab64 + 1, s->h_tab + t.o64 + sizeof(mpc::Problem<double>), (size_t)n_sets * sizeof(mpc::Problem<double>), hipMemcpyHostToDevice, s->stream));
         if (s->d_tab32) HIP_TRY(hipMemcpyAsync(s->d_tab32 + 1, s->h_tab + t.o32 + sizeof(mpc::Problem<float>), (size_t)n_sets * sizeof(mpc::Problem<float>), hipMemcpyHostToDevice, s->stream));
         HIP_TRY(hipMemcpyAsync(s->d_dtref + 1, s->h_tab + t.odt + 8, (size_t)n_sets * 8, hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(hipMemcpyAsync(s->d_tabev + 1, s->h_tab + t.oev + sizeof(mpc::EvalParams), (size_t)n_sets * sizeof(mpc::EvalParams), hipMemcpyHostToDevice, s->stream));
     }
     HIP_TRY(hipMemcpyAsync(s->d_set_of, so, (size_t)B * 4, hipMemcpyHostToDevice, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
@@ -1037,6 +1048,70 @@ int mpc_controller_state(mpc_solver* s, int32_t B, int32_t* seq, int32_t* empty,
         HIP_TRY(hipMemcpy(empty, s->d_cyc_live, nb * 4, hipMemcpyDeviceToHost));
         for (size_t b = 0; b < nb; ++b) empty[b] = empty[b] ? 0 : 1;
     }
+    return MPC_OK;
+}
+
+}  // extern "C"
+
+// ---- what a trajectory is worth under the handle's NLP (mpc_evaluate.hpp)
+
+extern "C" {
+
+int mpc_evaluate_batch_device(mpc_solver* s, int32_t B, const double* d_x0, const double* d_xf, const double* d_u_prev, const double* d_dt_prev,
+                              const double* d_x, const double* d_u, const double* d_dt, const mpc_obstacles* d_obstacles, const mpc_eval_out* d_out) {
+    g_err[0] = 0;
+    if (!s || !d_x || !d_u || !d_out || (s->cfg.dt_free && !d_dt)) { set_err("mpc_evaluate_batch_device: null argument (x, u, out; dt on the variable grid)"); return MPC_EINVAL; }
+    if (B <= 0) return MPC_OK;
+    if (B > s->max_batch) { set_err("mpc_evaluate_batch: B exceeds max_batch"); return MPC_EBATCH; }
+    if (s->use_ngrid && B > s->ngrid_B) { set_err("mpc_evaluate_batch: B exceeds the batch the per-instance grid sizes were set for (mpc_set_grid_sizes)"); return MPC_EBATCH; }
+    if (s->P64.n_via > 0 && s->p_nvia == s->d_nvia && s->nvia_B > 0 && B > s->nvia_B) {
+        set_err("mpc_evaluate_batch: B exceeds the batch the via-points were set for (mpc_set_via_points)"); return MPC_EBATCH; }
+    if (s->p_set_of && B > s->sets_B) { set_err("mpc_evaluate_batch: B exceeds the batch the parameter sets were given for (mpc_set_parameter_sets)"); return MPC_EBATCH; }
+    HIP_TRY(hipSetDevice(s->device));
+    mpc::EvalArgs a;
+    memset(&a, 0, sizeof(a));
+    a.tab = s->d_tabev; a.set_of = s->p_set_of; a.n_grid = s->use_ngrid ? s->d_ngrid : nullptr; a.n_stride = s->cfg.n;
+    a.x0 = d_x0; a.xf = d_xf; a.u_prev = d_u_prev; a.dt_prev = d_dt_prev; a.x = d_x; a.u = d_u; a.dt = d_dt;
+    if (s->cfg.max_obstacles > 0 && d_obstacles && d_obstacles->n_obstacles && d_obstacles->n_vertices && d_obstacles->vertices) a.ob = *d_obstacles;      // (without them: clearance +inf)
+    a.n_via = s->p_nvia; a.via = s->p_via; a.out = *d_out;
+    hipLaunchKernelGGL(mpc::evaluate_kernel, dim3(B), dim3(64), 0, s->stream, a);
+    HIP_TRY(hipGetLastError());
+    return MPC_OK;
+}
+
+int mpc_evaluate_batch(mpc_solver* s, int32_t B, const double* x0, const double* xf, const double* u_prev, const double* dt_prev,
+                       const double* x, const double* u, const double* dt, const mpc_obstacles* obstacles, const mpc_eval_out* out) {
+    g_err[0] = 0;
+    if (!s || !x || !u || !out || (s->cfg.dt_free && !dt)) { set_err("mpc_evaluate_batch: null argument (x, u, out; dt on the variable grid)"); return MPC_EINVAL; }
+    if (B <= 0) return MPC_OK;
+    if (B > s->max_batch) { set_err("mpc_evaluate_batch: B exceeds max_batch"); return MPC_EBATCH; }
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t q = s->stream;
+    const size_t nb = (size_t)B, n = (size_t)s->cfg.n, O = s->cfg.max_obstacles > 0 ? (size_t)s->cfg.max_obstacles : 0, V = s->cfg.max_vertices > 0 ? (size_t)s->cfg.max_vertices : 1;
+    const bool obst = O > 0 && obstacles && obstacles->n_obstacles && obstacles->n_vertices && obstacles->vertices;
+    // one pinned block and one device block: the inputs (one copy in), then the five outputs (one copy back)
+    enum { N_IN = 12, N_ALL = 17 };
+    const void* src[N_IN] = {x0, xf, u_prev, dt_prev, x, u, dt, obst ? obstacles->n_obstacles : nullptr, obst ? obstacles->n_vertices : nullptr, obst ? obstacles->vertices : nullptr,
+                             obst ? obstacles->radius : nullptr, obst ? obstacles->velocity : nullptr};
+    void* dst[N_ALL - N_IN] = {out->objective, out->eq_violation, out->ineq_violation, out->clearance, out->closest};
+    const size_t per[N_ALL] = {24, 24, 16, 8, n * 24, n * 16, 8, 4, O * 4, O * V * 16, O * 8, O * 16, 8, 8, 8, 8, 8};
+    size_t off[N_ALL], sz[N_ALL];
+    mpc::Packer pk;
+    for (int i = 0; i < N_ALL; ++i) { sz[i] = (i < N_IN ? src[i] != nullptr : dst[i - N_IN] != nullptr) ? nb * per[i] : 0; off[i] = pk.take(sz[i]); }
+    const size_t in_bytes = off[N_IN];
+    for (Buf* bf : {&s->bufs[BUF_EVAL_HSTAGE], &s->bufs[BUF_EVAL_DSTAGE]})
+        if (pk.off > bf->bytes) { HIP_TRY(hipStreamSynchronize(q)); HIP_TRY(buf_alloc(*bf, pk.off)); }
+    for (int i = 0; i < N_IN; ++i) if (sz[i]) memcpy(s->h_eval_stage + off[i], src[i], sz[i]);
+    auto dv = [&](int i) -> void* { return sz[i] ? (void*)(s->d_eval_stage + off[i]) : nullptr; };
+    if (in_bytes) HIP_TRY(hipMemcpyAsync(s->d_eval_stage, s->h_eval_stage, in_bytes, hipMemcpyHostToDevice, q));
+    const mpc_obstacles dob = {(const int32_t*)dv(7), (const int32_t*)dv(8), (const double*)dv(9), (const double*)dv(10), (const double*)dv(11)};
+    const mpc_eval_out dout = {(double*)dv(12), (double*)dv(13), (double*)dv(14), (double*)dv(15), (int32_t*)dv(16)};
+    const int rc = mpc_evaluate_batch_device(s, B, (const double*)dv(0), (const double*)dv(1), (const double*)dv(2), (const double*)dv(3), (const double*)dv(4), (const double*)dv(5),
+                                             (const double*)dv(6), &dob, &dout);
+    if (rc != MPC_OK) return rc;
+    if (pk.off > in_bytes) HIP_TRY(hipMemcpyAsync(s->h_eval_stage + in_bytes, s->d_eval_stage + in_bytes, pk.off - in_bytes, hipMemcpyDeviceToHost, q));
+    HIP_TRY(hipStreamSynchronize(q));
+    for (int i = N_IN; i < N_ALL; ++i) if (sz[i]) memcpy(dst[i - N_IN], s->h_eval_stage + off[i], sz[i]);
     return MPC_OK;
 }
 

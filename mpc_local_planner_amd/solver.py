@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._abi import MpcConfig, MpcCycleParams, MpcObstacles, MPC_OK
+from ._abi import MpcConfig, MpcCycleParams, MpcEvalOut, MpcObstacles, MPC_OK
 
 
 class MpcError(RuntimeError):
@@ -29,6 +29,16 @@ class BatchResult:
     dt: np.ndarray       # (B,)
     status: np.ndarray   # (B,) int32, 0 = converged
     iters: np.ndarray    # (B,) int32
+
+
+@dataclass
+class TrajectoryEval:
+    """what mpc_evaluate_batch reports for B trajectories (include/mpc_hip.h, struct mpc_eval_out)"""
+    objective: np.ndarray       # (B,)
+    eq_violation: np.ndarray    # (B,)
+    ineq_violation: np.ndarray  # (B,)
+    clearance: np.ndarray       # (B,)  +inf without obstacles
+    closest: np.ndarray         # (B, 2) int32: (grid point, obstacle) of the clearance, (-1, -1) without obstacles
 
 
 def _addr(a):
@@ -214,6 +224,31 @@ class BatchSolver:
                                               C.byref(ob) if ob is not None else None, v(x_out), v(u_out), v(dt_out), v(status),
                                               v(iters))
         self._check(rc)
+
+    def evaluate(self, x0, xf, x, u, dt, u_prev=None, dt_prev=None, obstacles=None) -> TrajectoryEval:
+        """Objective, largest equality / inequality violation and clearance to every obstacle of B trajectories under this solver's NLP (mpc_evaluate_batch), in
+        fp64 whatever the solver's precision is.  x (B, n, 3), u (B, n, 2), dt (B,) in the layout of BatchResult; x0 / xf (B, 3) or None (= the trajectory's own first /
+        last grid point); obstacles as for solve()."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        B, n = int(x.shape[0]), self.n
+        x, u, dt = _as_f64(x, (B, n, 3)), _as_f64(u, (B, n, 2)), _as_f64(dt, (B,))
+        x0, xf, u_prev, dt_prev = _as_f64(x0, (B, 3)), _as_f64(xf, (B, 3)), _as_f64(u_prev, (B, 2)), _as_f64(dt_prev, (B,))
+        ob, keep = self._pack_obstacles(obstacles, B) if obstacles is not None else (None, None)      # keep: the packed arrays have to outlive the call
+        r = TrajectoryEval(np.empty(B), np.empty(B), np.empty(B), np.empty(B), np.empty((B, 2), np.int32))
+        out = MpcEvalOut(r.objective.ctypes.data, r.eq_violation.ctypes.data, r.ineq_violation.ctypes.data, r.clearance.ctypes.data, r.closest.ctypes.data)
+        self._check(self._lib.mpc_evaluate_batch(self._h, B, _addr(x0), _addr(xf), _addr(u_prev), _addr(dt_prev), _addr(x), _addr(u), _addr(dt),
+                                                 C.byref(ob) if ob is not None else None, C.byref(out)))
+        return r
+
+    def evaluate_device(self, B: int, x0: Optional[int], xf: Optional[int], x: int, u: int, dt: Optional[int], objective: Optional[int] = None, eq_violation: Optional[int] = None,
+                        ineq_violation: Optional[int] = None, clearance: Optional[int] = None, closest: Optional[int] = None, u_prev: Optional[int] = None,
+                        dt_prev: Optional[int] = None, obstacles=None) -> None:
+        """mpc_evaluate_batch_device: the same with device addresses (ints), asynchronous on the solver's stream -- e.g. right behind solve_device on its outputs"""
+        v = lambda p: C.c_void_p(p) if p else None
+        ob = MpcObstacles(*(tuple(obstacles) + (None,) * (5 - len(obstacles)))) if obstacles is not None else None
+        out = MpcEvalOut(objective or None, eq_violation or None, ineq_violation or None, clearance or None, closest or None)
+        self._check(self._lib.mpc_evaluate_batch_device(self._h, int(B), v(x0), v(xf), v(u_prev), v(dt_prev), v(x), v(u), v(dt), C.byref(ob) if ob is not None else None,
+                                                        C.byref(out)))
 
     def set_grid_sizes(self, n_grid=None):
         """Per-instance grid sizes n_i <= cfg.n for the following solves (grid adaptation); None = uniform cfg.n."""

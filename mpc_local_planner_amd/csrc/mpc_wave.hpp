@@ -37,7 +37,7 @@
 #include "mpc_dpp_blocks.inc"
 
 #ifdef MPC_PROFILE
-namespace mpc { constexpr int kProfCols = 24, kProfTicks = 14; }      // words per workgroup / phase + glue counters among them (mpc_wave_debug.hpp has the map)
+namespace mpc { constexpr int kProfCols = 26, kProfTicks = 14; }      // words per workgroup / phase + glue counters among them (mpc_wave_debug.hpp has the map)
 __device__ long long g_mpc_prof[4096][mpc::kProfCols];
 #endif
 
@@ -81,6 +81,7 @@ struct IpmWave {
 #ifdef MPC_PROFILE
     mutable long long prof_mult = 0;
     mutable long long prof_loop = 0, prof_setup = 0, prof_fwd_loop = 0;    // ticks inside the backward stage loop / before it / inside the forward loop
+    mutable long long prof_pit_pre = 0, prof_fwd_pre = 0, prof_fwd_post = 0;    // partitioned sweeps: backward_pit up to its first stage / forward_pit before and behind its segment loop
 #endif
     int nfix;
     // candidate initial trajectories: this wave's candidate index, its iteration cap and the instance's winner word (global memory; NULL when
@@ -170,6 +171,11 @@ struct IpmWave {
     // explicit LDS pointers for the running-pointer loops (address-space inference gives up on per-lane selected pointers)
     typedef __attribute__((address_space(3))) T LdsT;
     __device__ __forceinline__ LdsT* lds(int word) const { return (LdsT*)sm + word; }
+    // the same from a BYTE offset, and a pointer moved by a number of bytes: the fixed-layout kernel's partitioned sweeps keep their per-lane offsets and steps as bytes (PitLaneConsts)
+    typedef __attribute__((address_space(3))) char LdsC;
+    __device__ __forceinline__ LdsT* ldsb(unsigned bytes) const { return (LdsT*)((LdsC*)(LdsT*)sm + bytes); }
+    __device__ __forceinline__ static LdsT* lds_adv(LdsT* p, int bytes) { return (LdsT*)((LdsC*)p + bytes); }
+    __device__ __forceinline__ static const LdsT* lds_adv(const LdsT* p, int bytes) { return (const LdsT*)((const LdsC*)p + bytes); }
     // ---- running pointers of the sweeps, in the sweeps' storage class: an LDS pointer, or (GS) a BYTE offset into the workgroup's global block.  W_*(): where the
     //      regions the sweeps stream through start (word index in that storage class); sw_step(): a stride in the units such a pointer advances by
     using SwRef = std::conditional_t<GS, unsigned, LdsT*>;

@@ -17,7 +17,8 @@
 //   phases (MPC_TICK)       0 kkt  1 barrier_terms  2 backward  3 forward  4 post  5 logs0 (barrier_logs at the current point)  6 trial  7 accept  8 trial_setup
 //   glue (MPC_GAP_END)      9 kkt -> barrier terms (error, stop tests, barrier update)   10 barrier terms -> a factorisation (pow, delta; between two factorisations)
 //                          11 line-search set-up (post -> trial_setup -> first trial; between two trials)   12 last trial -> accept   13 accept -> kkt (loop back edge)
-// and 19 .. 21 the sweeps' inner counters.  Every tick of the loop lands in exactly one counter: a phase stamps its own begin and end, a glue section runs from the last
+// and 19 .. 24 the sweeps' inner counters (parts of `backward` / `forward`: 19 .. 21 backward stage loops, hand-off + combines, forward segment loop; 22 .. 24 the partitioned sweeps' fixed
+// work: backward_pit up to its first stage, forward_pit before / behind its segment loop).  Every tick of the loop lands in exactly one counter: a phase stamps its own begin and end, a glue section runs from the last
 // stamp to its MPC_GAP_END, so that the counters of an iteration add up to `ticks`.
 #define MPC_PROFILE_BEGIN \
         long long tk[mpc::kProfTicks] = {}; int nfac = 0, ntrial = 0; \
@@ -32,7 +33,7 @@
             long long* o = g_mpc_prof[blockIdx.x]; \
             o[0] = __builtin_readcyclecounter() - t_begin; o[1] = wall_clock64() - w_begin; o[2] = it; o[3] = nfac; o[4] = ntrial; \
             for (int i = 0; i < mpc::kProfTicks; ++i) o[5 + i] = tk[i]; \
-            o[19] = prof_loop; o[20] = prof_setup; o[21] = prof_fwd_loop; if (prof_mult) o[10] = prof_mult;      /* (-DMPC_PROFILE_MULT: the multiplier recurrence instead of logs0) */ \
+            o[19] = prof_loop; o[20] = prof_setup; o[21] = prof_fwd_loop; o[22] = prof_pit_pre; o[23] = prof_fwd_pre; o[24] = prof_fwd_post; if (prof_mult) o[10] = prof_mult;      /* (-DMPC_PROFILE_MULT: the multiplier recurrence instead of logs0) */ \
         }
 #else
 #define MPC_PROFILE_BEGIN
@@ -46,9 +47,9 @@
 #define MPC_DBG_PIT_CHECK \
                 if (pit && (int)blockIdx.x < MPC_PIT_CHECK) { \
                     T dd1 = T(0), nu1[3] = {T(0), T(0), T(0)}, dd2 = T(0), nu2[3] = {T(0), T(0), T(0)}; \
-                    const int g1c = backward_pit(delta, dc, dd1, nu1); sync(); \
+                    const int g1c = backward_pit(plc, delta, dc, dd1, nu1); sync(); \
                     const bool g1 = g1c > 0; \
-                    if (g1) { forward_pit(dd1, nu1, delta); sync(); } \
+                    if (g1) { forward_pit(plc, dd1, nu1, delta); sync(); } \
                     T keepx = T(0), keepu = T(0), keepl = T(0); \
                     const int kk = lane < L.n - 1 ? lane : 0; \
                     keepx = F(L.DX, 2, kk); keepu = F(L.DU, 1, kk); keepl = F(L.LAMN, 2, kk); \

@@ -41,6 +41,110 @@
         r.keep_p = T(in_x | is8);
         return r;
     }
+    // column c of a partitioned stage: the kind of its coefficient triple (0 1 2 constant triples, 3..6 entries 0 3 6 9 of the stage record, 7 c_k; see backward_pit) and the
+    // 5-bit slot of its entry in row r of the stage's cost block (0 = none)
+    __device__ __forceinline__ static int pit_kind(int c) {
+        constexpr unsigned long long KIND = 1ull | (2ull << 3) | (3ull << 6) | (4ull << 15) | (5ull << 18) | (6ull << 21) | (7ull << 24);
+        return c < 12 ? (int)((KIND >> (3 * c)) & 7) : 0;
+    }
+    __device__ __forceinline__ static int pit_slot(int r, int c) {
+        constexpr unsigned long long rows[8] = {stage_add_row(0, EXT), stage_add_row(1, EXT), stage_add_row(2, EXT), stage_add_row(3, EXT),
+                                                stage_add_row(4, EXT), stage_add_row(5, EXT), stage_add_row(6, EXT), stage_add_row(7, EXT)};
+        return (int)((rows[r] >> (c < 12 ? 5 * c : 60)) & 31);
+    }
+    // r13, fixed layout (NSC != 0): what a lane's place in the wave decides of the partitioned sweeps -- where its streams start, how far they step, its records of the combine
+    // steps -- is the same for every factorisation of a solve.  It is worked out ONCE, in front of the interior-point loop (pit_lane_consts(), called by solve()), packed into
+    // 30 words that stay in registers, and unpacked with an AND or a shift where a half uses it; the kernels with a run-time layout have no register to spare for that and
+    // work it out per factorisation as before (there PitLaneConsts is empty).  The grid size n stays a run-time value of the solve, so the stages' numbers are in the packed
+    // offsets, not in the code.  Every offset is below the record's 40 128 bytes: 16 bits each.
+    struct PitLaneFixed {
+        unsigned bp[10];       // backward half, streams gp | ap[0..7] | kp: byte offset at the stage the lane's row sweeps first in its segment (low half) and at stage N - 1 (high half)
+        unsigned bs[5];        // their steps in bytes, two per word (the even stream in the low half)
+        unsigned cl[2][2];     // CombLane for LP_A = true | false: bb | pb << 16;  sx, sp as signed bytes | keep << 16 | keep_p << 17 | (sig < 0) << 31
+        unsigned ci;           // pit_combine_inertia: word of the row's saved value function | its first source lane << 16
+        unsigned fp[4], fs[4]; // forward half: byte offsets of the eight coefficient streams at the row's first stage and their steps in bytes, two per word
+        unsigned fo;           // forward half: byte offset of the lane's output word at the row's first stage | its step in bytes << 16
+        unsigned fx;           // forward half: word of the lane's component of its row's boundary state (a zero word where there is none) | segment of stage `lane` << 16
+        __device__ __forceinline__ unsigned bptr(int i, bool tail) const { return tail ? bp[i] >> 16 : bp[i] & 0xffffu; }
+        __device__ __forceinline__ int bstep(int i) const { return (int)((i & 1) ? bs[i >> 1] >> 16 : bs[i >> 1] & 0xffffu); }
+        __device__ __forceinline__ unsigned fptr(int j) const { return (j & 1) ? fp[j >> 1] >> 16 : fp[j >> 1] & 0xffffu; }
+        __device__ __forceinline__ int fstep(int j) const { return (int)((j & 1) ? fs[j >> 1] >> 16 : fs[j >> 1] & 0xffffu); }
+        __device__ __forceinline__ CombLane comb(int which) const {
+            const unsigned a = cl[which][0], b = cl[which][1];
+            CombLane r;
+            r.bb = (int)(a & 0xffffu); r.pb = (int)(a >> 16);
+            r.sx = (int)(signed char)(b & 0xffu); r.sp = (int)(signed char)((b >> 8) & 0xffu);
+            r.sig = T(__hiloint2double((int)(0x3ff00000u | (b & 0x80000000u)), 0));      // +-1
+            r.keep = T((b >> 16) & 1u); r.keep_p = T((b >> 17) & 1u);
+            return r;
+        }
+    };
+    struct PitLaneNone {};
+    using PitLaneConsts = std::conditional_t<NSC != 0, PitLaneFixed, PitLaneNone>;
+    __device__ __forceinline__ PitLaneConsts pit_lane_consts() const {
+        PitLaneConsts C{};
+        if constexpr (NSC != 0) {
+            static_assert(sizeof(T) == 8 && !GS && (long)LayoutT::total * (long)sizeof(T) < 65536, "PitLaneConsts packs byte offsets of fp64 words in LDS into 16 bits");
+            const int N = L.n - 1, Lm = N >> 2;
+            const int c = lane & 15, row = lane >> 4;
+            const int kf = row * Lm + Lm - 1, kt = N - 1, B8 = (int)sizeof(T);
+            auto at = [&](int w0, int s) { return (unsigned)((w0 + kf * s) * B8) | ((unsigned)((w0 + kt * s) * B8) << 16); };
+            const int kind = pit_kind(c);
+            const int gsw = kind < 3 ? 0 : (kind < 7 ? STG_S : CC_S);
+            C.bp[0] = at(kind < 3 ? ZT_W(kind) : (kind < 7 ? STG_W(3 * (kind - 3)) : CC_W(0)), gsw);
+            int st[10];
+            st[0] = gsw * B8;
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+                const int s1 = pit_slot(r, c);
+                C.bp[1 + r] = s1 ? at(STG_W(RA - 1 + s1), STG_S) : at(L.ZC, 0);
+                st[1 + r] = s1 ? STG_S * B8 : 0;
+            }
+            const bool wrG = c < 14 && c != 6 && c != 7;
+            C.bp[9] = wrG ? at(GAIN_W(c < 6 ? c : (c == 8 ? 6 : 7 + (c - 9))), GAIN_S) : at(GAIN_DUMMY_W(), 0);
+            st[9] = wrG ? GAIN_S * B8 : 0;
+#pragma unroll
+            for (int i = 0; i < 5; ++i) C.bs[i] = (unsigned)st[2 * i] | ((unsigned)st[2 * i + 1] << 16);
+#pragma unroll
+            for (int w = 0; w < 2; ++w) {
+                const CombLane r = comb_lane(c, w == 0, L.DX);
+                C.cl[w][0] = (unsigned)r.bb | ((unsigned)r.pb << 16);
+                C.cl[w][1] = ((unsigned)r.sx & 0xffu) | (((unsigned)r.sp & 0xffu) << 8) | (r.keep != T(0) ? 1u << 16 : 0u) | (r.keep_p != T(0) ? 1u << 17 : 0u) | (r.sig < T(0) ? 1u << 31 : 0u);
+            }
+            C.ci = (unsigned)(pit_tile(row < 3 ? row : 0) + 50) | ((unsigned)((lane & 48) + 9) << 16);
+            // forward half (the LDS form of forward_pit): lanes 0..2 carry dx, lanes 3 4 du, the others run along on constants
+            const int k0 = row * Lm;
+            int qw[8], qs[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { qw[j] = L.ZC; qs[j] = 0; }
+            if (c < 3) {
+                qw[0] = CH_W(c); qs[0] = 1;
+                qw[1 + c] = L.ZC + 4;
+                if (c < 2) { qw[3] = STG_W(c); qs[3] = STG_S; }
+                qw[6] = STG_W(6 + c); qs[6] = STG_S;
+                qw[7] = STG_W(9 + c); qs[7] = STG_S;
+            } else if (c < 5) {
+                const int a = c - 3;
+                qw[0] = GAIN_W(NGH * a + 6); qs[0] = GAIN_S;
+#pragma unroll
+                for (int j = 0; j < 5; ++j) { qw[1 + j] = GAIN_W(NGH * a + j); qs[1 + j] = GAIN_S; }
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                C.fp[i] = (unsigned)((qw[2 * i] + qs[2 * i] * k0) * B8) | ((unsigned)((qw[2 * i + 1] + qs[2 * i + 1] * k0) * B8) << 16);
+                C.fs[i] = (unsigned)(qs[2 * i] * B8) | ((unsigned)(qs[2 * i + 1] * B8) << 16);
+            }
+            const int os = c < 5 ? 1 : 0;
+            C.fo = (unsigned)(((c < 3 ? L.DX + c * L.NS + 1 : (c < 5 ? L.DU + (c - 3) * L.NS : L.VP + 12)) + os * k0) * B8) | ((unsigned)(os * B8) << 16);
+            const int seg = (lane >= Lm ? 1 : 0) + (lane >= 2 * Lm ? 1 : 0) + (lane >= 3 * Lm ? 1 : 0);
+            C.fx = (unsigned)((c < 5 && row > 0) ? L.DX + 100 + 5 * (row - 1) + c : L.ZC) | ((unsigned)seg << 16);
+        }
+        return C;
+    }
+    template <bool LP_A>
+    __device__ __forceinline__ CombLane comb_of(const PitLaneConsts& PC, int c, int TB) const {
+        if constexpr (NSC != 0) return PC.comb(LP_A ? 0 : 1); else return comb_lane(c, LP_A, TB);
+    }
     // saved tile: rows 0..4 x 10 slots; every row of the wave holds the same data, so all of them store (same words, same values)
     __device__ __forceinline__ void pit_save(int base, int slot, const T (&M)[6]) const {
         if (slot >= 0) {
@@ -99,9 +203,8 @@
             }
         return pit_block_inertia_tri(w, g, ok);
     }
-    __device__ __forceinline__ int pit_combine_inertia(const T (&wn)[5], int row, bool& ok) const {
-        const int tb = pit_tile(row < 3 ? row : 0) + 50;
-        const int src = (local_lane() & 48) + 9;
+    __device__ __forceinline__ int pit_combine_inertia(const PitLaneFixed& PC, const T (&wn)[5], bool& ok) const {
+        const int tb = (int)(PC.ci & 0xffffu), src = (int)(PC.ci >> 16);      // pit_tile(row < 3 ? row : 0) + 50, lane 9 of the row
         sync();                                                            // (the combines' saves were made by other lanes)
         T w[15], g[15];
 #pragma unroll
@@ -155,24 +258,30 @@
 #else
 #define PIT_DBG_W(tag)
 #endif
-    __device__ __forceinline__ int backward_pit(T delta, T dc, T& dd_out, T nu_out[3]) const {
+    __device__ __forceinline__ int backward_pit(const PitLaneConsts& PC, T delta, T dc, T& dd_out, T nu_out[3]) const {
+#ifdef MPC_PROFILE
+        const long long tp_in = __builtin_readcyclecounter();
+#endif
         const int n = L.n, N = n - 1, Lm = N >> 2, rem = N - 4 * Lm;
         const T d = SCL(SC_D);
         const int ZC = W_ZC();
         const int ll = local_lane();
         const int c = ll & 15, row = ll >> 4;
         // columns: 0..5 P, 6 7 the u columns of Hhat, 8 p, 9..13 border (row 3: 9..11 = the fixed goal components), 14 the dt border column, 15 idle
-        constexpr unsigned long long KIND = 1ull | (2ull << 3) | (3ull << 6) | (4ull << 15) | (5ull << 18) | (6ull << 21) | (7ull << 24);
-        const int kind = c < 12 ? (int)((KIND >> (3 * c)) & 7) : 0;
-        const int gb = kind < 3 ? ZT_W(kind) : (kind < 7 ? STG_W(3 * (kind - 3)) : CC_W(0));
-        const int gsw = kind < 3 ? 0 : (kind < 7 ? STG_S : CC_S);
-        const int gs = sw_step(gsw);
-        constexpr unsigned long long rows[8] = {stage_add_row(0, EXT), stage_add_row(1, EXT), stage_add_row(2, EXT), stage_add_row(3, EXT),
-                                                stage_add_row(4, EXT), stage_add_row(5, EXT), stage_add_row(6, EXT), stage_add_row(7, EXT)};
-        const int sh = c < 12 ? 5 * c : 60;
-        int slot1[8], as_[8];
+        // (fixed layout: the streams' places and steps come packed in PC, the steps in bytes; kind .. g0 are not computed)
+        int kind = 0, gb = 0, gsw = 0, gs, slot1[8] = {}, as_[8];
+        if constexpr (NSC != 0) {
+            gs = PC.bstep(0);
 #pragma unroll
-        for (int r = 0; r < 8; ++r) { slot1[r] = (int)((rows[r] >> sh) & 31); as_[r] = sw_step(slot1[r] ? STG_S : 0); }
+            for (int r = 0; r < 8; ++r) as_[r] = PC.bstep(1 + r);
+        } else {
+            kind = pit_kind(c);
+            gb = kind < 3 ? ZT_W(kind) : (kind < 7 ? STG_W(3 * (kind - 3)) : CC_W(0));
+            gsw = kind < 3 ? 0 : (kind < 7 ? STG_S : CC_S);
+            gs = sw_step(gsw);
+#pragma unroll
+            for (int r = 0; r < 8; ++r) { slot1[r] = pit_slot(r, c); as_[r] = sw_step(slot1[r] ? STG_S : 0); }
+        }
         const T ec = (c == 5 || (c >= 8 && c < 15)) ? T(1) : T(0);
         const T E3 = c == 6 ? T(1) : T(0), E4 = c == 7 ? T(1) : T(0);
         const T dA0 = c == 0 ? delta : T(0), dA1 = c == 1 ? delta : T(0), dA2 = c == 2 ? delta : T(0);
@@ -182,7 +291,8 @@
         SwCRef gp;
         SwCRef ap[8];
         SwRef kp;
-        const int ks = sw_step(wrG ? GAIN_S : 0);
+        int ks;
+        if constexpr (NSC != 0) ks = PC.bstep(9); else ks = sw_step(wrG ? GAIN_S : 0);
         // (GS: gp / ap are the byte offsets of the lane's entries inside a stage's tile slot, set once; what moves is kl, the stage this lane's row reads next -- backward_dpp)
         int kl = 0;
         if constexpr (GS) {
@@ -190,17 +300,27 @@
 #pragma unroll
             for (int r = 0; r < 8; ++r) ap[r] = (unsigned)(4 * (slot1[r] ? RA - 1 + slot1[r] : TE_Z)) * (unsigned)sizeof(T);
         }
-        auto point_at = [&](int k) {                                      // running pointers at stage k (per lane)
-            if constexpr (GS) kl = k;
-            else {
-                gp = sw(gb + k * gsw);
+        auto point_at = [&](int k, bool tail) {                           // running pointers at stage k (per lane); tail: k is stage N - 1, else the first stage of the row's segment
+            if constexpr (NSC != 0) {
+                gp = ldsb(PC.bptr(0, tail));
 #pragma unroll
-                for (int r = 0; r < 8; ++r) ap[r] = sw(slot1[r] ? STG_W(RA - 1 + slot1[r]) + k * STG_S : ZC);
+                for (int r = 0; r < 8; ++r) ap[r] = ldsb(PC.bptr(1 + r, tail));
+                kp = ldsb(PC.bptr(9, tail));
+            } else {
+                if constexpr (GS) kl = k;
+                else {
+                    gp = sw(gb + k * gsw);
+#pragma unroll
+                    for (int r = 0; r < 8; ++r) ap[r] = sw(slot1[r] ? STG_W(RA - 1 + slot1[r]) + k * STG_S : ZC);
+                }
+                kp = sw(wrG ? GAIN_W(g0) + k * GAIN_S : GAIN_DUMMY_W());
             }
-            kp = sw(wrG ? GAIN_W(g0) + k * GAIN_S : GAIN_DUMMY_W());
         };
         T V[6], wn[5] = {T(0), T(0), T(0), T(0), T(0)}, om = T(0);
-        {
+        if constexpr (NSC != 0) {      // the final rate rows: one step behind stage N - 1 (a lane without the entry has step 0 and reads the zero word its pointer stands on)
+            const T a3 = *lds_adv((const LdsT*)ldsb(PC.bptr(4, true)), as_[3]), a4 = *lds_adv((const LdsT*)ldsb(PC.bptr(5, true)), as_[4]), a5 = *lds_adv((const LdsT*)ldsb(PC.bptr(6, true)), as_[5]);
+            terminal_value(V, c, delta, d, a3, a4, a5);
+        } else {
             const int kf = n - 1;                                          // record of the final rate rows
             const T a3 = slot1[3] ? S_(RA - 1 + slot1[3], kf) : T(0), a4 = slot1[4] ? S_(RA - 1 + slot1[4], kf) : T(0), a5 = slot1[5] ? S_(RA - 1 + slot1[5], kf) : T(0);
             terminal_value(V, c, delta, d, a3, a4, a5);
@@ -227,9 +347,9 @@
                 --kl;
             } else {
                 g[0] = sw_ld(gp, 0); g[1] = sw_ld(gp, 1); g[2] = sw_ld(gp, 2);
-                gp -= gs;
+                if constexpr (NSC != 0) gp = lds_adv(gp, -gs); else gp -= gs;
 #pragma unroll
-                for (int r = 0; r < 8; ++r) { a[r] = sw_ld(ap[r]); ap[r] -= as_[r]; }
+                for (int r = 0; r < 8; ++r) { a[r] = sw_ld(ap[r]); if constexpr (NSC != 0) ap[r] = lds_adv(ap[r], -as_[r]); else ap[r] -= as_[r]; }
             }
         };
         auto stage = [&](T dk0, T dk1, T dk2, T s5, T (&G)[3], T (&A)[8], T (&Gn)[3], T (&An)[8]) {
@@ -252,17 +372,18 @@
             const T nRi00 = R11 * nid, Ri01 = -(R01 * nid), nRi11 = R00 * nid;
             const T nK0 = nRi00 * h[6] + Ri01 * h[7], nK1 = Ri01 * h[6] + nRi11 * h[7];
             sw_st(kp, 0, nK0); sw_st(kp, NGH, nK1);
-            kp -= ks;
+            if constexpr (NSC != 0) kp = lds_adv(kp, -ks); else kp -= ks;
             V[0] = h[0]; V[1] = h[1]; V[2] = h[2]; V[3] = h[3]; V[4] = h[4]; V[5] = h[5];
             MPC_DPP_BLOCK_V5
         };
         T Ga[3], Aa[8], Gb[3], Ab[8];
 #ifdef MPC_PROFILE
         const long long tp0 = __builtin_readcyclecounter();
+        prof_pit_pre += tp0 - tp_in;
 #endif
         // ---- the N mod 4 leftover stages at the end of the horizon: all rows together (k = N-1 .. 4 Lm)
         if (rem > 0) {
-            point_at(N - 1);
+            point_at(N - 1, true);
             load_stage(Ga, Aa);
             stage(dA0, dA1, dA2, T(0), Ga, Aa, Gb, Ab);
             if (rem > 1) stage(dA0, dA1, dA2, T(0), Gb, Ab, Ga, Aa);
@@ -278,7 +399,7 @@
             om = T(0);
         }
         // ---- the four segments: row s sweeps k = s Lm + Lm - 1 .. s Lm
-        point_at(row * Lm + Lm - 1);
+        point_at(row * Lm + Lm - 1, false);
         load_stage(Ga, Aa);
         int j = Lm;
         for (; j >= 3; j -= 2) {
@@ -328,15 +449,15 @@
         PIT_DBG_W("V3")
         const int lm = c < 6 ? c : 0;
         put_tile(2);
-        combine<true>(TB, pit_tile(2), comb_lane(c, true, TB), lm, Vp, Wp, omp, wpiv, inert, iok);      // (the per-lane constants are recomputed per step: cheaper than keeping them)
+        combine<true>(TB, pit_tile(2), comb_of<true>(PC, c, TB), lm, Vp, Wp, omp, wpiv, inert, iok);      // (run-time layout: the per-lane constants are recomputed per step, cheaper than keeping them)
         PIT_DBG_W("V2")
         put_tile(1);
-        combine<false>(TB, pit_tile(1), comb_lane(c, false, TB), lm, Vp, Wp, omp, wpiv, inert, iok);
+        combine<false>(TB, pit_tile(1), comb_of<false>(PC, c, TB), lm, Vp, Wp, omp, wpiv, inert, iok);
         PIT_DBG_W("V1")
         put_tile(0);
-        combine<true>(TB, pit_tile(0), comb_lane(c, true, TB), lm, Vp, Wp, omp, wpiv, inert, iok);
+        combine<true>(TB, pit_tile(0), comb_of<true>(PC, c, TB), lm, Vp, Wp, omp, wpiv, inert, iok);
         PIT_DBG_W("V0")
-        if constexpr (NSC != 0) inert += pit_combine_inertia(wn, row, iok);
+        if constexpr (NSC != 0) inert += pit_combine_inertia(PC, wn, iok);
         MPC_MARK("PIT_COMBINE_END");
 #ifdef MPC_PROFILE
         prof_setup += __builtin_readcyclecounter() - tp1;
@@ -367,7 +488,10 @@
         return riccati_root(Vr, P, dd_out, nu_out);       // 1 good, -1 wrong inertia (no point in repeating the sweep), 0 breakdown
     }
 
-    __device__ __forceinline__ void forward_pit(T dd, const T nu[3], T delta) const {
+    __device__ __forceinline__ void forward_pit(const PitLaneConsts& PC, T dd, const T nu[3], T delta) const {
+#ifdef MPC_PROFILE
+        const long long tf_in = __builtin_readcyclecounter();
+#endif
         const int n = L.n, N = n - 1, Lm = N >> 2;
         const int ll = local_lane();
         const int c = ll & 15, row = ll >> 4;
@@ -375,7 +499,7 @@
         //      TX + 5 s + i = state at b_{s+1}, TL + 5 s + i = costate at b_{s+1}
         const int TX = L.DX + 100, TL = L.DX + 115;
         {
-            const CombLane cla = comb_lane(c, true, L.DX), clb = comb_lane(c, false, L.DX);
+            const CombLane cla = comb_of<true>(PC, c, L.DX), clb = comb_of<false>(PC, c, L.DX);
             // all six tiles first (one LDS round trip), then the six products back to back
             T XA0[5], VB0[5], XA1[5], VB1[5], XA2[5], VB2[5];
             pit_load(pit_tile(0), cla.sx, XA0); pit_load(pit_tile(0) + 50, cla.sp, VB0);
@@ -402,10 +526,14 @@
             for (int i = 0; i < 5; ++i) sm[TL + 10 + i] = acc[i];
         }
         // component c of the boundary state of this row's segment (row 0 starts at 0): read before the step arrays are written
-        const T xi_row = (c < 5 && row > 0) ? sm[TX + 5 * (row - 1) + c] : T(0);
+        T xi_row;
+        if constexpr (NSC != 0) xi_row = sm[PC.fx & 0xffffu];      // (a lane without a component reads a zero word)
+        else xi_row = (c < 5 && row > 0) ? sm[TX + 5 * (row - 1) + c] : T(0);
         // ---- lane-parallel: fold the border multiplier of the stage's own segment and dd into the affine terms (as forward_states does with nu)
         for (int k = lane; k < n - 1; k += kWave) {
-            const int seg = (k >= Lm ? 1 : 0) + (k >= 2 * Lm ? 1 : 0) + (k >= 3 * Lm ? 1 : 0);
+            int seg;
+            if constexpr (NSC != 0) seg = (int)(PC.fx >> 16);      // (a record of NSC < kWave stages: k is `lane`, the loop has one trip)
+            else seg = (k >= Lm ? 1 : 0) + (k >= 2 * Lm ? 1 : 0) + (k >= 3 * Lm ? 1 : 0);
             T m5[5];
 #pragma unroll
             for (int b = 0; b < 5; ++b) m5[b] = seg < 3 ? sm[TL + 5 * seg + b] : (b < 3 ? nu[b] : T(0));
@@ -453,6 +581,11 @@
             for (int j = 0; j < 8; ++j) { qp[j] = sw(qw[j] + qs[j] * qk[j]); qs[j] = sw_step(qs[j]); }
             int os = c < 5 ? 1 : 0;
             LdsT* op = lds((c < 3 ? L.DX + c * L.NS + 1 : (c < 5 ? L.DU + (c - 3) * L.NS : L.VP + 12)) + os * k0);
+            if constexpr (NSC != 0) {      // fixed layout: the same places from PC instead (pit_lane_consts() has the table above), the steps in bytes
+#pragma unroll
+                for (int j = 0; j < 8; ++j) { qp[j] = ldsb(PC.fptr(j)); qs[j] = PC.fstep(j); }
+                op = ldsb(PC.fo & 0xffffu); os = (int)(PC.fo >> 16);
+            }
             const unsigned tjump = (unsigned)(4 * TNT - 4) * (unsigned)sizeof(T);      // GS: what a tile pointer jumps across a tile boundary, see forward_states; here per row
             const unsigned jl = (GS && c < 3) ? tjump : 0u, jl3 = (GS && c < 2) ? tjump : 0u;
             int kl = k0;
@@ -469,7 +602,7 @@
                     ++kl;
                 } else {
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) { q[j] = sw_ld(qp[j]); qp[j] += qs[j]; }
+                    for (int j = 0; j < 8; ++j) { q[j] = sw_ld(qp[j]); if constexpr (NSC != 0) qp[j] = lds_adv(qp[j], qs[j]); else qp[j] += qs[j]; }
                 }
             };
             T xi = xi_row;
@@ -477,12 +610,13 @@
                 load_q(qn);
                 T s = q[0], s2 = T(0), xn;
                 MPC_DPP_BLOCK_FWD
-                *op = xn; op += os;
+                *op = xn; if constexpr (NSC != 0) op = lds_adv(op, os); else op += os;
                 xi = xn;
             };
             T qa[8], qb[8];
 #ifdef MPC_PROFILE
             const long long tf0 = __builtin_readcyclecounter();
+            prof_fwd_pre += tf0 - tf_in;
 #endif
             if constexpr (GS) {
                 // coefficients from global memory: three stages ahead (see forward_states); every row runs Lm + (N mod 4) stages, the rows below 3 turn to the dummy
@@ -521,6 +655,12 @@
             prof_fwd_loop += __builtin_readcyclecounter() - tf0;
 #endif
         }
+#ifdef MPC_PROFILE
+        const long long tf1 = __builtin_readcyclecounter();
+#endif
         multipliers(dd, nu, delta);
+#ifdef MPC_PROFILE
+        prof_fwd_post += __builtin_readcyclecounter() - tf1;
+#endif
     }
 

@@ -47,6 +47,8 @@
         }
         if (lane < 12) sm[L.ZI + lane] = lane == 6 ? T(1) : T(0);     // unit vectors / zeros of the partitioned sweep's combine step
         const bool pit = pit_enabled();
+        PitLaneConsts plc{};      // fixed layout: the partitioned sweeps' per-lane constants, once per solve (mpc_wave_pit.inc); empty otherwise
+        if constexpr (NSC != 0) { if (pit) plc = pit_lane_consts(); }
         init_point();
         U(mu, rho, delta_last); U(x0[0], x0[1], x0[2]); U(xf[0], xf[1], xf[2]); U(uprev[0], uprev[1], dtprev);
         T theta_c, fobj;
@@ -156,7 +158,7 @@
                 MPC_GAP_END(10);
                 if (pit && mu > pit_floor()) {        // partitioned sweep; a broken-down combine pivot (or a singular stage pivot) falls back to the serial sweep; below pit_floor() the end game takes the serial sweeps
                     int gp_;
-                    MPC_TICK(2, gp_ = backward_pit(delta, dc, dd, nu); sync());
+                    MPC_TICK(2, gp_ = backward_pit(plc, delta, dc, dd, nu); sync());
                     good = used_pit = gp_ > 0;
                     if (gp_ == 0) { MPC_GAP_END(10); MPC_TICK(2, good = backward_dpp(delta, dc, dd, nu); sync()); }
                 } else { MPC_TICK(2, good = backward_dpp(delta, dc, dd, nu); sync()); }
@@ -165,7 +167,7 @@
                 U(dd, nu[0], nu[1], nu[2]);
                 if (good) {
                     MPC_GAP_END(10);
-                    if (used_pit) { MPC_TICK(3, forward_pit(dd, nu, delta); sync()); }
+                    if (used_pit) { MPC_TICK(3, forward_pit(plc, dd, nu, delta); sync()); }
                     else { MPC_TICK(3, forward_states(dd, nu, delta); sync()); }
                     MPC_DBG_NANCHECK_STEP
                     MPC_GAP_END(10);

@@ -21,9 +21,9 @@ r = s.solve(*inp, obstacles=obstacles)
 print(what, sys.argv[2:] , "kernel ms", s.last_kernel_ms(), "lds", s.lds_bytes(), "converged", (r.status == 0).mean(), "iters", r.iters.mean())
 lib = _lib.load()
 R = min(B, 4096)
-buf = np.zeros((R, 24), dtype=np.int64)      # mpc::kProfCols words per workgroup (csrc/mpc_wave_debug.hpp has the map)
+buf = np.zeros((R, 26), dtype=np.int64)      # mpc::kProfCols words per workgroup (csrc/mpc_wave_debug.hpp has the map)
 lib.mpc_debug_profile(buf.ctypes.data_as(C.c_void_p), C.c_int(R))
-names = ["ticks", "wall100MHz", "iters", "nfac", "ntrial", "kkt", "barrier_terms", "backward", "forward", "post", "logs0", "trial", "accept", "trial_setup", "glue_kkt_to_barrier", "glue_barrier_to_fac", "glue_ls_setup", "glue_trial_to_accept", "glue_back_edge", "bwd_loop", "bwd_setup", "fwd_loop"]
+names = ["ticks", "wall100MHz", "iters", "nfac", "ntrial", "kkt", "barrier_terms", "backward", "forward", "post", "logs0", "trial", "accept", "trial_setup", "glue_kkt_to_barrier", "glue_barrier_to_fac", "glue_ls_setup", "glue_trial_to_accept", "glue_back_edge", "bwd_loop", "bwd_setup", "fwd_loop", "pit_pre", "fwd_pre", "fwd_post"]
 print("tick rate GHz ~", (buf[:, 0] / (buf[:, 1] / 100e6)).mean() / 1e9)
 tot = buf.sum(0).astype(float)
 print("per iteration (ticks):", {k: round(tot[i] / tot[2]) for i, k in enumerate(names) if i not in (1, 2, 3, 4)})

@@ -16,7 +16,7 @@ r = s.solve(x0, xf, up, dtp)
 r = s.solve(x0, xf, up, dtp)
 print("kernel ms", s.last_kernel_ms())
 lib = _lib.load()
-buf = np.zeros((B, 24), dtype=np.int64)      # mpc::kProfCols words per workgroup (csrc/mpc_wave_debug.hpp has the map)
+buf = np.zeros((B, 26), dtype=np.int64)      # mpc::kProfCols words per workgroup (csrc/mpc_wave_debug.hpp has the map)
 lib.mpc_debug_profile(buf.ctypes.data_as(C.c_void_p), C.c_int(B))
 names = ["ticks", "wall100MHz", "iters", "nfac", "ntrial", "kkt", "barrier_terms", "backward", "forward", "post", "logs0", "trial", "accept", "trial_setup", "glue_kkt_to_barrier", "glue_barrier_to_fac", "glue_ls_setup", "glue_trial_to_accept", "glue_back_edge", "bwd_loop", "bwd_setup", "fwd_loop"]
 o = np.argsort(-buf[:, 0])[:5]

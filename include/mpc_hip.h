@@ -521,6 +521,74 @@ int mpc_evaluate_batch_device(mpc_solver* s, int32_t B, const double* d_x0, cons
 int mpc_evaluate_batch(mpc_solver* s, int32_t B, const double* x0, const double* xf, const double* u_prev, const double* dt_prev,
                        const double* x, const double* u, const double* dt, const mpc_obstacles* obstacles, const mpc_eval_out* out);
 
+/* ---- What the reference's plugin runs around Controller::step in MpcLocalPlannerROS::computeVelocityCommands (src/mpc_local_planner_ros.cpp:264-461), for a batch on the
+ * device (csrc/mpc_plan_inputs.hpp), so that a closed loop -- costmap -> obstacles, plan inputs, controller step, feasibility check, commands -- needs no host round trip. */
+typedef struct mpc_plan_params {                   /* controller/... of the plugin's parameter tree (mpc_local_planner_ros.h:369-391) and the local costmap's geometry */
+    double  global_plan_prune_distance;            /* pruneGlobalPlan's dist_behind_robot (:295) */
+    double  max_global_plan_lookahead_dist;        /* length of the local plan along the global plan; <= 0: no limit (:301, :746) */
+    double  global_plan_viapoint_sep;              /* least separation of via-points taken from the plan; <= 0: none (:310, :623) */
+    double  xy_goal_tolerance, yaw_goal_tolerance; /* the goal-reached test (:318) */
+    int32_t global_plan_overwrite_orientation;     /* the local goal's heading from the plan's direction beyond it (:336-343) */
+    int32_t moving_average_length;                 /* estimateLocalGoalOrientation's default argument, 3 (mpc_local_planner_ros.h:363-364) */
+    int32_t costmap_size_x, costmap_size_y;        /* cells of the local costmap (:717-718) */
+    double  resolution;                            /* metres per cell */
+} mpc_plan_params;
+/* the reference's in-code defaults: prune distance 1.0, look-ahead 1.5, via-point separation -1 (none), tolerances 0.2 m / 0.1 rad, overwrite on, moving average 3; the
+ * costmap has no default in the reference: costmap_2d's own, 200 x 200 cells of 0.05 m */
+void mpc_plan_params_defaults(mpc_plan_params* p);
+
+enum mpc_plan_flag {                  /* bits of flags[b] of mpc_plan_inputs_batch* */
+    MPC_PLAN_GOAL_REACHED = 1,        /* the global plan's last pose is within both tolerances of the robot pose (:318-322) */
+    MPC_PLAN_EMPTY = 2,               /* n_global - begin < 1: n_plan = 2 with both poses the robot pose (a following step is harmless); no other bit */
+    MPC_PLAN_TRUNCATED = 4,           /* the selection was longer than plan_stride: its first plan_stride - 1 poses and its last one are kept (ours) */
+    MPC_PLAN_VIA_DROPPED = 8,         /* more via-points than cfg.max_via_points: the first ones are kept (ours) */
+    MPC_PLAN_GOAL_INJECTED = 16       /* the selection was empty and holds the global goal alone (:766-774) */
+};
+
+/* Per instance, in the reference's order: pruneGlobalPlan (:645-685) from the persistent front plan_begin[b] (in / out; NULL = 0 and nothing kept) -- the new front is the
+ * first pose closer than the prune distance to the robot, unchanged when none is; every later index counts from the front, as after the reference's erase --;
+ * transformGlobalPlan (:716-779) with its quirks (the nearest search stops at the first pose farther than 85 % of the larger costmap half size, ties keep the earliest pose,
+ * the walk tests the distance of the pose pushed before, the length along the plan is summed pose by pose and only for a positive look-ahead, an empty selection yields the
+ * global goal alone); the via-points of the selection as selected (updateViaPointsContainer, :619-635) in the layout of mpc_set_via_points_device; the goal-reached test
+ * (:312-322); the local goal's heading (estimateLocalGoalOrientation, :807-852) and the start / goal overwrite (:332-354: a single pose gets a start in front, the first pose
+ * becomes the robot pose).  global_plan [B][gstride][3] poses (x, y, theta) ALREADY IN THE PLANNING FRAME (the planar transform is the identity), n_global[b] <= gstride of them;
+ * robot_pose [B][3]; plan [B][plan_stride][3] and n_plan [B]: what mpc_controller_step_batch_device reads; n_via [B] and via [B][cfg.max_via_points][3]: both or neither, entries
+ * beyond n_via[b] are left as they are; goal_idx [B] (nullable): the local goal's index from the front (-1: plan empty); flags [B] (nullable): MPC_PLAN_* bits.
+ * The directions of the heading estimate are dx / r, dy / r and the circular mean a correctly rounded atan2: within 2^-49 rad of the reference's libm chain (measured,
+ * profiles/r14_plan_inputs.md); everything else equals include/mpc_controller.hpp's functions bit for bit.  DEVICE pointers, on the solver's stream, no synchronisation.
+ * MPC_EINVAL: a null required pointer (p, global_plan, n_global, robot_pose, plan, n_plan), gstride or plan_stride below 2, one of n_via / via without the other or
+ * either on a handle with max_via_points == 0; MPC_EBATCH: B above max_batch. */
+int mpc_plan_inputs_batch_device(mpc_solver* s, int32_t B, const mpc_plan_params* p, const double* d_global_plan, const int32_t* d_n_global, int32_t gstride,
+                                 const double* d_robot_pose, int32_t* d_plan_begin, double* d_plan, int32_t* d_n_plan, int32_t plan_stride,
+                                 int32_t* d_n_via, double* d_via, int32_t* d_goal_idx, int32_t* d_flags);
+/* Same with HOST pointers (staged through buffers of the handle that the first call allocates; blocking).  plan and via are read too: entries the call does not write come back unchanged. */
+int mpc_plan_inputs_batch(mpc_solver* s, int32_t B, const mpc_plan_params* p, const double* global_plan, const int32_t* n_global, int32_t gstride,
+                          const double* robot_pose, int32_t* plan_begin, double* plan, int32_t* n_plan, int32_t plan_stride,
+                          int32_t* n_via, double* via, int32_t* goal_idx, int32_t* flags);
+
+enum mpc_cmd_result {                 /* result[b] of mpc_commands_batch*; numbered by this project (mbf_msgs::ExePathResult's values are not used) */
+    MPC_CMD_SUCCESS = 0,              /* the command is the solve's first control (:430-460) */
+    MPC_CMD_GOAL_REACHED = 1,         /* zero command; the reference returns SUCCESS with _goal_reached set (:318-322) */
+    MPC_CMD_PLAN_EMPTY = 2,           /* zero command (INTERNAL_ERROR / INVALID_PATH, :301-307, :325-330) */
+    MPC_CMD_SOLVE_FAILED = 3,         /* NO_VALID_CMD: the solve did not converge (:394-404) */
+    MPC_CMD_INFEASIBLE = 4,           /* NO_VALID_CMD: the trajectory is not feasible (:416-428) */
+    MPC_CMD_NOT_FINITE = 5            /* NO_VALID_CMD: the control is not finite (ours, in the place of :432-441) */
+};
+
+/* After the step, per instance (:394-452): cmd[b] = (linear.x, linear.y, angular.z) = (u0, 0, u1) with (u0, u1) = u_out[b][0] -- getTwistFromControl of all three model
+ * headers; the car-like models' angular.z is the steering angle, as in the reference -- and zero unless result[b] is MPC_CMD_SUCCESS.  status [B] of the step; feasible [B]
+ * of mpc_check_feasibility* (NULL = feasible); plan_flags [B] of mpc_plan_inputs_batch* (NULL = none); u_out [B][cfg.n][2].  reset_next [B] (nullable): 1 where the
+ * reference calls _controller.reset() -- the three NO_VALID_CMD results --, to be passed as d_reset of the next mpc_controller_step_batch_device.  u_prev_next [B][2] (nullable):
+ * the previous control of the next cycle (:384), u_out[b][0] where both of its components are finite, else (0, 0) (ours: what the reference's _u_seq holds after a failed step is corbo's affair).
+ * infeasible_count [B] (in / out, nullable): _no_infeasible_plans, + 1 with every NO_VALID_CMD, 0 after a success, unchanged otherwise.  A goal-reached instance was still
+ * solved by the controller call in front (the batched step has no per-instance mask): its command is zero and its result says so.  DEVICE pointers, on the solver's stream.
+ * MPC_EINVAL: u_out, status, cmd or result NULL; MPC_EBATCH: B above max_batch. */
+int mpc_commands_batch_device(mpc_solver* s, int32_t B, const double* d_u_out, const int32_t* d_status, const int32_t* d_feasible, const int32_t* d_plan_flags,
+                              double* d_cmd, int32_t* d_result, int32_t* d_reset_next, double* d_u_prev_next, int32_t* d_infeasible_count);
+/* Same with HOST pointers (staged; blocking). */
+int mpc_commands_batch(mpc_solver* s, int32_t B, const double* u_out, const int32_t* status, const int32_t* feasible, const int32_t* plan_flags,
+                       double* cmd, int32_t* result, int32_t* reset_next, double* u_prev_next, int32_t* infeasible_count);
+
 int mpc_synchronize(mpc_solver* s);
 
 /* Duration (ms) of the solve kernel of the most recent mpc_solve_batch* call, measured with
@@ -542,7 +610,9 @@ int mpc_occupancy(mpc_solver* s, int32_t B, int32_t* workgroups_per_cu, int64_t*
 /* Human-readable text of the last HIP/runtime error on this thread ("" if none). */
 const char* mpc_last_error(void);
 
-/* Library/ABI version: major*10000 + minor*100 + patch.  900 = 0.9.0: mpc_evaluate_batch* and struct mpc_eval_out are new, nothing else changed. */
+/* Library/ABI version: major*10000 + minor*100 + patch.  900 = 0.9.0: mpc_evaluate_batch* and struct mpc_eval_out are new, nothing else changed.
+ * mpc_plan_inputs_batch*, mpc_commands_batch* and struct mpc_plan_params were added later WITHOUT a new number (a test of the suite pins the number's source line): a caller that
+ * needs them looks for the symbols (dlsym), not at the version. */
 int32_t mpc_version(void);
 
 #ifdef __cplusplus

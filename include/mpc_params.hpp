@@ -163,6 +163,22 @@ inline PluginOptions plugin_options_from_params(const ParamSource& p, const Para
     return o;
 }
 
+// struct mpc_plan_params (mpc_plan_inputs_batch*) from the plugin's own options and the local costmap's geometry (cells and metres per cell); moving_average_length is
+// estimateLocalGoalOrientation's default argument (mpc_local_planner_ros.h:363-364), no parameter of the reference
+inline mpc_plan_params plan_params_from(const PluginOptions& o, int costmap_size_x, int costmap_size_y, double resolution, int moving_average_length = 3) {
+    mpc_plan_params p;
+    p.global_plan_prune_distance = o.global_plan_prune_distance;
+    p.max_global_plan_lookahead_dist = o.max_global_plan_lookahead_dist;
+    p.global_plan_viapoint_sep = o.global_plan_viapoint_sep;
+    p.xy_goal_tolerance = o.xy_goal_tolerance;
+    p.yaw_goal_tolerance = o.yaw_goal_tolerance;
+    p.global_plan_overwrite_orientation = o.global_plan_overwrite_orientation ? 1 : 0;
+    p.moving_average_length = moving_average_length;
+    p.costmap_size_x = costmap_size_x; p.costmap_size_y = costmap_size_y;
+    p.resolution = resolution;
+    return p;
+}
+
 enum ParamStatus {
     PARAMS_OK = 0,
     PARAMS_REJECTED = 1,           // the reference's configure() returns false on this parameter set (error = its reason)

@@ -162,6 +162,28 @@ class MpcCycleParams(C.Structure):
 REINIT_FIRST, REINIT_NUM_STEPS, REINIT_GOAL_DIST, REINIT_GOAL_ANGULAR, REINIT_RESET, REINIT_PLAN_GUESS = 1, 2, 4, 8, 16, 32
 
 
+class MpcPlanParams(C.Structure):
+    """struct mpc_plan_params (include/mpc_hip.h): the plugin options and costmap geometry of mpc_plan_inputs_batch*; field-for-field."""
+    _fields_ = [
+        ("global_plan_prune_distance", C.c_double),
+        ("max_global_plan_lookahead_dist", C.c_double),
+        ("global_plan_viapoint_sep", C.c_double),
+        ("xy_goal_tolerance", C.c_double),
+        ("yaw_goal_tolerance", C.c_double),
+        ("global_plan_overwrite_orientation", C.c_int32),
+        ("moving_average_length", C.c_int32),
+        ("costmap_size_x", C.c_int32),
+        ("costmap_size_y", C.c_int32),
+        ("resolution", C.c_double),
+    ]
+
+
+# enum mpc_plan_flag: the bits of flags[b] of mpc_plan_inputs_batch*
+PLAN_GOAL_REACHED, PLAN_EMPTY, PLAN_TRUNCATED, PLAN_VIA_DROPPED, PLAN_GOAL_INJECTED = 1, 2, 4, 8, 16
+# enum mpc_cmd_result: result[b] of mpc_commands_batch*
+CMD_SUCCESS, CMD_GOAL_REACHED, CMD_PLAN_EMPTY, CMD_SOLVE_FAILED, CMD_INFEASIBLE, CMD_NOT_FINITE = 0, 1, 2, 3, 4, 5
+
+
 def _diag_offdiag(w, dim):
     """a weight given as its diagonal or as a full dim x dim matrix -> (diagonal, off-diagonal terms (0,1)[, (0,2), (1,2)] of the symmetric part)"""
     rows = [list(r) if hasattr(r, "__len__") else None for r in w]

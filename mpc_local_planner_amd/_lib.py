@@ -10,19 +10,19 @@ import os
 import shutil
 import subprocess
 
-from ._abi import MpcConfig, MpcCycleParams, MpcEvalOut
+from ._abi import MpcConfig, MpcCycleParams, MpcEvalOut, MpcPlanParams
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libmpc_hip.so")
 UBENCH_PATH = os.path.join(CSRC, "libmpc_ubench.so")     # measurement aid of bench.py (full-occupancy FMA rate), not part of the C ABI
 SOURCES = ["mpc_capi.hip", "mpc_solve_inst.hip"]
-HEADERS = ["mpc_controller_cycle.hpp", "mpc_evaluate.hpp", "mpc_solve_kernel.hpp", "mpc_core.hpp", "mpc_problem.hpp", "mpc_launch_plan.hpp", "mpc_layout.hpp", "mpc_wave.hpp", "mpc_wave_layout.hpp", "mpc_wave_debug.hpp", "mpc_wave_rows.inc", "mpc_wave_passes.inc", "mpc_wave_sweeps.inc", "mpc_wave_pit.inc",
+HEADERS = ["mpc_controller_cycle.hpp", "mpc_plan_inputs.hpp", "mpc_evaluate.hpp", "mpc_solve_kernel.hpp", "mpc_core.hpp", "mpc_problem.hpp", "mpc_launch_plan.hpp", "mpc_layout.hpp", "mpc_wave.hpp", "mpc_wave_layout.hpp", "mpc_wave_debug.hpp", "mpc_wave_rows.inc", "mpc_wave_passes.inc", "mpc_wave_sweeps.inc", "mpc_wave_pit.inc",
            "mpc_wave_step.inc", "mpc_wave_solve.inc", "mpc_dpp_blocks.inc", "mpc_costmap.hpp", "mpc_feasibility.hpp", "mpc_grid_update.hpp", os.path.join("..", "..", "include", "mpc_hip.h")]
 
 EXPORTS = [
     "mpc_config_defaults", "mpc_create", "mpc_reset", "mpc_destroy", "mpc_solve_batch",
-    "mpc_solve_batch_device", "mpc_step_batch", "mpc_step_batch_device", "mpc_cycle_params_defaults", "mpc_controller_step_batch", "mpc_controller_step_batch_device", "mpc_controller_state", "mpc_set_grid_sizes", "mpc_set_parameter_sets", "mpc_set_via_points", "mpc_set_via_points_device", "mpc_costmap_to_obstacles", "mpc_costmap_to_obstacles_device", "mpc_last_candidates", "mpc_last_rows_dropped", "mpc_check_feasibility", "mpc_check_feasibility_device", "mpc_evaluate_batch", "mpc_evaluate_batch_device", "mpc_grid_update_device", "mpc_get_grid_sizes", "mpc_synchronize", "mpc_last_kernel_ms", "mpc_lds_bytes", "mpc_occupancy", "mpc_last_error", "mpc_version",
+    "mpc_solve_batch_device", "mpc_step_batch", "mpc_step_batch_device", "mpc_cycle_params_defaults", "mpc_controller_step_batch", "mpc_controller_step_batch_device", "mpc_controller_state", "mpc_set_grid_sizes", "mpc_set_parameter_sets", "mpc_set_via_points", "mpc_set_via_points_device", "mpc_costmap_to_obstacles", "mpc_costmap_to_obstacles_device", "mpc_last_candidates", "mpc_last_rows_dropped", "mpc_check_feasibility", "mpc_check_feasibility_device", "mpc_evaluate_batch", "mpc_evaluate_batch_device", "mpc_plan_params_defaults", "mpc_plan_inputs_batch", "mpc_plan_inputs_batch_device", "mpc_commands_batch", "mpc_commands_batch_device", "mpc_grid_update_device", "mpc_get_grid_sizes", "mpc_synchronize", "mpc_last_kernel_ms", "mpc_lds_bytes", "mpc_occupancy", "mpc_last_error", "mpc_version",
 ]
 
 
@@ -174,6 +174,18 @@ def load() -> C.CDLL:
     lib.mpc_evaluate_batch.restype = C.c_int
     lib.mpc_evaluate_batch_device.argtypes = ev
     lib.mpc_evaluate_batch_device.restype = C.c_int
+    lib.mpc_plan_params_defaults.argtypes = [C.POINTER(MpcPlanParams)]
+    lib.mpc_plan_params_defaults.restype = None
+    pin = [C.c_void_p, C.c_int32, C.POINTER(MpcPlanParams), dp, dp, C.c_int32, dp, dp, dp, dp, C.c_int32] + [dp] * 4      # ..., global_plan, n_global, gstride, robot_pose, plan_begin, plan, n_plan, plan_stride, n_via, via, goal_idx, flags
+    lib.mpc_plan_inputs_batch.argtypes = pin
+    lib.mpc_plan_inputs_batch.restype = C.c_int
+    lib.mpc_plan_inputs_batch_device.argtypes = pin
+    lib.mpc_plan_inputs_batch_device.restype = C.c_int
+    cmdsig = [C.c_void_p, C.c_int32] + [dp] * 9      # ..., u_out, status, feasible, plan_flags, cmd, result, reset_next, u_prev_next, infeasible_count
+    lib.mpc_commands_batch.argtypes = cmdsig
+    lib.mpc_commands_batch.restype = C.c_int
+    lib.mpc_commands_batch_device.argtypes = cmdsig
+    lib.mpc_commands_batch_device.restype = C.c_int
     lib.mpc_grid_update_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double]
     lib.mpc_grid_update_device.restype = C.c_int
     lib.mpc_get_grid_sizes.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]

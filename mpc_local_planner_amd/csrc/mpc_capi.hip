@@ -22,6 +22,7 @@
 #include "mpc_grid_update.hpp"
 #include "mpc_controller_cycle.hpp"
 #include "mpc_evaluate.hpp"
+#include "mpc_plan_inputs.hpp"
 
 namespace {
 
@@ -49,7 +50,7 @@ struct Buf {
     int fill;           // the idle contents mpc_create writes
     bool reset, pinned; // mpc_reset writes them again; host memory (hipHostMalloc)
 };
-enum { BUF_TAB, BUF_SET_OF, BUF_H_TAB, BUF_STAGE, BUF_H_IN, BUF_CYC_LIVE, BUF_CYC, BUF_CYC_HSTAGE, BUF_CYC_DSTAGE, BUF_EVAL_HSTAGE, BUF_EVAL_DSTAGE, BUF_NAMED };      // the entries other entry points ask for (declare_buffers assigns them by index)
+enum { BUF_TAB, BUF_SET_OF, BUF_H_TAB, BUF_STAGE, BUF_H_IN, BUF_CYC_LIVE, BUF_CYC, BUF_CYC_HSTAGE, BUF_CYC_DSTAGE, BUF_EVAL_HSTAGE, BUF_EVAL_DSTAGE, BUF_PLAN_HSTAGE, BUF_PLAN_DSTAGE, BUF_NAMED };      // the entries other entry points ask for (declare_buffers assigns them by index)
 
 struct mpc_solver {
     mpc_config cfg;
@@ -105,6 +106,7 @@ struct mpc_solver {
     unsigned char* d_cyc;
     unsigned char *h_cyc_stage, *d_cyc_stage;      // staging of the host variant's own inputs (plans, feedback, reset) and of reinit_out, grows on demand
     unsigned char *h_eval_stage, *d_eval_stage;    // staging of mpc_evaluate_batch (inputs, then the five outputs), allocated by its first call, grows on demand
+    unsigned char *h_plan_stage, *d_plan_stage;    // staging of mpc_plan_inputs_batch and mpc_commands_batch, allocated by the first such call, grows on demand
 };
 
 // the pieces of the slot-state block
@@ -232,6 +234,8 @@ static void declare_buffers(mpc_solver* s) {
     s->bufs[BUF_CYC_DSTAGE] = {(void**)&s->d_cyc_stage, 0, FILL_NONE, false, false};
     s->bufs[BUF_EVAL_HSTAGE] = {(void**)&s->h_eval_stage, 0, FILL_NONE, false, true};       // the two of mpc_evaluate_batch: allocated by its first call
     s->bufs[BUF_EVAL_DSTAGE] = {(void**)&s->d_eval_stage, 0, FILL_NONE, false, false};
+    s->bufs[BUF_PLAN_HSTAGE] = {(void**)&s->h_plan_stage, 0, FILL_NONE, false, true};       // the two of mpc_plan_inputs_batch / mpc_commands_batch: allocated by the first such call
+    s->bufs[BUF_PLAN_DSTAGE] = {(void**)&s->d_plan_stage, 0, FILL_NONE, false, false};
     add(&s->h_out, cap.out_bytes, FILL_NONE, false, true);
     add(&s->d_in, cap.in_bytes);
     add(&s->d_out, cap.out_bytes);
@@ -309,8 +313,20 @@ void mpc_cycle_params_defaults(mpc_cycle_params* p) {
     p->period = 0.1;
 }
 
+void mpc_plan_params_defaults(mpc_plan_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->global_plan_prune_distance = 1.0;        // include/mpc_local_planner/mpc_local_planner_ros.h:369-391
+    p->max_global_plan_lookahead_dist = 1.5;
+    p->global_plan_viapoint_sep = -1.0;
+    p->xy_goal_tolerance = 0.2; p->yaw_goal_tolerance = 0.1;
+    p->global_plan_overwrite_orientation = 1;
+    p->moving_average_length = 3;               // :363-364
+    p->costmap_size_x = 200; p->costmap_size_y = 200; p->resolution = 0.05;      // costmap_2d's own defaults (10 m x 10 m)
+}
+
 const char* mpc_last_error(void) { return g_err; }
-int32_t mpc_version(void) { return 900; }      // 0.9.0: mpc_evaluate_batch* (CHANGELOG.md has what each version brought)
+int32_t mpc_version(void) { return 900; }      // 0.9.0: mpc_evaluate_batch* (CHANGELOG.md has what each version brought); mpc_plan_inputs_batch* / mpc_commands_batch* came later under the same number: tests/test_evaluate_host.py pins this line
 
 #ifdef MPC_PROFILE
 // developer build only (-DMPC_PROFILE): per-wave phase cycle counters of the last wave-kernel launch, mpc::kProfCols words per row
@@ -1113,6 +1129,135 @@ int mpc_evaluate_batch(mpc_solver* s, int32_t B, const double* x0, const double*
     HIP_TRY(hipStreamSynchronize(q));
     for (int i = N_IN; i < N_ALL; ++i) if (sz[i]) memcpy(dst[i - N_IN], s->h_eval_stage + off[i], sz[i]);
     return MPC_OK;
+}
+
+}  // extern "C"
+
+// ---- what the plugin runs around the step (mpc_plan_inputs.hpp)
+
+// the argument checks both variants of mpc_plan_inputs_batch share: NULL when the call is fine
+static const char* plan_inputs_error(const mpc_solver* s, const mpc_plan_params* p, const void* global_plan, const void* n_global, int32_t gstride, const void* robot_pose,
+                                     const void* plan, const void* n_plan, int32_t plan_stride, const void* n_via, const void* via) {
+    if (!s || !p || !global_plan || !n_global || !robot_pose || !plan || !n_plan) return "mpc_plan_inputs_batch: null argument (p, global_plan, n_global, robot_pose, plan, n_plan)";
+    if (gstride < 2 || plan_stride < 2) return "mpc_plan_inputs_batch: gstride and plan_stride have to be at least 2";
+    if ((n_via != nullptr) != (via != nullptr)) return "mpc_plan_inputs_batch: n_via and via go together";
+    if (via && s->cfg.max_via_points <= 0) return "mpc_plan_inputs_batch: via-point outputs on a handle with max_via_points == 0";
+    return nullptr;
+}
+
+extern "C" {
+
+int mpc_plan_inputs_batch_device(mpc_solver* s, int32_t B, const mpc_plan_params* p, const double* d_global_plan, const int32_t* d_n_global, int32_t gstride,
+                                 const double* d_robot_pose, int32_t* d_plan_begin, double* d_plan, int32_t* d_n_plan, int32_t plan_stride,
+                                 int32_t* d_n_via, double* d_via, int32_t* d_goal_idx, int32_t* d_flags) {
+    g_err[0] = 0;
+    if (const char* e = plan_inputs_error(s, p, d_global_plan, d_n_global, gstride, d_robot_pose, d_plan, d_n_plan, plan_stride, d_n_via, d_via)) { set_err(e); return MPC_EINVAL; }
+    if (B <= 0) return MPC_OK;
+    if (B > s->max_batch) { set_err("mpc_plan_inputs_batch: B exceeds max_batch"); return MPC_EBATCH; }
+    HIP_TRY(hipSetDevice(s->device));
+    mpc::PlanInputsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.p = {p->global_plan_prune_distance, p->max_global_plan_lookahead_dist, p->global_plan_viapoint_sep, p->xy_goal_tolerance, p->yaw_goal_tolerance,
+           p->global_plan_overwrite_orientation, p->moving_average_length, p->costmap_size_x, p->costmap_size_y, p->resolution};
+    a.global = d_global_plan; a.n_global = d_n_global; a.gstride = gstride; a.robot = d_robot_pose; a.begin = d_plan_begin;
+    a.plan = d_plan; a.n_plan = d_n_plan; a.plan_stride = plan_stride; a.max_via = s->cfg.max_via_points > 0 ? s->cfg.max_via_points : 0;
+    a.n_via = d_n_via; a.via = d_via; a.goal_idx = d_goal_idx; a.flags = d_flags;
+    hipLaunchKernelGGL(mpc::plan_inputs_kernel, dim3(B), dim3(64), 0, s->stream, a);
+    HIP_TRY(hipGetLastError());
+    return MPC_OK;
+}
+
+}  // extern "C"
+
+// u_stride: rows between two instances' first controls (cfg.n for u_out itself; 1 for the host variant's compact copy of the first rows)
+static int commands_device(mpc_solver* s, int32_t B, const double* d_u, int32_t u_stride, const int32_t* d_status, const int32_t* d_feasible, const int32_t* d_plan_flags,
+                           double* d_cmd, int32_t* d_result, int32_t* d_reset_next, double* d_u_prev_next, int32_t* d_infeasible_count) {
+    g_err[0] = 0;
+    if (!s || !d_u || !d_status || !d_cmd || !d_result) { set_err("mpc_commands_batch: null argument (u_out, status, cmd, result)"); return MPC_EINVAL; }
+    if (B <= 0) return MPC_OK;
+    if (B > s->max_batch) { set_err("mpc_commands_batch: B exceeds max_batch"); return MPC_EBATCH; }
+    HIP_TRY(hipSetDevice(s->device));
+    const mpc::CommandsArgs a = {d_u, u_stride, B, d_status, d_feasible, d_plan_flags, d_cmd, d_result, d_reset_next, d_u_prev_next, d_infeasible_count};
+    hipLaunchKernelGGL(mpc::commands_kernel, dim3((B + 63) / 64), dim3(64), 0, s->stream, a);
+    HIP_TRY(hipGetLastError());
+    return MPC_OK;
+}
+
+extern "C" {
+
+int mpc_commands_batch_device(mpc_solver* s, int32_t B, const double* d_u_out, const int32_t* d_status, const int32_t* d_feasible, const int32_t* d_plan_flags,
+                              double* d_cmd, int32_t* d_result, int32_t* d_reset_next, double* d_u_prev_next, int32_t* d_infeasible_count) {
+    return commands_device(s, B, d_u_out, s ? s->cfg.n : 0, d_status, d_feasible, d_plan_flags, d_cmd, d_result, d_reset_next, d_u_prev_next, d_infeasible_count);
+}
+
+}  // extern "C"
+
+// One pinned block and one device block for the host variants: every given array goes in (in / out ones and outputs alike, so that what a kernel leaves alone comes back
+// as it was), the kernel runs, the arrays marked `back` come out.
+struct StagePiece { const void* src; void* dst; size_t bytes; };
+static int staged_call(mpc_solver* s, StagePiece* pc, int count, void** dev, int (*run)(void* ctx, void** dev), void* ctx) {
+    hipStream_t q = s->stream;
+    size_t off[24];
+    mpc::Packer pk;
+    for (int i = 0; i < count; ++i) off[i] = pk.take(pc[i].src || pc[i].dst ? pc[i].bytes : 0);
+    for (Buf* bf : {&s->bufs[BUF_PLAN_HSTAGE], &s->bufs[BUF_PLAN_DSTAGE]})
+        if (pk.off > bf->bytes) { HIP_TRY(hipStreamSynchronize(q)); HIP_TRY(buf_alloc(*bf, pk.off)); }
+    for (int i = 0; i < count; ++i) {
+        const void* from = pc[i].src ? pc[i].src : pc[i].dst;
+        dev[i] = from ? (void*)(s->d_plan_stage + off[i]) : nullptr;
+        if (from) memcpy(s->h_plan_stage + off[i], from, pc[i].bytes);
+    }
+    if (pk.off) HIP_TRY(hipMemcpyAsync(s->d_plan_stage, s->h_plan_stage, pk.off, hipMemcpyHostToDevice, q));
+    const int rc = run(ctx, dev);
+    if (rc != MPC_OK) return rc;
+    if (pk.off) HIP_TRY(hipMemcpyAsync(s->h_plan_stage, s->d_plan_stage, pk.off, hipMemcpyDeviceToHost, q));
+    HIP_TRY(hipStreamSynchronize(q));
+    for (int i = 0; i < count; ++i) if (pc[i].dst) memcpy(pc[i].dst, s->h_plan_stage + off[i], pc[i].bytes);
+    return MPC_OK;
+}
+
+extern "C" {
+
+int mpc_plan_inputs_batch(mpc_solver* s, int32_t B, const mpc_plan_params* p, const double* global_plan, const int32_t* n_global, int32_t gstride,
+                          const double* robot_pose, int32_t* plan_begin, double* plan, int32_t* n_plan, int32_t plan_stride,
+                          int32_t* n_via, double* via, int32_t* goal_idx, int32_t* flags) {
+    g_err[0] = 0;
+    if (const char* e = plan_inputs_error(s, p, global_plan, n_global, gstride, robot_pose, plan, n_plan, plan_stride, n_via, via)) { set_err(e); return MPC_EINVAL; }
+    if (B <= 0) return MPC_OK;
+    if (B > s->max_batch) { set_err("mpc_plan_inputs_batch: B exceeds max_batch"); return MPC_EBATCH; }
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t nb = (size_t)B, mv = s->cfg.max_via_points > 0 ? (size_t)s->cfg.max_via_points : 0;
+    StagePiece pc[10] = {{global_plan, nullptr, nb * (size_t)gstride * 24}, {n_global, nullptr, nb * 4}, {robot_pose, nullptr, nb * 24}, {nullptr, plan_begin, nb * 4},
+                         {nullptr, plan, nb * (size_t)plan_stride * 24}, {nullptr, n_plan, nb * 4}, {nullptr, n_via, nb * 4}, {nullptr, via, nb * mv * 24},
+                         {nullptr, goal_idx, nb * 4}, {nullptr, flags, nb * 4}};
+    void* dev[10];
+    struct Ctx { mpc_solver* s; int32_t B, gstride, plan_stride; const mpc_plan_params* p; } ctx = {s, B, gstride, plan_stride, p};
+    return staged_call(s, pc, 10, dev, [](void* c, void** d) {
+        const Ctx& x = *(const Ctx*)c;
+        return mpc_plan_inputs_batch_device(x.s, x.B, x.p, (const double*)d[0], (const int32_t*)d[1], x.gstride, (const double*)d[2], (int32_t*)d[3], (double*)d[4], (int32_t*)d[5],
+                                            x.plan_stride, (int32_t*)d[6], (double*)d[7], (int32_t*)d[8], (int32_t*)d[9]);
+    }, &ctx);
+}
+
+int mpc_commands_batch(mpc_solver* s, int32_t B, const double* u_out, const int32_t* status, const int32_t* feasible, const int32_t* plan_flags,
+                       double* cmd, int32_t* result, int32_t* reset_next, double* u_prev_next, int32_t* infeasible_count) {
+    g_err[0] = 0;
+    if (!s || !u_out || !status || !cmd || !result) { set_err("mpc_commands_batch: null argument (u_out, status, cmd, result)"); return MPC_EINVAL; }
+    if (B <= 0) return MPC_OK;
+    if (B > s->max_batch) { set_err("mpc_commands_batch: B exceeds max_batch"); return MPC_EBATCH; }
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t nb = (size_t)B;
+    std::vector<double> u0(2 * nb);      // only the first control of every instance travels
+    for (size_t b = 0; b < nb; ++b) { u0[2 * b] = u_out[b * (size_t)s->cfg.n * 2]; u0[2 * b + 1] = u_out[b * (size_t)s->cfg.n * 2 + 1]; }
+    StagePiece pc[9] = {{u0.data(), nullptr, nb * 16}, {status, nullptr, nb * 4}, {feasible, nullptr, nb * 4}, {plan_flags, nullptr, nb * 4},
+                        {nullptr, cmd, nb * 24}, {nullptr, result, nb * 4}, {nullptr, reset_next, nb * 4}, {nullptr, u_prev_next, nb * 16}, {nullptr, infeasible_count, nb * 4}};
+    void* dev[9];
+    struct Ctx { mpc_solver* s; int32_t B; } ctx = {s, B};
+    return staged_call(s, pc, 9, dev, [](void* c, void** d) {
+        const Ctx& x = *(const Ctx*)c;
+        return commands_device(x.s, x.B, (const double*)d[0], 1, (const int32_t*)d[1], (const int32_t*)d[2], (const int32_t*)d[3], (double*)d[4], (int32_t*)d[5],
+                               (int32_t*)d[6], (double*)d[7], (int32_t*)d[8]);
+    }, &ctx);
 }
 
 }  // extern "C"

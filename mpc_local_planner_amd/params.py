@@ -360,7 +360,7 @@ def cycle_params_from_dict(params: dict, period: float = 0.1, reference_reinit_s
 def plugin_options_from_params(params: dict, move_base_params: dict | None = None) -> dict:
     """The parameters that MpcLocalPlannerROS::initialize reads for ITSELF (src/mpc_local_planner_ros.cpp:96-125, :220), with the in-code defaults of
     include/mpc_local_planner/mpc_local_planner_ros.h:369-391 -- what a binding needs around the solve: goal tolerances, plan pruning / look-ahead, via-point separation
-    (plugin_inputs.via_points_from_plan), the costmap scan (BatchSolver.costmap_to_obstacles: include_costmap_obstacles, costmap_obstacles_behind_robot_dist), the
+    (all five through plan_params_from_options -> BatchSolver.plan_inputs), the costmap scan (BatchSolver.costmap_to_obstacles: include_costmap_obstacles, costmap_obstacles_behind_robot_dist), the
     feasibility check (BatchSolver.check_feasibility: collision_check_min_resolution_angular, collision_check_no_poses).  controller_frequency is move_base's own
     parameter (the control period handed to step() is its inverse, :380): taken from move_base_params."""
     p = _Reader(params)
@@ -381,6 +381,23 @@ def plugin_options_from_params(params: dict, move_base_params: dict | None = Non
         "costmap_converter_spin_thread": p.get("costmap_converter_spin_thread", True),
         "controller_frequency": mb.get("controller_frequency", 10.0),
     }
+
+
+def plan_params_from_options(plugin_options: dict, costmap_shape, resolution: float, moving_average_length: int = 3) -> "A.MpcPlanParams":
+    """struct mpc_plan_params (mpc_plan_inputs_batch*) from what plugin_options_from_params returns and the local costmap's geometry: costmap_shape = (size_y, size_x)
+    cells as a costmap array has them (BatchSolver.costmap_to_obstacles), resolution in metres per cell.  moving_average_length: estimateLocalGoalOrientation's default
+    argument (mpc_local_planner_ros.h:363-364), no parameter of the reference."""
+    c = A.MpcPlanParams()
+    c.global_plan_prune_distance = float(plugin_options["global_plan_prune_distance"])
+    c.max_global_plan_lookahead_dist = float(plugin_options["max_global_plan_lookahead_dist"])
+    c.global_plan_viapoint_sep = float(plugin_options["global_plan_viapoint_sep"])
+    c.xy_goal_tolerance = float(plugin_options["xy_goal_tolerance"])
+    c.yaw_goal_tolerance = float(plugin_options["yaw_goal_tolerance"])
+    c.global_plan_overwrite_orientation = int(bool(plugin_options["global_plan_overwrite_orientation"]))
+    c.moving_average_length = int(moving_average_length)
+    c.costmap_size_y, c.costmap_size_x = int(costmap_shape[0]), int(costmap_shape[1])
+    c.resolution = float(resolution)
+    return c
 
 
 def _is_number(v) -> bool:

@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._abi import MpcConfig, MpcCycleParams, MpcEvalOut, MpcObstacles, MPC_OK
+from ._abi import MpcConfig, MpcCycleParams, MpcEvalOut, MpcObstacles, MpcPlanParams, MPC_OK
 
 
 class MpcError(RuntimeError):
@@ -39,6 +39,28 @@ class TrajectoryEval:
     ineq_violation: np.ndarray  # (B,)
     clearance: np.ndarray       # (B,)  +inf without obstacles
     closest: np.ndarray         # (B, 2) int32: (grid point, obstacle) of the clearance, (-1, -1) without obstacles
+
+
+@dataclass
+class PlanInputs:
+    """what mpc_plan_inputs_batch prepares for B robots (include/mpc_hip.h)"""
+    plan: np.ndarray            # (B, plan_stride, 3) the local plan, first pose = the robot pose
+    n_plan: np.ndarray          # (B,) int32 poses of it
+    plan_begin: np.ndarray      # (B,) int32 the pruned fronts: plan_begin of the next cycle
+    goal_idx: np.ndarray        # (B,) int32 index of the local goal counted from the front (-1: plan empty)
+    flags: np.ndarray           # (B,) int32 PLAN_* bits
+    n_via: Optional[np.ndarray]     # (B,) int32, with via_points
+    via: Optional[np.ndarray]       # (B, max_via_points, 3)
+
+
+@dataclass
+class Commands:
+    """what mpc_commands_batch makes of a step's result for B robots (include/mpc_hip.h)"""
+    cmd: np.ndarray             # (B, 3) linear.x, linear.y, angular.z
+    result: np.ndarray          # (B,) int32 CMD_*
+    reset_next: np.ndarray      # (B,) int32: reset of the next controller_step
+    u_prev_next: np.ndarray     # (B, 2): u_prev of the next controller_step
+    infeasible_count: np.ndarray    # (B,) int32 failures in a row
 
 
 def _addr(a):
@@ -249,6 +271,67 @@ class BatchSolver:
         out = MpcEvalOut(objective or None, eq_violation or None, ineq_violation or None, clearance or None, closest or None)
         self._check(self._lib.mpc_evaluate_batch_device(self._h, int(B), v(x0), v(xf), v(u_prev), v(dt_prev), v(x), v(u), v(dt), C.byref(ob) if ob is not None else None,
                                                         C.byref(out)))
+
+    def plan_params(self, **fields) -> MpcPlanParams:
+        """mpc_plan_params with the reference's in-code defaults (mpc_plan_params_defaults), then the given fields"""
+        p = MpcPlanParams()
+        self._lib.mpc_plan_params_defaults(C.byref(p))
+        for k, v in fields.items():
+            if k not in dict(MpcPlanParams._fields_):
+                raise ValueError(f"mpc_plan_params has no field {k}")
+            setattr(p, k, v)
+        return p
+
+    def plan_inputs(self, params: MpcPlanParams, global_plan, n_global, robot_pose, plan_stride: int, plan_begin=None, via_points: bool = False) -> PlanInputs:
+        """What the plugin prepares before Controller::step, for B robots (mpc_plan_inputs_batch; src/mpc_local_planner_ros.cpp:294-354): prune, select, via-points,
+        goal-reached test, local goal heading, start / goal overwrite.  global_plan (B, gstride, 3) in the planning frame with n_global (B,) poses each; robot_pose (B, 3);
+        plan_begin (B,) the persistent fronts of the cycle before (None = 0).  via_points: also fill n_via / via (needs cfg.max_via_points > 0)."""
+        gp = np.ascontiguousarray(global_plan, dtype=np.float64)
+        B, gstride = int(gp.shape[0]), int(gp.shape[1])
+        gp = _as_f64(gp, (B, gstride, 3))
+        ng = np.ascontiguousarray(n_global, dtype=np.int32)
+        if ng.shape != (B,):
+            raise ValueError("n_global must have shape (B,)")
+        rp = _as_f64(robot_pose, (B, 3))
+        r = PlanInputs(np.zeros((B, int(plan_stride), 3)), np.zeros(B, np.int32),
+                       np.zeros(B, np.int32) if plan_begin is None else np.array(plan_begin, dtype=np.int32).reshape(B),
+                       np.zeros(B, np.int32), np.zeros(B, np.int32),
+                       np.zeros(B, np.int32) if via_points else None, np.zeros((B, max(int(self.cfg.max_via_points), 0), 3)) if via_points else None)
+        self._check(self._lib.mpc_plan_inputs_batch(self._h, B, C.byref(params), _addr(gp), _addr(ng), gstride, _addr(rp), _addr(r.plan_begin), _addr(r.plan), _addr(r.n_plan),
+                                                    int(plan_stride), _addr(r.n_via), _addr(r.via), _addr(r.goal_idx), _addr(r.flags)))
+        return r
+
+    def plan_inputs_device(self, B: int, params: MpcPlanParams, global_plan: int, n_global: int, gstride: int, robot_pose: int, plan_begin: Optional[int], plan: int,
+                           n_plan: int, plan_stride: int, n_via: Optional[int] = None, via: Optional[int] = None, goal_idx: Optional[int] = None,
+                           flags: Optional[int] = None) -> None:
+        """mpc_plan_inputs_batch_device: the same with device addresses (ints), asynchronous on the solver's stream; plan / n_plan feed controller_step_device, n_via / via
+        mpc_set_via_points_device"""
+        v = lambda p: C.c_void_p(p) if p else None
+        self._check(self._lib.mpc_plan_inputs_batch_device(self._h, int(B), C.byref(params), v(global_plan), v(n_global), int(gstride), v(robot_pose), v(plan_begin), v(plan),
+                                                           v(n_plan), int(plan_stride), v(n_via), v(via), v(goal_idx), v(flags)))
+
+    def commands(self, u, status, feasible=None, plan_flags=None, infeasible_count=None) -> Commands:
+        """What the plugin does with the step's result, for B robots (mpc_commands_batch; src/mpc_local_planner_ros.cpp:394-452): the velocity command, the result code,
+        the reset flag and the previous control of the next cycle.  u (B, n, 2) = BatchResult.u; status (B,); feasible (B,) of check_feasibility (None = feasible);
+        plan_flags (B,) of plan_inputs (None = none); infeasible_count (B,): the counts so far (None = 0)."""
+        u = np.ascontiguousarray(u, dtype=np.float64)
+        B = int(u.shape[0])
+        u = _as_f64(u, (B, self.n, 2))
+        i32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32).reshape(B)
+        st, fe, fl = i32(status), i32(feasible), i32(plan_flags)
+        r = Commands(np.zeros((B, 3)), np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros((B, 2)),
+                     np.zeros(B, np.int32) if infeasible_count is None else np.array(infeasible_count, dtype=np.int32).reshape(B))
+        self._check(self._lib.mpc_commands_batch(self._h, B, _addr(u), _addr(st), _addr(fe), _addr(fl), _addr(r.cmd), _addr(r.result), _addr(r.reset_next), _addr(r.u_prev_next),
+                                                 _addr(r.infeasible_count)))
+        return r
+
+    def commands_device(self, B: int, u: int, status: int, feasible: Optional[int], plan_flags: Optional[int], cmd: int, result: int, reset_next: Optional[int] = None,
+                        u_prev_next: Optional[int] = None, infeasible_count: Optional[int] = None) -> None:
+        """mpc_commands_batch_device: the same with device addresses (ints), asynchronous on the solver's stream; reset_next / u_prev_next are the reset / u_prev of the
+        next controller_step_device"""
+        v = lambda p: C.c_void_p(p) if p else None
+        self._check(self._lib.mpc_commands_batch_device(self._h, int(B), v(u), v(status), v(feasible), v(plan_flags), v(cmd), v(result), v(reset_next), v(u_prev_next),
+                                                        v(infeasible_count)))
 
     def set_grid_sizes(self, n_grid=None):
         """Per-instance grid sizes n_i <= cfg.n for the following solves (grid adaptation); None = uniform cfg.n."""

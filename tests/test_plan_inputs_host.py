@@ -1,0 +1,274 @@
+"""CPU tests of the per-instance logic of mpc_plan_inputs_batch* and mpc_commands_batch* (mpc_local_planner_amd/csrc/mpc_plan_inputs.hpp), compiled for the host with g++ by
+a tests-only harness (tests/host_harness/plan_inputs_host.cpp): on scripted and random plans every discrete output (front, goal index, n_plan, n_via, flags) and every copied
+pose equals, exactly, what the facade's prune_global_plan, transform_global_plan and via_points_from_plan (include/mpc_controller.hpp) plus a literal restatement of
+src/mpc_local_planner_ros.cpp:312-354 give; the local goal's heading is held to the facade's estimate_local_goal_orientation (libm) within a bound measured here; the
+double-double atan2 of this header equals cc_atan2 bit for bit; struct mpc_plan_params has the C layout; and the harness, built as a stand-alone program with
+-fsanitize=address,undefined, runs its own cases clean."""
+import ctypes as C
+import math
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import _plan_inputs_cases as K
+from mpc_local_planner_amd._abi import (PLAN_EMPTY, PLAN_GOAL_INJECTED, PLAN_GOAL_REACHED, PLAN_TRUNCATED, PLAN_VIA_DROPPED, CMD_GOAL_REACHED, CMD_INFEASIBLE, CMD_NOT_FINITE,
+                                        CMD_PLAN_EMPTY, CMD_SOLVE_FAILED, CMD_SUCCESS)
+
+# The heading estimate against libm (test_goal_heading_*): largest difference measured on 20000 plans whose segment directions turn by at most 60 degrees: 4.44e-16 rad = 2^-51
+# (profiles/r14_plan_inputs.md); the bound is 4 x that, rounded up to a power of two.  Anything above 1.6e-14 would be a mistake, not a bound to accept.
+HEADING_BOUND = 2.0 ** -49      # 1.78e-15
+
+
+@pytest.fixture(scope="module")
+def h():
+    return K.harness()
+
+
+def _wrapped(a, b):
+    d = abs(a - b)
+    return min(d, abs(2.0 * math.pi - d))
+
+
+def _same_as_facade(p, plan, robot, begin, plan_stride, max_via, what):
+    """one instance through pi_instance and through the facade: discrete outputs and copied poses exact, the last pose's heading within HEADING_BOUND; returns pi's outputs"""
+    g = np.full((1, max(2, len(plan)), 3), 777.0)
+    g[0, :len(plan)] = plan
+    mine = K.host_batch(p, g, np.array([len(plan)], np.int32), np.ascontiguousarray(robot[None]), np.array([begin], np.int32), plan_stride, max_via)
+    ref = K.host_facade(p, plan, robot, begin, plan_stride, max_via)
+    front, pl, n_plan, n_via, via, gi, fl = mine
+    rfront, rpl, rn_plan, rn_via, rvia, rgi, rfl = ref
+    assert (front[0], n_plan[0], n_via[0], gi[0]) == (rfront[0], rn_plan[0], rn_via[0], rgi[0]), what
+    assert fl[0] & ~PLAN_GOAL_INJECTED == rfl[0], what
+    assert via.tobytes() == rvia.tobytes(), what
+    n = int(n_plan[0])
+    assert pl[0].reshape(-1)[:3 * n - 1].tobytes() == rpl[0].reshape(-1)[:3 * n - 1].tobytes(), what
+    assert pl[0, n:].tobytes() == rpl[0, n:].tobytes(), what
+    if p.global_plan_overwrite_orientation:
+        assert _wrapped(pl[0, n - 1, 2], rpl[0, n - 1, 2]) <= HEADING_BOUND, (what, pl[0, n - 1, 2], rpl[0, n - 1, 2])
+    else:
+        assert pl[0, n - 1, 2].tobytes() == rpl[0, n - 1, 2].tobytes(), what
+    if fl[0] & PLAN_GOAL_INJECTED:
+        assert n == 2 and gi[0] == len(plan) - front[0] - 1, what
+    return mine
+
+
+def test_scripted_plans_equal_the_facade(h):
+    seen = {}
+    for grp in K.groups():
+        for what, plan, robot, begin in grp.inst:
+            out = _same_as_facade(grp.p, plan, robot, begin, grp.plan_stride, K.MAX_VIA, (grp.name, what))
+            seen[(grp.name, what)] = out
+    f = lambda g, w: tuple(int(a[0]) for a in (seen[(g, w)][0], seen[(g, w)][2], seen[(g, w)][3], seen[(g, w)][5], seen[(g, w)][6]))      # front, n_plan, n_via, goal_idx, flags
+    # what the scripted plans are there for does happen
+    assert f("main", "length 1, begin 0") == (0, 2, 0, 0, PLAN_GOAL_REACHED)
+    assert f("main", "length 1, robot far")[4] == PLAN_GOAL_INJECTED and f("main", "length 3, robot far")[3] == 2
+    assert f("main", "nearest pose tied between two indices")[0] == 0 and seen[("main", "nearest pose tied between two indices")][1][0, 1, 0] == 1.0      # walk starts at pose 1 (0.5), not 2 (1.0)
+    assert f("main", "robot beyond the prune distance of every pose")[0] == 0 and f("main", "robot within the prune distance of the first pose")[0] == 0
+    assert f("main", "look-ahead reached exactly at a pose")[1] == 8          # 0 .. 1.5 m in steps of 0.25 m, and the pose after: length <= look-ahead still held at 1.5
+    assert f("main", "begin at the last pose")[:2] == (99, 2)
+    assert [f("main", f"front at {a}, length {n}")[0] for a, n in ((0, 2), (63, 65), (64, 128), (63, 129))] == [0, 63, 64, 63]
+    assert [f("main", f"selection ends with the plan, length {n}")[3] for n in (1, 63, 64, 65)] == [0, 62, 63, 64]
+    sq_thr = (max(120 * 0.05 / 2.0, 100 * 0.05 / 2.0) * 0.85) ** 2
+    for lane, (step, n) in ((63, (0.041, 128)), (64, (0.04, 129))):      # where the nearest scan breaks (the look-ahead ends the walk long before)
+        assert int(np.argmax(K.line(n, step)[:, 0] ** 2 > sq_thr)) == lane
+    assert f("main", "non-zero begin off the chunk grid")[0] == 61 and f("main", "leaves the radius and returns")[3] < 60
+    assert f("no look-ahead limit (0)", "line")[1] == 51 + 1                   # poses 0 .. 50 lie within 2.55 m; pose 51, the first beyond, is still pushed
+    assert f("no look-ahead limit (< 0), truncated", "line")[1:5:3] == (5, PLAN_TRUNCATED | PLAN_VIA_DROPPED) and f("no look-ahead limit (< 0), truncated", "fits")[4] == 0
+    assert f("no look-ahead limit (< 0), truncated", "one more than fits")[4] == PLAN_TRUNCATED
+    assert f("no via-points (0)", "line")[2] == 0 and f("no via-points (< 0)", "line")[2] == 0
+    assert f("more via-points than fit", "line")[2:5:2] == (K.MAX_VIA, PLAN_VIA_DROPPED) and f("more via-points than fit", "exactly four")[2:5:2] == (4, 0)
+    assert f("xy tolerance, outside", "goal")[4] == 0 and f("xy tolerance, inside", "goal")[4] == PLAN_GOAL_REACHED
+    assert f("yaw tolerance, outside", "goal")[4] == 0 and f("yaw tolerance, inside", "goal")[4] == PLAN_GOAL_REACHED
+    assert f("heading difference of pi", f"goal heading {math.pi}")[4] == 0 and f("heading difference of pi", f"goal heading {-math.pi}")[4] == 0
+    assert f("heading difference of pi, wide", "goal heading pi")[4] == PLAN_GOAL_REACHED
+    assert len(seen) >= 50
+
+
+def test_random_plans_equal_the_facade(h):
+    count = 0
+    flags = 0
+    for p, plan, robot, begin, plan_stride, max_via in K.random_plans():
+        out = _same_as_facade(p, plan, robot, begin, plan_stride, max_via, count)
+        flags |= int(out[6][0])
+        count += 1
+    assert count == 300
+    assert flags & PLAN_TRUNCATED and flags & PLAN_VIA_DROPPED and flags & PLAN_GOAL_REACHED      # the random set reaches these on its own
+
+
+def test_empty_plan_and_null_begin(h):
+    p = K.params()
+    g = K.line(4, 0.1)[None].copy()
+    robot = np.array([[0.3, 0.2, 0.1]])
+    for ng, beg in ((0, 0), (4, 4), (4, 9), (-2, 0)):
+        front, pl, n_plan, n_via, via, gi, fl = K.host_batch(p, g, np.array([ng], np.int32), robot, np.array([beg], np.int32), 8)
+        assert (front[0], n_plan[0], n_via[0], gi[0], fl[0]) == (beg, 2, 0, -1, PLAN_EMPTY)
+        assert pl[0, 0].tolist() == pl[0, 1].tolist() == robot[0].tolist()
+    # no persistent front: begin NULL counts as 0, via outputs NULL skip the walk
+    plan, n_plan, n_via, via, gi, fl = K.blank_outputs(1, 8)
+    robot = np.array([[0.0, 0.2, 0.1]])
+    h.pin_batch(1, C.byref(p), K.d_(g), K.i_(np.array([4], np.int32)), 4, K.d_(robot), None, K.d_(plan), K.i_(n_plan), 8, 0, None, None, None, None)
+    assert n_plan[0] == 4 and plan[0, 0].tolist() == robot[0].tolist() and n_via[0] == -1
+
+
+def _turning_plan(rng, n, max_turn):
+    th = np.cumsum(np.concatenate([[rng.uniform(-math.pi, math.pi)], rng.uniform(-max_turn, max_turn, n - 1)]))
+    step = rng.uniform(0.01, 0.3, n)
+    return np.ascontiguousarray(np.column_stack([np.cumsum(step * np.cos(th)), np.cumsum(step * np.sin(th)), rng.uniform(-math.pi, math.pi, n)]))
+
+
+def test_goal_heading_against_the_facade_on_well_conditioned_sums(h):
+    """successive segment directions turn by at most 60 degrees: the three unit vectors sum to a length of at least 1, the mean is well conditioned, no case is left out"""
+    rng = np.random.default_rng(32)
+    worst = 0.0
+    for rep in range(20000):
+        n = int(rng.integers(6, 12))
+        plan = _turning_plan(rng, n, math.pi / 3.0)
+        gi = int(rng.integers(0, n - 5 + 1))          # goal_idx <= n - moving_average_length - 2: the averaging branch
+        a, b = h.pin_goal_heading(K.d_(plan), n, gi, 3), h.pin_facade_goal_heading(K.d_(plan), n, gi, 3)
+        worst = max(worst, _wrapped(a, b))
+    print(f"goal heading against libm: largest difference {worst:.3e} rad over 20000 plans")
+    assert worst <= HEADING_BOUND
+
+
+def test_goal_heading_near_the_end_of_the_plan_and_on_cancelling_sums(h):
+    rng = np.random.default_rng(33)
+    for rep in range(300):
+        n = int(rng.integers(1, 9))
+        plan = _turning_plan(rng, n, math.pi / 3.0)
+        if rep % 3 == 0:
+            plan[-1, 2] = (math.pi, -math.pi, 3.5)[rep // 3 % 3] if rep % 2 else plan[-1, 2]      # the last heading at +-pi and outside [-pi, pi)
+        for gi in range(n):                           # goal_idx >= n - 1: the pose's own heading; inside the window: the last pose's; outside: the mean
+            a, b = h.pin_goal_heading(K.d_(plan), n, gi, 3), h.pin_facade_goal_heading(K.d_(plan), n, gi, 3)
+            if gi >= n - 1:
+                assert a == plan[gi, 2] == b
+            elif gi > n - 3 - 2:
+                assert a == K.goal_distance((0, 0, plan[-1, 2]), (0, 0, 0.0))[1] * (1 if a >= 0 else -1) and -math.pi <= a < math.pi      # normalize_theta of the last heading
+                assert _wrapped(a, b) <= HEADING_BOUND, (rep, gi)
+            else:
+                assert _wrapped(a, b) <= HEADING_BOUND, (rep, gi)
+    # opposite directions: the sums cancel (exactly, or down to rounding); finite and in [-pi, pi], no comparison
+    for ang in np.linspace(-math.pi, math.pi, 49):
+        c, s = math.cos(ang), math.sin(ang)
+        for d in (0.5, 0.1, 1.0 / 3.0):
+            pts = [(0.0, 0.0), (d * c, d * s), (0.0, 0.0), (d * c, d * s), (0.0, 0.0), (d * c, d * s), (2 * d * c, 2 * d * s), (3 * d * c, 3 * d * s)]
+            plan = np.ascontiguousarray([(x, y, 0.1) for x, y in pts])
+            for mal in (2, 3, 4):
+                a = h.pin_goal_heading(K.d_(plan), len(plan), 0, mal)
+                assert math.isfinite(a) and -math.pi <= a <= math.pi, (ang, d, mal)
+    rep = np.ascontiguousarray([(1.0, 2.0, 0.3)] * 8)          # repeated poses: r == 0 gives (1, 0), as libm's atan2(0, 0) = 0
+    assert h.pin_goal_heading(K.d_(rep), 8, 0, 3) == 0.0 == h.pin_facade_goal_heading(K.d_(rep), 8, 0, 3)
+
+
+def test_this_headers_atan2_equals_cc_atan2_bit_for_bit(h):
+    rng = np.random.default_rng(34)
+    ys = np.concatenate([rng.uniform(-3, 3, 20000), rng.normal(0, 1e-3, 5000), rng.uniform(-3, 3, 5000)])
+    xs = np.concatenate([rng.uniform(-3, 3, 20000), rng.uniform(-3, 3, 5000), rng.normal(0, 1e-3, 5000)])
+    edge = [(0.0, 0.0), (0.0, -0.0), (-0.0, 0.0), (-0.0, -0.0), (0.0, 1.0), (0.0, -1.0), (-0.0, -1.0), (1.0, 0.0), (-1.0, 0.0), (1.0, -0.0), (1.0, 1.0), (-1.0, 1.0), (1.0, -1.0),
+            (-1.0, -1.0), (1e-300, 1.0), (1.0, 1e-300), (0.125, 1.0), (0.0625, 1.0), (1.0, 0.9375), (math.nan, 1.0), (1.0, math.nan)]
+    for y, x in list(zip(ys.tolist(), xs.tolist())) + edge:
+        assert np.float64(h.pin_atan2(y, x)).tobytes() == np.float64(h.pin_cc_atan2(y, x)).tobytes(), (y, x)
+
+
+def _commands_numpy(u0, status, feasible, flags, count):
+    """src/mpc_local_planner_ros.cpp:394-452 written from the source, with this project's result codes and its rule for a control that is not finite"""
+    cmd, reset, up = (0.0, 0.0, 0.0), 0, (tuple(u0) if all(math.isfinite(v) for v in u0) else (0.0, 0.0))
+    if flags & PLAN_EMPTY:
+        res = CMD_PLAN_EMPTY
+    elif flags & PLAN_GOAL_REACHED:
+        res = CMD_GOAL_REACHED
+    elif status != 0:
+        res, reset, count = CMD_SOLVE_FAILED, 1, count + 1
+    elif not feasible:
+        res, reset, count = CMD_INFEASIBLE, 1, count + 1
+    elif not all(math.isfinite(v) for v in u0):
+        res, reset, count = CMD_NOT_FINITE, 1, count + 1
+    else:
+        res, cmd, count = CMD_SUCCESS, (u0[0], 0.0, u0[1]), 0
+    return cmd, res, reset, up, count
+
+
+def commands_cases():
+    """every combination of status, feasibility, each plan flag and a control that is not finite: (u [B][2][2], status, feasible, flags)"""
+    rows = []
+    for status in (0, 1, 4):
+        for feasible in (1, 0):
+            for flags in (0, PLAN_GOAL_REACHED, PLAN_EMPTY, PLAN_TRUNCATED, PLAN_VIA_DROPPED, PLAN_GOAL_INJECTED, PLAN_GOAL_REACHED | PLAN_TRUNCATED):
+                for u0 in ((0.3, -0.2), (math.nan, 0.1), (0.2, math.inf)):
+                    rows.append((u0, status, feasible, flags))
+    u = np.zeros((len(rows), 2, 2))
+    u[:, 0] = [r[0] for r in rows]
+    u[:, 1] = 9.0
+    return u, np.array([r[1] for r in rows], np.int32), np.array([r[2] for r in rows], np.int32), np.array([r[3] for r in rows], np.int32)
+
+
+def test_commands_equal_the_restatement_over_three_calls(h):
+    u, st, fe, fl = commands_cases()
+    B = len(st)
+    cnt = (np.arange(B, dtype=np.int32) % 3).copy()
+    expect_cnt = cnt.tolist()
+    for call in range(3):
+        cmd, res, rs, up = np.full((B, 3), -7.0), np.full(B, -1, np.int32), np.full(B, -1, np.int32), np.full((B, 2), -7.0)
+        h.pin_commands(B, K.d_(u), 2, K.i_(st), K.i_(fe), K.i_(fl), K.d_(cmd), K.i_(res), K.i_(rs), K.d_(up), K.i_(cnt))
+        for b in range(B):
+            e = _commands_numpy(tuple(u[b, 0]), int(st[b]), int(fe[b]), int(fl[b]), expect_cnt[b])
+            assert (tuple(cmd[b]), int(res[b]), int(rs[b]), tuple(up[b])) == e[:4], (call, b)
+            expect_cnt[b] = e[4]
+        assert cnt.tolist() == expect_cnt
+    assert set(res.tolist()) == {CMD_SUCCESS, CMD_GOAL_REACHED, CMD_PLAN_EMPTY, CMD_SOLVE_FAILED, CMD_INFEASIBLE, CMD_NOT_FINITE}
+    # feasible / flags NULL count as feasible / none
+    cmd, res = np.zeros((B, 3)), np.zeros(B, np.int32)
+    h.pin_commands(B, K.d_(u), 2, K.i_(st), None, None, K.d_(cmd), K.i_(res), None, None, None)
+    assert all(int(res[b]) == _commands_numpy(tuple(u[b, 0]), int(st[b]), 1, 0, 0)[1] for b in range(B))
+
+
+def test_plan_params_struct_layout_matches_c(tmp_path):
+    from mpc_local_planner_amd._abi import MpcPlanParams
+    fields = [f[0] for f in MpcPlanParams._fields_]
+    src = tmp_path / "sz.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "mpc_hip.h"\nint main(){\nprintf("%zu\\n", sizeof(mpc_plan_params));\n' +
+                   "".join('printf("%%zu\\n", offsetof(mpc_plan_params,%s));\n' % f for f in fields) +
+                   'printf("%d %d %d %d %d\\n", MPC_PLAN_GOAL_REACHED, MPC_PLAN_EMPTY, MPC_PLAN_TRUNCATED, MPC_PLAN_VIA_DROPPED, MPC_PLAN_GOAL_INJECTED);\n'
+                   'printf("%d %d %d %d %d %d\\n", MPC_CMD_SUCCESS, MPC_CMD_GOAL_REACHED, MPC_CMD_PLAN_EMPTY, MPC_CMD_SOLVE_FAILED, MPC_CMD_INFEASIBLE, MPC_CMD_NOT_FINITE);\nreturn 0;}\n')
+    exe = tmp_path / "sz"
+    subprocess.run(["gcc", "-I", os.path.join(K.ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    out = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
+    assert out[0] == C.sizeof(MpcPlanParams)
+    assert len(out) == 1 + len(fields) + 11 and len(fields) == 10
+    for f, o in zip(fields, out[1:]):
+        assert getattr(MpcPlanParams, f).offset == o, f
+    assert out[1 + len(fields):] == [PLAN_GOAL_REACHED, PLAN_EMPTY, PLAN_TRUNCATED, PLAN_VIA_DROPPED, PLAN_GOAL_INJECTED, CMD_SUCCESS, CMD_GOAL_REACHED, CMD_PLAN_EMPTY,
+                                     CMD_SOLVE_FAILED, CMD_INFEASIBLE, CMD_NOT_FINITE]
+
+
+def test_plan_params_readers_fill_the_struct_from_the_plugin_options():
+    from mpc_local_planner_amd import params
+    o = params.plugin_options_from_params({"controller": {"xy_goal_tolerance": 0.3, "global_plan_viapoint_sep": 0.5, "global_plan_overwrite_orientation": False}})
+    p = params.plan_params_from_options(o, (100, 120), 0.05)
+    assert (p.global_plan_prune_distance, p.max_global_plan_lookahead_dist, p.global_plan_viapoint_sep, p.xy_goal_tolerance, p.yaw_goal_tolerance) == (1.0, 1.5, 0.5, 0.3, 0.1)
+    assert (p.global_plan_overwrite_orientation, p.moving_average_length, p.costmap_size_x, p.costmap_size_y, p.resolution) == (0, 3, 120, 100, 0.05)
+    assert "plugin_inputs" not in params.plugin_options_from_params.__doc__ and "plan_params_from_options" in params.plugin_options_from_params.__doc__
+    # the C++ twin (include/mpc_params.hpp) and mpc_plan_params_defaults' documented values
+    src = os.path.join(K.BUILD, "plan_params_from.cpp")
+    exe = os.path.join(K.BUILD, "plan_params_from")
+    os.makedirs(K.BUILD, exist_ok=True)
+    with open(src, "w") as f:
+        f.write('#include <cstdio>\n#include "mpc_params.hpp"\nint main(){ mpc_local_planner_amd::PluginOptions o; o.xy_goal_tolerance = 0.3; o.global_plan_viapoint_sep = 0.5; '
+                'o.global_plan_overwrite_orientation = false;\nconst mpc_plan_params p = mpc_local_planner_amd::plan_params_from(o, 120, 100, 0.05);\n'
+                'std::printf("%g %g %g %g %g %d %d %d %d %g\\n", p.global_plan_prune_distance, p.max_global_plan_lookahead_dist, p.global_plan_viapoint_sep, p.xy_goal_tolerance, '
+                'p.yaw_goal_tolerance, p.global_plan_overwrite_orientation, p.moving_average_length, p.costmap_size_x, p.costmap_size_y, p.resolution);\nreturn 0; }\n')
+    subprocess.run(["g++", "-std=c++17", "-DMPC_FACADE_HOST_LOOP_ONLY", "-I", os.path.join(K.ROOT, "include"), src, "-o", exe], check=True)
+    assert subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split() == "1 1.5 0.5 0.3 0.1 0 3 120 100 0.05".split()
+
+
+def test_harness_runs_clean_under_address_and_undefined_sanitizers():
+    """the stand-alone program (own main, own scripted and random plans, commands) built with -fsanitize=address,undefined; nothing sanitized is loaded into Python"""
+    exe = os.path.join(K.BUILD, "plan_inputs_sanitized")
+    if K.stale(exe):
+        os.makedirs(K.BUILD, exist_ok=True)
+        subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-DPIN_MAIN", K.SRC, "-o", exe],
+                       check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "333 cases, 0 differ" in r.stdout and "runtime error" not in r.stderr

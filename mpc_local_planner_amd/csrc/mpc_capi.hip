@@ -50,7 +50,7 @@ struct Buf {
     int fill;           // the idle contents mpc_create writes
     bool reset, pinned; // mpc_reset writes them again; host memory (hipHostMalloc)
 };
-enum { BUF_TAB, BUF_SET_OF, BUF_H_TAB, BUF_STAGE, BUF_H_IN, BUF_CYC_LIVE, BUF_CYC, BUF_CYC_HSTAGE, BUF_CYC_DSTAGE, BUF_EVAL_HSTAGE, BUF_EVAL_DSTAGE, BUF_PLAN_HSTAGE, BUF_PLAN_DSTAGE, BUF_NAMED };      // the entries other entry points ask for (declare_buffers assigns them by index)
+enum { BUF_TAB, BUF_SET_OF, BUF_H_TAB, BUF_H_IN, BUF_CYC_LIVE, BUF_CYC, BUF_H_STAGE, BUF_D_STAGE, BUF_NAMED };      // the entries other entry points ask for (declare_buffers assigns them by index)
 
 struct mpc_solver {
     mpc_config cfg;
@@ -79,8 +79,13 @@ struct mpc_solver {
     int max_batch;
     hipStream_t stream;
     hipEvent_t ev0, ev1;
-    // staging of the host-pointer entry point: ONE pinned host block and ONE device block each way (one H2D and one D2H per call; mpc::step_pieces)
+    // staging of mpc_solve_batch / mpc_step_batch (and of the solve inside mpc_controller_step_batch): ONE pinned host block and ONE device block each way (one H2D and
+    // one D2H per call; mpc::step_pieces), sized at mpc_create so that no call on the solve path allocates.  They stay apart from the shared pair below: a solve leaves
+    // last_status / last_iters pointing into d_out, and mpc_last_candidates reads them after whatever other host-pointer call came in between
     unsigned char *h_in, *h_out, *d_in, *d_out;
+    // staging of every other host-pointer call (staged_call; mpc::stage_layout): ONE pinned block and ONE device block, allocated by the first call that needs them,
+    // grown on demand.  Every such call ends in hipStreamSynchronize, so the pair is never in use twice
+    unsigned char *h_stage, *d_stage;
     int32_t* d_ngrid;
     int32_t *d_nvia;            // own copy of the via-point counts / poses (mpc_set_via_points) ...
     double *d_via;
@@ -95,7 +100,6 @@ struct mpc_solver {
     int32_t *d_winner, *d_iters_total;
     int32_t* d_rows_dropped;    // per instance: clearance rows that did not fit (solvers with obstacles)
     double* d_dual;             // per instance: multipliers of the last converged solve (dual_warm_start)
-    void* d_stage;              // device staging of the host-pointer helpers (mpc_costmap_to_obstacles, mpc_check_feasibility): kept across calls, grows on demand
     int dual_words;
     int32_t* last_status;       // device pointers of the most recent solve (mpc_last_candidates without candidates)
     int32_t* last_iters;
@@ -104,9 +108,6 @@ struct mpc_solver {
     // block with everything else -- step counts, has-solution flags, start modes, last goals, the x0 / xf the solves read and the slots' previous solutions x / u / dt
     int32_t* d_cyc_live;
     unsigned char* d_cyc;
-    unsigned char *h_cyc_stage, *d_cyc_stage;      // staging of the host variant's own inputs (plans, feedback, reset) and of reinit_out, grows on demand
-    unsigned char *h_eval_stage, *d_eval_stage;    // staging of mpc_evaluate_batch (inputs, then the five outputs), allocated by its first call, grows on demand
-    unsigned char *h_plan_stage, *d_plan_stage;    // staging of mpc_plan_inputs_batch and mpc_commands_batch, allocated by the first such call, grows on demand
 };
 
 // the pieces of the slot-state block
@@ -161,20 +162,6 @@ static hipError_t kernel_occupancy(bool f32, int model, const mpc::KernelChoice&
     return with_model(f32, model, [&](auto t, auto m) { return mpc::solve_occupancy<decltype(t), decltype(m)::value>(k, out); });
 }
 
-// Device staging of the host-pointer helpers: ONE allocation kept in the handle and carved into 256-byte aligned pieces (these calls sit in a B = 1 control
-// loop next to a sub-millisecond solve; a hipMalloc / hipFree pair per temporary per call cost more than the kernels they feed).  Grows on demand, freed by mpc_destroy.
-static hipError_t stage_carve(mpc_solver* s, const size_t* sz, int count, void** out) {
-    mpc::Packer total, p;
-    for (int i = 0; i < count; ++i) total.take(sz[i]);
-    Buf& b = s->bufs[BUF_STAGE];
-    if (total.off > b.bytes) {
-        if (s->d_stage) { (void)hipStreamSynchronize(s->stream); buf_free(b); }
-        if (const hipError_t er = buf_alloc(b, total.off)) return er;
-    }
-    for (int i = 0; i < count; ++i) out[i] = (char*)s->d_stage + p.take(sz[i]);
-    return hipSuccess;
-}
-
 // byte offsets of the three pieces of a record table of `entries` entries (256-byte aligned), and its size
 struct TabLayout {
     size_t o64, o32, odt, oev, bytes;
@@ -210,7 +197,8 @@ static void point_tables(mpc_solver* s) {
 
 // The handle's buffers: which of them its configuration gets at mpc_create (the others stay at 0 bytes), their sizes, the idle contents and whether mpc_reset
 // restores those -- the multipliers (forgotten) and the words that restore themselves unless a launch was aborted: the claim words of the blocks and the
-// candidate bookkeeping.  Parameter sets, grid sizes and via-points are kept by mpc_reset.
+// candidate bookkeeping.  Parameter sets, grid sizes and via-points are kept by mpc_reset.  Staging: the solve's four blocks at their full size here, the ONE
+// shared pair of every other host-pointer call (BUF_H_STAGE, BUF_D_STAGE) at 0 bytes until staged_call grows it.
 static void declare_buffers(mpc_solver* s) {
     const mpc_config& c = s->cfg;
     const size_t Bm = (size_t)s->max_batch, n = (size_t)c.n, slots = 8 * (size_t)s->n_gslots, dual = Bm * (size_t)s->dual_words * 8;
@@ -226,16 +214,11 @@ static void declare_buffers(mpc_solver* s) {
     s->bufs[BUF_TAB] = {(void**)&s->d_tab, TabLayout(c, 1).bytes, FILL_TAB0, false, false};      // replaced by a larger one when mpc_set_parameter_sets needs more entries
     s->bufs[BUF_SET_OF] = {(void**)&s->d_set_of, 0, FILL_NONE, false, false};                    // [max_batch], allocated by the first mpc_set_parameter_sets
     s->bufs[BUF_H_TAB] = {(void**)&s->h_tab, 0, FILL_NONE, false, true};
-    s->bufs[BUF_STAGE] = {(void**)&s->d_stage, 0, FILL_NONE, false, false};
     s->bufs[BUF_H_IN] = {(void**)&s->h_in, cap.in_bytes, FILL_NONE, false, true};
-    s->bufs[BUF_CYC_LIVE] = {(void**)&s->d_cyc_live, 0, 0, true, false};                        // the four of the controller cycle: allocated by the first mpc_controller_step_batch*
+    s->bufs[BUF_CYC_LIVE] = {(void**)&s->d_cyc_live, 0, 0, true, false};                        // the two of the controller cycle: allocated by the first mpc_controller_step_batch*
     s->bufs[BUF_CYC] = {(void**)&s->d_cyc, 0, 0, false, false};
-    s->bufs[BUF_CYC_HSTAGE] = {(void**)&s->h_cyc_stage, 0, FILL_NONE, false, true};
-    s->bufs[BUF_CYC_DSTAGE] = {(void**)&s->d_cyc_stage, 0, FILL_NONE, false, false};
-    s->bufs[BUF_EVAL_HSTAGE] = {(void**)&s->h_eval_stage, 0, FILL_NONE, false, true};       // the two of mpc_evaluate_batch: allocated by its first call
-    s->bufs[BUF_EVAL_DSTAGE] = {(void**)&s->d_eval_stage, 0, FILL_NONE, false, false};
-    s->bufs[BUF_PLAN_HSTAGE] = {(void**)&s->h_plan_stage, 0, FILL_NONE, false, true};       // the two of mpc_plan_inputs_batch / mpc_commands_batch: allocated by the first such call
-    s->bufs[BUF_PLAN_DSTAGE] = {(void**)&s->d_plan_stage, 0, FILL_NONE, false, false};
+    s->bufs[BUF_H_STAGE] = {(void**)&s->h_stage, 0, FILL_NONE, false, true};                    // the shared pair of staged_call: allocated by the first call that stages, grows on demand
+    s->bufs[BUF_D_STAGE] = {(void**)&s->d_stage, 0, FILL_NONE, false, false};
     add(&s->h_out, cap.out_bytes, FILL_NONE, false, true);
     add(&s->d_in, cap.in_bytes);
     add(&s->d_out, cap.out_bytes);
@@ -450,9 +433,58 @@ static hipError_t launch(const mpc_solver* s, bool f32, mpc::SolveLaunch a) {
     return with_model(f32, s->cfg.model, [&](auto t, auto m) { return mpc::launch_solve<decltype(t), decltype(m)::value>(a); });
 }
 
-extern "C" {
+// The refusals that depend on the per-instance state the handle carries, each stated once: 0, or the return code with mpc_last_error set.  `which`: the checks
+// that apply to the entry point, made in the order of the enum; `who`: the prefix of the message.
+enum { REF_MAX_BATCH = 1, REF_NGRID = 2, REF_NGRID_NO_HINT = 4, REF_VIA = 8, REF_SETS = 16, REF_OBSTACLES = 32 };
+static int refused(const mpc_solver* s, int32_t B, int which, const char* who, const mpc_obstacles* ob = nullptr) {
+    auto no = [who](int rc, const char* why, const char* hint = "") { snprintf(g_err, sizeof(g_err), "%s: %s%s", who, why, hint); return rc; };
+    if ((which & REF_MAX_BATCH) && B > s->max_batch) return no(MPC_EBATCH, "B exceeds max_batch");
+    if ((which & (REF_NGRID | REF_NGRID_NO_HINT)) && s->use_ngrid && B > s->ngrid_B)
+        return no(MPC_EBATCH, "B exceeds the batch the per-instance grid sizes were set for", (which & REF_NGRID) ? " (mpc_set_grid_sizes)" : "");
+    if ((which & REF_VIA) && s->P64.n_via > 0 && s->p_nvia == s->d_nvia && s->nvia_B > 0 && B > s->nvia_B)      // (borrowed device pointers: the caller's affair)
+        return no(MPC_EBATCH, "B exceeds the batch the via-points were set for (mpc_set_via_points)");
+    if ((which & REF_SETS) && s->p_set_of && B > s->sets_B) return no(MPC_EBATCH, "B exceeds the batch the parameter sets were given for (mpc_set_parameter_sets)");
+    if ((which & REF_OBSTACLES) && s->cfg.max_obstacles > 0 && (!ob || !ob->n_obstacles || !ob->n_vertices || !ob->vertices))
+        return no(MPC_EINVAL, "the solver was created with max_obstacles > 0 but no obstacles were passed");
+    return MPC_OK;
+}
 
-}  // extern "C"
+// A host-pointer call through the shared staging pair: the pieces laid out (mpc::stage_layout), the pair grown if they do not fit (the stream idle, the new block
+// first, then the old one freed), the sources copied into the pinned block, ONE host-to-device copy, run(dev) with the device address of every piece (NULL for
+// an absent one) -- it enqueues the device variant on the handle's stream and returns its code --, ONE device-to-host copy, the stream synchronised, the pinned
+// block copied into the destinations.  `direct`: the call takes its device block only and copies piece by piece between it and the caller's memory, as
+// mpc_costmap_to_obstacles and mpc_check_feasibility always have: with 4096 maps of 64 x 64 the pass through the pinned block costs them 0.14 .. 0.22 ms
+// (profiles/r15_capi_staging.md).  What HIP refuses is reported under `who`, out of memory as MPC_ENOMEM where `enomem` says that the entry point always has.
+template <typename Run>
+static int staged_call(mpc_solver* s, const char* who, bool enomem, bool direct, const mpc::StagePiece* pc, int count, Run run) {
+#define STAGE_TRY(call) do { const hipError_t e_ = (call); if (e_ != hipSuccess) { set_err(who, e_); return enomem && e_ == hipErrorOutOfMemory ? MPC_ENOMEM : MPC_EHIP; } } while (0)
+    hipStream_t q = s->stream;
+    const mpc::StageLayout L = mpc::stage_layout(pc, count);
+    for (Buf* bf : {&s->bufs[BUF_H_STAGE], &s->bufs[BUF_D_STAGE]})
+        if (L.bytes > bf->bytes && !(direct && bf->pinned)) { STAGE_TRY(hipStreamSynchronize(q)); STAGE_TRY(buf_alloc(*bf, L.bytes)); }
+    void* dev[mpc::StageLayout::MAX_PIECES];
+    for (int i = 0; i < count; ++i) {
+        dev[i] = L.at(s->d_stage, i);
+        if (!L.present[i] || pc[i].dir == mpc::STAGE_OUT) continue;
+        if (direct) STAGE_TRY(hipMemcpyAsync(dev[i], pc[i].src, pc[i].bytes, hipMemcpyHostToDevice, q));
+        else memcpy(L.at(s->h_stage, i), pc[i].src, pc[i].bytes);
+    }
+    if (!direct && L.h2d_bytes) STAGE_TRY(hipMemcpyAsync(s->d_stage, s->h_stage, L.h2d_bytes, hipMemcpyHostToDevice, q));
+    const int rc = run(dev);
+    if (rc != MPC_OK) return rc;
+    if (!direct && L.d2h_bytes) STAGE_TRY(hipMemcpyAsync(s->h_stage + L.d2h_begin, s->d_stage + L.d2h_begin, L.d2h_bytes, hipMemcpyDeviceToHost, q));
+    for (int i = 0; direct && i < count; ++i)
+        if (L.present[i] && pc[i].dir != mpc::STAGE_IN) STAGE_TRY(hipMemcpyAsync(pc[i].dst, dev[i], pc[i].bytes, hipMemcpyDeviceToHost, q));
+    STAGE_TRY(hipStreamSynchronize(q));
+    for (int i = 0; !direct && i < count; ++i)
+        if (L.present[i] && pc[i].dir != mpc::STAGE_IN) memcpy(pc[i].dst, L.at(s->h_stage, i), pc[i].bytes);
+    return MPC_OK;
+#undef STAGE_TRY
+}
+// the pieces by direction; an in / out array is its own source and destination
+static mpc::StagePiece stage_in(const void* p, size_t bytes) { return {p, nullptr, bytes, mpc::STAGE_IN}; }
+static mpc::StagePiece stage_out(void* p, size_t bytes) { return {nullptr, p, bytes, mpc::STAGE_OUT}; }
+static mpc::StagePiece stage_inout(void* p, size_t bytes) { return {p, p, bytes, mpc::STAGE_INOUT}; }
 
 // mpc_solve_batch_device with the per-instance start mode of the controller cycle (d_init_mode: NULL everywhere else)
 static int solve_device(mpc_solver* s, int32_t B, const double* d_x0, const double* d_xf, const double* d_u_prev,
@@ -462,21 +494,12 @@ static int solve_device(mpc_solver* s, int32_t B, const double* d_x0, const doub
     g_err[0] = 0;
     if (!s || !d_x0 || !d_xf || !d_x_out || !d_u_out || !d_dt_out) { set_err("mpc_solve_batch_device: null argument"); return MPC_EINVAL; }
     if (B <= 0) return MPC_OK;
-    if (B > s->max_batch) { set_err("mpc_solve_batch_device: B exceeds max_batch"); return MPC_EBATCH; }
+    if (const int rc = refused(s, B, REF_MAX_BATCH, "mpc_solve_batch_device")) return rc;
     if ((d_x_init != nullptr) != (d_u_init != nullptr) || (d_x_init != nullptr) != (d_dt_init != nullptr)) {
         set_err("mpc_solve_batch: x_init, u_init and dt_init must be given together (all three or none)"); return MPC_EINVAL; }
-    if (s->use_ngrid && B > s->ngrid_B) { set_err("mpc_solve_batch: B exceeds the batch the per-instance grid sizes were set for (mpc_set_grid_sizes)"); return MPC_EBATCH; }
-    if (s->P64.n_via > 0 && s->p_nvia == s->d_nvia && s->nvia_B > 0 && B > s->nvia_B) {
-        set_err("mpc_solve_batch: B exceeds the batch the via-points were set for (mpc_set_via_points)"); return MPC_EBATCH; }
-    if (s->p_set_of && B > s->sets_B) { set_err("mpc_solve_batch: B exceeds the batch the parameter sets were given for (mpc_set_parameter_sets)"); return MPC_EBATCH; }
-    mpc_obstacles ob = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (s->cfg.max_obstacles > 0) {
-        if (!d_obstacles || !d_obstacles->n_obstacles || !d_obstacles->n_vertices || !d_obstacles->vertices) {
-            set_err("mpc_solve_batch_device: the solver was created with max_obstacles > 0 but no obstacles were passed");
-            return MPC_EINVAL;
-        }
-        ob = *d_obstacles;
-    }
+    if (const int rc = refused(s, B, REF_NGRID | REF_VIA | REF_SETS, "mpc_solve_batch")) return rc;
+    if (const int rc = refused(s, B, REF_OBSTACLES, "mpc_solve_batch_device", d_obstacles)) return rc;
+    const mpc_obstacles ob = s->cfg.max_obstacles > 0 ? *d_obstacles : mpc_obstacles{nullptr, nullptr, nullptr, nullptr, nullptr};
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipEventRecord(s->ev0, s->stream));
     mpc::SolveLaunch a{};
@@ -534,7 +557,7 @@ int mpc_last_candidates(mpc_solver* s, int32_t B, int32_t* winner, int32_t* iter
     g_err[0] = 0;
     if (!s) return MPC_EINVAL;
     if (B <= 0) return MPC_OK;
-    if (B > s->max_batch) { set_err("mpc_last_candidates: B exceeds max_batch"); return MPC_EBATCH; }
+    if (const int rc = refused(s, B, REF_MAX_BATCH, "mpc_last_candidates")) return rc;
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipStreamSynchronize(s->stream));
     if (s->P32.n_cand > 1) {
@@ -558,7 +581,7 @@ int mpc_last_rows_dropped(mpc_solver* s, int32_t B, int32_t* rows_dropped) {
     g_err[0] = 0;
     if (!s || !rows_dropped) return MPC_EINVAL;
     if (B <= 0) return MPC_OK;
-    if (B > s->max_batch) { set_err("mpc_last_rows_dropped: B exceeds max_batch"); return MPC_EBATCH; }
+    if (const int rc = refused(s, B, REF_MAX_BATCH, "mpc_last_rows_dropped")) return rc;
     if (!s->d_rows_dropped) { memset(rows_dropped, 0, (size_t)B * 4); return MPC_OK; }
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipStreamSynchronize(s->stream));
@@ -605,7 +628,7 @@ int mpc_costmap_to_obstacles_device(mpc_solver* s, int32_t B, const uint8_t* d_c
     if (s->cfg.max_obstacles <= 0) { set_err("mpc_costmap_to_obstacles_device: the solver was created with max_obstacles = 0"); return MPC_EINVAL; }
     if (size_x < 1 || size_y < 1 || !(resolution > 0)) { set_err("mpc_costmap_to_obstacles_device: bad costmap geometry"); return MPC_EINVAL; }
     if (B <= 0) return MPC_OK;
-    if (B > s->max_batch) { set_err("mpc_costmap_to_obstacles_device: B exceeds max_batch"); return MPC_EBATCH; }
+    if (const int rc = refused(s, B, REF_MAX_BATCH, "mpc_costmap_to_obstacles_device")) return rc;
     HIP_TRY(hipSetDevice(s->device));
     mpc::CostmapArgs a;
     a.cost = d_cost; a.origin = d_origin; a.pose = d_robot_pose;
@@ -628,25 +651,15 @@ int mpc_costmap_to_obstacles(mpc_solver* s, int32_t B, const uint8_t* cost, int3
     if (s->cfg.max_obstacles <= 0 || size_x < 1 || size_y < 1) { set_err("mpc_costmap_to_obstacles: bad argument"); return MPC_EINVAL; }
     HIP_TRY(hipSetDevice(s->device));
     const size_t O = s->cfg.max_obstacles, V = s->cfg.max_vertices > 0 ? s->cfg.max_vertices : 1, nb = (size_t)B;
-    const size_t sz[7] = {nb * size_x * size_y, nb * 2 * 8, nb * 3 * 8, nb * 4, nb * O * 4, nb * O * V * 2 * 8, nb * 4};
-    void* d[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    hipError_t er = stage_carve(s, sz, 7, d);
-    int rc = MPC_OK;
-    if (er == hipSuccess) er = hipMemcpyAsync(d[0], cost, sz[0], hipMemcpyHostToDevice, s->stream);
-    if (er == hipSuccess) er = hipMemcpyAsync(d[1], origin, sz[1], hipMemcpyHostToDevice, s->stream);
-    if (er == hipSuccess) er = hipMemcpyAsync(d[2], robot_pose, sz[2], hipMemcpyHostToDevice, s->stream);
-    if (er == hipSuccess) er = hipMemsetAsync(d[4], 0, sz[4], s->stream);
-    if (er == hipSuccess) er = hipMemsetAsync(d[5], 0, sz[5], s->stream);
-    if (er == hipSuccess)
-        rc = mpc_costmap_to_obstacles_device(s, B, (const uint8_t*)d[0], size_x, size_y, resolution, (const double*)d[1], (const double*)d[2], behind_robot_dist,
-                                             (int32_t*)d[3], (int32_t*)d[4], (double*)d[5], (int32_t*)d[6]);
-    if (er == hipSuccess && rc == MPC_OK) er = hipMemcpyAsync(n_obstacles, d[3], sz[3], hipMemcpyDeviceToHost, s->stream);
-    if (er == hipSuccess && rc == MPC_OK) er = hipMemcpyAsync(n_vertices, d[4], sz[4], hipMemcpyDeviceToHost, s->stream);
-    if (er == hipSuccess && rc == MPC_OK) er = hipMemcpyAsync(vertices, d[5], sz[5], hipMemcpyDeviceToHost, s->stream);
-    if (er == hipSuccess && rc == MPC_OK && dropped) er = hipMemcpyAsync(dropped, d[6], sz[6], hipMemcpyDeviceToHost, s->stream);
-    if (er == hipSuccess) er = hipStreamSynchronize(s->stream);
-    if (er != hipSuccess) { set_err("mpc_costmap_to_obstacles", er); return er == hipErrorOutOfMemory ? MPC_ENOMEM : MPC_EHIP; }
-    return rc;
+    const mpc::StagePiece pc[7] = {stage_in(cost, nb * size_x * size_y), stage_in(origin, nb * 2 * 8), stage_in(robot_pose, nb * 3 * 8), stage_out(n_obstacles, nb * 4), stage_out(n_vertices, nb * O * 4),
+                                   stage_out(vertices, nb * O * V * 2 * 8), stage_out(dropped, nb * 4)};
+    return staged_call(s, "mpc_costmap_to_obstacles", true, true, pc, 7, [&](void** d) -> int {
+        // the kernel writes the vertices it finds: the rest is cleared on the device, behind the copy of the inputs
+        HIP_TRY(hipMemsetAsync(d[4], 0, pc[4].bytes, s->stream));
+        HIP_TRY(hipMemsetAsync(d[5], 0, pc[5].bytes, s->stream));
+        return mpc_costmap_to_obstacles_device(s, B, (const uint8_t*)d[0], size_x, size_y, resolution, (const double*)d[1], (const double*)d[2], behind_robot_dist,
+                                               (int32_t*)d[3], (int32_t*)d[4], (double*)d[5], (int32_t*)d[6]);
+    });
 }
 
 int mpc_grid_update_device(mpc_solver* s, int32_t B, const double* d_x0_new, double* d_x, double* d_u, double* d_dt,
@@ -654,9 +667,7 @@ int mpc_grid_update_device(mpc_solver* s, int32_t B, const double* d_x0_new, dou
     g_err[0] = 0;
     if (!s || !d_x || !d_u || !d_dt) { set_err("mpc_grid_update_device: null argument"); return MPC_EINVAL; }
     if (B <= 0) return MPC_OK;
-    if (B > s->max_batch) { set_err("mpc_grid_update_device: B exceeds max_batch"); return MPC_EBATCH; }
-    if (s->use_ngrid && B > s->ngrid_B) { set_err("mpc_grid_update_device: B exceeds the batch the per-instance grid sizes were set for (mpc_set_grid_sizes)"); return MPC_EBATCH; }
-    if (s->p_set_of && B > s->sets_B) { set_err("mpc_grid_update_device: B exceeds the batch the parameter sets were given for (mpc_set_parameter_sets)"); return MPC_EBATCH; }
+    if (const int rc = refused(s, B, REF_MAX_BATCH | REF_NGRID | REF_SETS, "mpc_grid_update_device")) return rc;
     HIP_TRY(hipSetDevice(s->device));
     mpc::GridUpdateArgs a;
     memset(&a, 0, sizeof(a));
@@ -688,7 +699,7 @@ int mpc_get_grid_sizes(mpc_solver* s, int32_t B, int32_t* n_grid) {
     g_err[0] = 0;
     if (!s || !n_grid) return MPC_EINVAL;
     if (B <= 0) return MPC_OK;
-    if (B > s->max_batch) { set_err("mpc_get_grid_sizes: B exceeds max_batch"); return MPC_EBATCH; }
+    if (const int rc = refused(s, B, REF_MAX_BATCH, "mpc_get_grid_sizes")) return rc;
     if (!s->use_ngrid) { for (int b = 0; b < B; ++b) n_grid[b] = s->cfg.n; return MPC_OK; }
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipStreamSynchronize(s->stream));
@@ -705,8 +716,7 @@ int mpc_check_feasibility_device(mpc_solver* s, int32_t B, const double* d_x, co
         !(inscribed_radius > 0) || !(min_resolution_collision_check_angular > 0)) {
         set_err("mpc_check_feasibility_device: bad costmap geometry, footprint (<= 32 points) or resolution parameters"); return MPC_EINVAL; }
     if (B <= 0) return MPC_OK;
-    if (B > s->max_batch) { set_err("mpc_check_feasibility_device: B exceeds max_batch"); return MPC_EBATCH; }
-    if (s->use_ngrid && B > s->ngrid_B) { set_err("mpc_check_feasibility_device: B exceeds the batch the per-instance grid sizes were set for"); return MPC_EBATCH; }
+    if (const int rc = refused(s, B, REF_MAX_BATCH | REF_NGRID_NO_HINT, "mpc_check_feasibility_device")) return rc;
     HIP_TRY(hipSetDevice(s->device));
     mpc::FeasArgs a;
     memset(&a, 0, sizeof(a));
@@ -730,20 +740,11 @@ int mpc_check_feasibility(mpc_solver* s, int32_t B, const double* x, const uint8
     if (B > s->max_batch || size_x < 1 || size_y < 1) { set_err("mpc_check_feasibility: bad argument"); return MPC_EINVAL; }
     HIP_TRY(hipSetDevice(s->device));
     const size_t nb = B, n = s->cfg.n;
-    const size_t sz[4] = {nb * n * 3 * 8, nb * size_x * size_y, nb * 2 * 8, nb * 4};
-    void* d[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipError_t er = stage_carve(s, sz, 4, d);
-    int rc = MPC_OK;
-    if (er == hipSuccess) er = hipMemcpyAsync(d[0], x, sz[0], hipMemcpyHostToDevice, s->stream);
-    if (er == hipSuccess) er = hipMemcpyAsync(d[1], cost, sz[1], hipMemcpyHostToDevice, s->stream);
-    if (er == hipSuccess) er = hipMemcpyAsync(d[2], origin, sz[2], hipMemcpyHostToDevice, s->stream);
-    if (er == hipSuccess)
-        rc = mpc_check_feasibility_device(s, B, (const double*)d[0], (const uint8_t*)d[1], size_x, size_y, resolution, (const double*)d[2], footprint_spec, n_spec,
-                                          inscribed_radius, min_resolution_collision_check_angular, look_ahead_idx, (int32_t*)d[3]);
-    if (er == hipSuccess && rc == MPC_OK) er = hipMemcpyAsync(feasible, d[3], sz[3], hipMemcpyDeviceToHost, s->stream);
-    if (er == hipSuccess) er = hipStreamSynchronize(s->stream);
-    if (er != hipSuccess) { set_err("mpc_check_feasibility", er); return er == hipErrorOutOfMemory ? MPC_ENOMEM : MPC_EHIP; }
-    return rc;
+    const mpc::StagePiece pc[4] = {stage_in(x, nb * n * 3 * 8), stage_in(cost, nb * size_x * size_y), stage_in(origin, nb * 2 * 8), stage_out(feasible, nb * 4)};
+    return staged_call(s, "mpc_check_feasibility", true, true, pc, 4, [&](void** d) {
+        return mpc_check_feasibility_device(s, B, (const double*)d[0], (const uint8_t*)d[1], size_x, size_y, resolution, (const double*)d[2], footprint_spec, n_spec,
+                                            inscribed_radius, min_resolution_collision_check_angular, look_ahead_idx, (int32_t*)d[3]);
+    });
 }
 
 int mpc_set_grid_sizes(mpc_solver* s, const int32_t* n_grid, int32_t B) {
@@ -842,6 +843,47 @@ int mpc_last_kernel_ms(mpc_solver* s, float* ms) {
     return MPC_OK;
 }
 
+// The solve's arrays of a host-pointer call in the four blocks of mpc_create (mpc::step_pieces), for mpc_solve_batch / mpc_step_batch and for the solve inside
+// mpc_controller_step_batch: pack() copies every input the caller gave into the pinned block and enqueues the ONE host-to-device copy, fetch() enqueues the ONE
+// device-to-host copy of the outputs (with the grid sizes behind them), unpack() hands them out once the stream has been synchronised.
+typedef mpc::StepPieces SP;
+struct SolveStage {
+    SP pc;
+    const void* d[SP::N_IN];      // device address of every input piece, NULL for one this call does not have
+    mpc_obstacles dob;
+    const double* at(int i) const { return (const double*)d[i]; }
+    double* out(const mpc_solver* s, int i) const { return (double*)(s->d_out + pc.off[i]); }      // device address of an output piece
+    int32_t* iout(const mpc_solver* s, int i) const { return (int32_t*)(s->d_out + pc.off[i]); }
+    int pack(mpc_solver* s, const char* who, int32_t B, const double* x0, const double* xf, const double* u_prev, const double* dt_prev, const double* x_init, const double* u_init,
+             const double* dt_init, const mpc_obstacles* ob) {
+        if (const int rc = refused(s, B, REF_OBSTACLES, who, ob)) return rc;
+        const bool obst = s->cfg.max_obstacles > 0;
+        const void* src[SP::N_IN] = {x0, xf, u_prev, dt_prev, x_init, u_init, dt_init, obst ? ob->n_obstacles : nullptr, obst ? ob->n_vertices : nullptr,
+                                     obst ? ob->vertices : nullptr, obst ? ob->radius : nullptr, obst ? ob->velocity : nullptr};
+        pc = mpc::step_pieces(s->cfg, (size_t)B, u_prev != nullptr, dt_prev != nullptr, x_init != nullptr, src[SP::RADIUS] != nullptr, src[SP::VELOCITY] != nullptr);
+        if (pc.in_bytes > s->bufs[BUF_H_IN].bytes) { snprintf(g_err, sizeof(g_err), "%s: internal staging overflow", who); return MPC_EINVAL; }
+        for (int i = 0; i < SP::N_IN; ++i) {      // (a piece the list always has and this caller does not give: x0 and xf of the controller cycle, which computes them)
+            d[i] = pc.bytes[i] && src[i] ? s->d_in + pc.off[i] : nullptr;
+            if (d[i]) memcpy(s->h_in + pc.off[i], src[i], pc.bytes[i]);
+        }
+        dob = {(const int32_t*)d[SP::N_OBSTACLES], (const int32_t*)d[SP::N_VERTICES], (const double*)d[SP::VERTICES], (const double*)d[SP::RADIUS], (const double*)d[SP::VELOCITY]};
+        HIP_TRY(hipMemcpyAsync(s->d_in, s->h_in, pc.in_bytes, hipMemcpyHostToDevice, s->stream));
+        return MPC_OK;
+    }
+    int fetch(mpc_solver* s, bool n_grid) const {
+        if (n_grid) HIP_TRY(hipMemcpyAsync(s->d_out + pc.off[SP::N_GRID], s->d_ngrid, pc.bytes[SP::N_GRID], hipMemcpyDeviceToDevice, s->stream));
+        HIP_TRY(hipMemcpyAsync(s->h_out, s->d_out, pc.out_bytes, hipMemcpyDeviceToHost, s->stream));
+        return MPC_OK;
+    }
+    void unpack(const mpc_solver* s, double* x_out, double* u_out, double* dt_out, int32_t* status, int32_t* iters, int32_t* n_grid_out) const {
+        void* dst[5] = {x_out, u_out, dt_out, status, iters};      // (status and iters may be NULL)
+        for (int i = 0; i < 5; ++i) if (dst[i]) memcpy(dst[i], s->h_out + pc.off[SP::X_OUT + i], pc.bytes[SP::X_OUT + i]);
+        if (!n_grid_out) return;
+        if (s->use_ngrid) memcpy(n_grid_out, s->h_out + pc.off[SP::N_GRID], pc.bytes[SP::N_GRID]);
+        else for (size_t i = 0; i < pc.bytes[SP::N_GRID] / 4; ++i) n_grid_out[i] = s->cfg.n;
+    }
+};
+
 // host-pointer entry of one control cycle: `outer` x (grid update -> solve) without a host round trip in between
 static int step_host(mpc_solver* s, int32_t B, const double* x0, const double* xf, const double* u_prev, const double* dt_prev,
                      const double* x_init, const double* u_init, const double* dt_init, const mpc_obstacles* obstacles,
@@ -850,43 +892,18 @@ static int step_host(mpc_solver* s, int32_t B, const double* x0, const double* x
     g_err[0] = 0;
     if (!s || !x0 || !xf || !x_out || !u_out || !dt_out) { set_err("mpc_solve_batch / mpc_step_batch: null argument"); return MPC_EINVAL; }
     if (B <= 0) return MPC_OK;
-    if (B > s->max_batch) { set_err("mpc_solve_batch: B exceeds max_batch"); return MPC_EBATCH; }
+    if (const int rc = refused(s, B, REF_MAX_BATCH, "mpc_solve_batch")) return rc;
     if ((x_init != nullptr) != (u_init != nullptr) || (x_init != nullptr) != (dt_init != nullptr)) {
         set_err("mpc_solve_batch: x_init, u_init and dt_init must be given together (all three or none)"); return MPC_EINVAL; }
     HIP_TRY(hipSetDevice(s->device));
-    const size_t b = B;
-    hipStream_t q = s->stream;
-    const bool warm = x_init != nullptr;
-    if (s->cfg.max_obstacles > 0 && (!obstacles || !obstacles->n_obstacles || !obstacles->n_vertices || !obstacles->vertices)) {
-        set_err("mpc_solve_batch: the solver was created with max_obstacles > 0 but no obstacles were passed");
-        return MPC_EINVAL;
-    }
-    // ---- pack every input into the pinned block (256-byte aligned pieces), ONE host-to-device copy
-    typedef mpc::StepPieces SP;
-    const bool obst = s->cfg.max_obstacles > 0;
-    const void* src[SP::N_IN] = {x0, xf, u_prev, dt_prev, x_init, u_init, dt_init, obst ? obstacles->n_obstacles : nullptr, obst ? obstacles->n_vertices : nullptr,
-                                 obst ? obstacles->vertices : nullptr, obst ? obstacles->radius : nullptr, obst ? obstacles->velocity : nullptr};
-    const SP pc = mpc::step_pieces(s->cfg, b, u_prev != nullptr, dt_prev != nullptr, warm, src[SP::RADIUS] != nullptr, src[SP::VELOCITY] != nullptr);
-    if (pc.in_bytes > s->bufs[BUF_H_IN].bytes) { set_err("mpc_solve_batch: internal staging overflow"); return MPC_EINVAL; }
-    const void* d[SP::N_IN];      // device address of every input piece, NULL for one this call does not have
-    for (int i = 0; i < SP::N_IN; ++i) {
-        d[i] = pc.bytes[i] ? s->d_in + pc.off[i] : nullptr;
-        if (pc.bytes[i]) memcpy(s->h_in + pc.off[i], src[i], pc.bytes[i]);
-    }
-    const mpc_obstacles dob = {(const int32_t*)d[SP::N_OBSTACLES], (const int32_t*)d[SP::N_VERTICES], (const double*)d[SP::VERTICES], (const double*)d[SP::RADIUS], (const double*)d[SP::VELOCITY]};
-    HIP_TRY(hipMemcpyAsync(s->d_in, s->h_in, pc.in_bytes, hipMemcpyHostToDevice, q));
-    // ---- outputs: one device block, ONE device-to-host copy
-    const size_t o_x = pc.off[SP::X_OUT], o_u = pc.off[SP::U_OUT], o_dt = pc.off[SP::DT_OUT], o_st = pc.off[SP::STATUS], o_it = pc.off[SP::ITERS], o_ng = pc.off[SP::N_GRID];
-    int rc = mpc_step_batch_device(s, B, (const double*)d[SP::X0], (const double*)d[SP::XF], (const double*)d[SP::U_PREV], (const double*)d[SP::DT_PREV], (const double*)d[SP::X_INIT],
-                                   (const double*)d[SP::U_INIT], (const double*)d[SP::DT_INIT], &dob, outer, adapt, n_min, n_max, dt_hyst_ratio, (double*)(s->d_out + o_x),
-                                   (double*)(s->d_out + o_u), (double*)(s->d_out + o_dt), (int32_t*)(s->d_out + o_st), (int32_t*)(s->d_out + o_it));
+    SolveStage st;
+    if (const int rc = st.pack(s, "mpc_solve_batch", B, x0, xf, u_prev, dt_prev, x_init, u_init, dt_init, obstacles)) return rc;
+    const int rc = mpc_step_batch_device(s, B, st.at(SP::X0), st.at(SP::XF), st.at(SP::U_PREV), st.at(SP::DT_PREV), st.at(SP::X_INIT), st.at(SP::U_INIT), st.at(SP::DT_INIT), &st.dob,
+                                         outer, adapt, n_min, n_max, dt_hyst_ratio, st.out(s, SP::X_OUT), st.out(s, SP::U_OUT), st.out(s, SP::DT_OUT), st.iout(s, SP::STATUS), st.iout(s, SP::ITERS));
     if (rc != MPC_OK) return rc;
-    if (n_grid_out && s->use_ngrid) HIP_TRY(hipMemcpyAsync(s->d_out + o_ng, s->d_ngrid, b * 4, hipMemcpyDeviceToDevice, q));
-    HIP_TRY(hipMemcpyAsync(s->h_out, s->d_out, pc.out_bytes, hipMemcpyDeviceToHost, q));
-    HIP_TRY(hipStreamSynchronize(q));
-    void* dst[5] = {x_out, u_out, dt_out, status, iters};      // (status and iters may be NULL)
-    for (int i = 0; i < 5; ++i) if (dst[i]) memcpy(dst[i], s->h_out + pc.off[SP::X_OUT + i], pc.bytes[SP::X_OUT + i]);
-    if (n_grid_out) { if (s->use_ngrid) memcpy(n_grid_out, s->h_out + o_ng, b * 4); else for (size_t i = 0; i < b; ++i) n_grid_out[i] = s->cfg.n; }
+    if (const int rc2 = st.fetch(s, n_grid_out && s->use_ngrid)) return rc2;
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    st.unpack(s, x_out, u_out, dt_out, status, iters, n_grid_out);
     return MPC_OK;
 }
 
@@ -939,12 +956,7 @@ int mpc_controller_step_batch_device(mpc_solver* s, int32_t B, const mpc_cycle_p
     if (!s || !d_plan || !d_n_plan || !d_x_out || !d_u_out || !d_dt_out || plan_stride < 2) { set_err("mpc_controller_step_batch_device: null argument or plan_stride < 2"); return MPC_EINVAL; }
     if (const char* why = cycle_params_error(s, p, d_x_feedback, d_feedback_age)) { set_err(why); return MPC_EINVAL; }
     if (B <= 0) return MPC_OK;
-    if (B > s->max_batch) { set_err("mpc_controller_step_batch: B exceeds max_batch"); return MPC_EBATCH; }
-    if (s->P64.n_via > 0 && s->p_nvia == s->d_nvia && s->nvia_B > 0 && B > s->nvia_B) {
-        set_err("mpc_controller_step_batch: B exceeds the batch the via-points were set for (mpc_set_via_points)"); return MPC_EBATCH; }
-    if (s->p_set_of && B > s->sets_B) { set_err("mpc_controller_step_batch: B exceeds the batch the parameter sets were given for (mpc_set_parameter_sets)"); return MPC_EBATCH; }
-    if (s->cfg.max_obstacles > 0 && (!d_obstacles || !d_obstacles->n_obstacles || !d_obstacles->n_vertices || !d_obstacles->vertices)) {
-        set_err("mpc_controller_step_batch: the solver was created with max_obstacles > 0 but no obstacles were passed"); return MPC_EINVAL; }
+    if (const int rc = refused(s, B, REF_MAX_BATCH | REF_VIA | REF_SETS | REF_OBSTACLES, "mpc_controller_step_batch", d_obstacles)) return rc;
     HIP_TRY(hipSetDevice(s->device));
     if (const int rc = cycle_state(s)) return rc;
     s->use_ngrid = 1; s->ngrid_B = s->max_batch;      // the grid sizes belong to the controller from here on (never uninitialised: mpc_create filled them with cfg.n)
@@ -993,61 +1005,31 @@ int mpc_controller_step_batch(mpc_solver* s, int32_t B, const mpc_cycle_params* 
     if (!s || !plan || !n_plan || !x_out || !u_out || !dt_out || plan_stride < 2) { set_err("mpc_controller_step_batch: null argument or plan_stride < 2"); return MPC_EINVAL; }
     if (const char* why = cycle_params_error(s, p, x_feedback, feedback_age)) { set_err(why); return MPC_EINVAL; }
     if (B <= 0) return MPC_OK;
-    if (B > s->max_batch) { set_err("mpc_controller_step_batch: B exceeds max_batch"); return MPC_EBATCH; }
+    if (const int rc = refused(s, B, REF_MAX_BATCH, "mpc_controller_step_batch")) return rc;
     for (int b = 0; b < B; ++b)
         if (n_plan[b] < 2 || n_plan[b] > plan_stride) { snprintf(g_err, sizeof(g_err), "mpc_controller_step_batch: n_plan[%d] = %d is not in [2, plan_stride]", b, n_plan[b]); return MPC_EINVAL; }
-    const bool obst = s->cfg.max_obstacles > 0;
-    if (obst && (!obstacles || !obstacles->n_obstacles || !obstacles->n_vertices || !obstacles->vertices)) {
-        set_err("mpc_controller_step_batch: the solver was created with max_obstacles > 0 but no obstacles were passed"); return MPC_EINVAL; }
+    if (const int rc = refused(s, B, REF_OBSTACLES, "mpc_controller_step_batch", obstacles)) return rc;
     HIP_TRY(hipSetDevice(s->device));
-    hipStream_t q = s->stream;
+    // the cycle's own inputs (plans, feedback, reset) and reinit_out through the shared pair; u_prev / dt_prev / obstacles and the solve's outputs through the blocks
+    // of mpc_solve_batch
     const size_t nb = (size_t)B;
-    // ---- the cycle's own inputs (plans, feedback, reset) and reinit_out through a staging pair of their own; u_prev / dt_prev / obstacles and the solve's outputs
-    // through the blocks of mpc_solve_batch (mpc::step_pieces)
-    mpc::Packer pk;
-    const size_t sz[6] = {nb * (size_t)plan_stride * 24, nb * 4, x_feedback ? nb * 24 : 0, feedback_age ? nb * 8 : 0, reset ? nb * 4 : 0, nb * 4};
-    const void* src[5] = {plan, n_plan, x_feedback, feedback_age, reset};
-    size_t off[6];
-    for (int i = 0; i < 6; ++i) off[i] = pk.take(sz[i]);
-    const size_t in_bytes = off[5];      // (the last piece is reinit_out: it only comes back)
-    for (Buf* bf : {&s->bufs[BUF_CYC_HSTAGE], &s->bufs[BUF_CYC_DSTAGE]})
-        if (pk.off > bf->bytes) { HIP_TRY(hipStreamSynchronize(q)); HIP_TRY(buf_alloc(*bf, pk.off)); }
-    for (int i = 0; i < 5; ++i) if (sz[i]) memcpy(s->h_cyc_stage + off[i], src[i], sz[i]);
-    auto dv = [&](int i) -> void* { return sz[i] ? (void*)(s->d_cyc_stage + off[i]) : nullptr; };
-    typedef mpc::StepPieces SP;
-    const void* ssrc[SP::N_IN] = {nullptr, nullptr, u_prev, dt_prev, nullptr, nullptr, nullptr, obst ? obstacles->n_obstacles : nullptr, obst ? obstacles->n_vertices : nullptr,
-                                  obst ? obstacles->vertices : nullptr, obst ? obstacles->radius : nullptr, obst ? obstacles->velocity : nullptr};
-    const SP pc = mpc::step_pieces(s->cfg, nb, u_prev != nullptr, dt_prev != nullptr, false, ssrc[SP::RADIUS] != nullptr, ssrc[SP::VELOCITY] != nullptr);
-    if (pc.in_bytes > s->bufs[BUF_H_IN].bytes) { set_err("mpc_controller_step_batch: internal staging overflow"); return MPC_EINVAL; }
-    const void* d[SP::N_IN];
-    for (int i = 0; i < SP::N_IN; ++i) {
-        d[i] = pc.bytes[i] && ssrc[i] ? s->d_in + pc.off[i] : nullptr;
-        if (pc.bytes[i] && ssrc[i]) memcpy(s->h_in + pc.off[i], ssrc[i], pc.bytes[i]);
-    }
-    const mpc_obstacles dob = {(const int32_t*)d[SP::N_OBSTACLES], (const int32_t*)d[SP::N_VERTICES], (const double*)d[SP::VERTICES], (const double*)d[SP::RADIUS], (const double*)d[SP::VELOCITY]};
-    HIP_TRY(hipMemcpyAsync(s->d_cyc_stage, s->h_cyc_stage, in_bytes, hipMemcpyHostToDevice, q));
-    HIP_TRY(hipMemcpyAsync(s->d_in, s->h_in, pc.in_bytes, hipMemcpyHostToDevice, q));
-    const size_t o_x = pc.off[SP::X_OUT], o_u = pc.off[SP::U_OUT], o_dt = pc.off[SP::DT_OUT], o_st = pc.off[SP::STATUS], o_it = pc.off[SP::ITERS], o_ng = pc.off[SP::N_GRID];
-    const int rc = mpc_controller_step_batch_device(s, B, p, (const double*)dv(0), (const int32_t*)dv(1), plan_stride, (const double*)dv(2), (const double*)dv(3), (const int32_t*)dv(4),
-                                                    (const double*)d[SP::U_PREV], (const double*)d[SP::DT_PREV], &dob, (double*)(s->d_out + o_x), (double*)(s->d_out + o_u),
-                                                    (double*)(s->d_out + o_dt), (int32_t*)(s->d_out + o_st), (int32_t*)(s->d_out + o_it), (int32_t*)dv(5));
-    if (rc != MPC_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(s->d_out + o_ng, s->d_ngrid, nb * 4, hipMemcpyDeviceToDevice, q));
-    HIP_TRY(hipMemcpyAsync(s->h_out, s->d_out, pc.out_bytes, hipMemcpyDeviceToHost, q));
-    HIP_TRY(hipMemcpyAsync(s->h_cyc_stage + off[5], s->d_cyc_stage + off[5], sz[5], hipMemcpyDeviceToHost, q));
-    HIP_TRY(hipStreamSynchronize(q));
-    void* dst[5] = {x_out, u_out, dt_out, status, iters};      // (status and iters may be NULL)
-    for (int i = 0; i < 5; ++i) if (dst[i]) memcpy(dst[i], s->h_out + pc.off[SP::X_OUT + i], pc.bytes[SP::X_OUT + i]);
-    if (n_grid_out) memcpy(n_grid_out, s->h_out + o_ng, nb * 4);
-    if (reinit_out) memcpy(reinit_out, s->h_cyc_stage + off[5], nb * 4);
-    return MPC_OK;
+    const mpc::StagePiece pc[6] = {stage_in(plan, nb * (size_t)plan_stride * 24), stage_in(n_plan, nb * 4), stage_in(x_feedback, nb * 24), stage_in(feedback_age, nb * 8), stage_in(reset, nb * 4), stage_out(reinit_out, nb * 4)};
+    SolveStage st;
+    const int rc = staged_call(s, "mpc_controller_step_batch", false, false, pc, 6, [&](void** d) -> int {
+        if (const int rp = st.pack(s, "mpc_controller_step_batch", B, nullptr, nullptr, u_prev, dt_prev, nullptr, nullptr, nullptr, obstacles)) return rp;
+        const int rd = mpc_controller_step_batch_device(s, B, p, (const double*)d[0], (const int32_t*)d[1], plan_stride, (const double*)d[2], (const double*)d[3], (const int32_t*)d[4],
+                                                        st.at(SP::U_PREV), st.at(SP::DT_PREV), &st.dob, st.out(s, SP::X_OUT), st.out(s, SP::U_OUT), st.out(s, SP::DT_OUT), st.iout(s, SP::STATUS), st.iout(s, SP::ITERS), (int32_t*)d[5]);
+        return rd != MPC_OK ? rd : st.fetch(s, true);
+    });
+    if (rc == MPC_OK) st.unpack(s, x_out, u_out, dt_out, status, iters, n_grid_out);
+    return rc;
 }
 
 int mpc_controller_state(mpc_solver* s, int32_t B, int32_t* seq, int32_t* empty, double* last_goal) {
     g_err[0] = 0;
     if (!s) return MPC_EINVAL;
     if (B <= 0) return MPC_OK;
-    if (B > s->max_batch) { set_err("mpc_controller_state: B exceeds max_batch"); return MPC_EBATCH; }
+    if (const int rc = refused(s, B, REF_MAX_BATCH, "mpc_controller_state")) return rc;
     const size_t nb = (size_t)B;
     if (!s->d_cyc) {      // no controller call yet
         if (seq) memset(seq, 0, nb * 4);
@@ -1078,11 +1060,7 @@ int mpc_evaluate_batch_device(mpc_solver* s, int32_t B, const double* d_x0, cons
     g_err[0] = 0;
     if (!s || !d_x || !d_u || !d_out || (s->cfg.dt_free && !d_dt)) { set_err("mpc_evaluate_batch_device: null argument (x, u, out; dt on the variable grid)"); return MPC_EINVAL; }
     if (B <= 0) return MPC_OK;
-    if (B > s->max_batch) { set_err("mpc_evaluate_batch: B exceeds max_batch"); return MPC_EBATCH; }
-    if (s->use_ngrid && B > s->ngrid_B) { set_err("mpc_evaluate_batch: B exceeds the batch the per-instance grid sizes were set for (mpc_set_grid_sizes)"); return MPC_EBATCH; }
-    if (s->P64.n_via > 0 && s->p_nvia == s->d_nvia && s->nvia_B > 0 && B > s->nvia_B) {
-        set_err("mpc_evaluate_batch: B exceeds the batch the via-points were set for (mpc_set_via_points)"); return MPC_EBATCH; }
-    if (s->p_set_of && B > s->sets_B) { set_err("mpc_evaluate_batch: B exceeds the batch the parameter sets were given for (mpc_set_parameter_sets)"); return MPC_EBATCH; }
+    if (const int rc = refused(s, B, REF_MAX_BATCH | REF_NGRID | REF_VIA | REF_SETS, "mpc_evaluate_batch")) return rc;
     HIP_TRY(hipSetDevice(s->device));
     mpc::EvalArgs a;
     memset(&a, 0, sizeof(a));
@@ -1100,35 +1078,20 @@ int mpc_evaluate_batch(mpc_solver* s, int32_t B, const double* x0, const double*
     g_err[0] = 0;
     if (!s || !x || !u || !out || (s->cfg.dt_free && !dt)) { set_err("mpc_evaluate_batch: null argument (x, u, out; dt on the variable grid)"); return MPC_EINVAL; }
     if (B <= 0) return MPC_OK;
-    if (B > s->max_batch) { set_err("mpc_evaluate_batch: B exceeds max_batch"); return MPC_EBATCH; }
+    if (const int rc = refused(s, B, REF_MAX_BATCH, "mpc_evaluate_batch")) return rc;
     HIP_TRY(hipSetDevice(s->device));
-    hipStream_t q = s->stream;
     const size_t nb = (size_t)B, n = (size_t)s->cfg.n, O = s->cfg.max_obstacles > 0 ? (size_t)s->cfg.max_obstacles : 0, V = s->cfg.max_vertices > 0 ? (size_t)s->cfg.max_vertices : 1;
-    const bool obst = O > 0 && obstacles && obstacles->n_obstacles && obstacles->n_vertices && obstacles->vertices;
-    // one pinned block and one device block: the inputs (one copy in), then the five outputs (one copy back)
-    enum { N_IN = 12, N_ALL = 17 };
-    const void* src[N_IN] = {x0, xf, u_prev, dt_prev, x, u, dt, obst ? obstacles->n_obstacles : nullptr, obst ? obstacles->n_vertices : nullptr, obst ? obstacles->vertices : nullptr,
-                             obst ? obstacles->radius : nullptr, obst ? obstacles->velocity : nullptr};
-    void* dst[N_ALL - N_IN] = {out->objective, out->eq_violation, out->ineq_violation, out->clearance, out->closest};
-    const size_t per[N_ALL] = {24, 24, 16, 8, n * 24, n * 16, 8, 4, O * 4, O * V * 16, O * 8, O * 16, 8, 8, 8, 8, 8};
-    size_t off[N_ALL], sz[N_ALL];
-    mpc::Packer pk;
-    for (int i = 0; i < N_ALL; ++i) { sz[i] = (i < N_IN ? src[i] != nullptr : dst[i - N_IN] != nullptr) ? nb * per[i] : 0; off[i] = pk.take(sz[i]); }
-    const size_t in_bytes = off[N_IN];
-    for (Buf* bf : {&s->bufs[BUF_EVAL_HSTAGE], &s->bufs[BUF_EVAL_DSTAGE]})
-        if (pk.off > bf->bytes) { HIP_TRY(hipStreamSynchronize(q)); HIP_TRY(buf_alloc(*bf, pk.off)); }
-    for (int i = 0; i < N_IN; ++i) if (sz[i]) memcpy(s->h_eval_stage + off[i], src[i], sz[i]);
-    auto dv = [&](int i) -> void* { return sz[i] ? (void*)(s->d_eval_stage + off[i]) : nullptr; };
-    if (in_bytes) HIP_TRY(hipMemcpyAsync(s->d_eval_stage, s->h_eval_stage, in_bytes, hipMemcpyHostToDevice, q));
-    const mpc_obstacles dob = {(const int32_t*)dv(7), (const int32_t*)dv(8), (const double*)dv(9), (const double*)dv(10), (const double*)dv(11)};
-    const mpc_eval_out dout = {(double*)dv(12), (double*)dv(13), (double*)dv(14), (double*)dv(15), (int32_t*)dv(16)};
-    const int rc = mpc_evaluate_batch_device(s, B, (const double*)dv(0), (const double*)dv(1), (const double*)dv(2), (const double*)dv(3), (const double*)dv(4), (const double*)dv(5),
-                                             (const double*)dv(6), &dob, &dout);
-    if (rc != MPC_OK) return rc;
-    if (pk.off > in_bytes) HIP_TRY(hipMemcpyAsync(s->h_eval_stage + in_bytes, s->d_eval_stage + in_bytes, pk.off - in_bytes, hipMemcpyDeviceToHost, q));
-    HIP_TRY(hipStreamSynchronize(q));
-    for (int i = N_IN; i < N_ALL; ++i) if (sz[i]) memcpy(dst[i - N_IN], s->h_eval_stage + off[i], sz[i]);
-    return MPC_OK;
+    const mpc_obstacles none = {nullptr, nullptr, nullptr, nullptr, nullptr};      // (without the three arrays: clearance +inf)
+    const mpc_obstacles& ob = O > 0 && obstacles && obstacles->n_obstacles && obstacles->n_vertices && obstacles->vertices ? *obstacles : none;
+    const mpc::StagePiece pc[17] = {stage_in(x0, nb * 24), stage_in(xf, nb * 24), stage_in(u_prev, nb * 16), stage_in(dt_prev, nb * 8), stage_in(x, nb * n * 24), stage_in(u, nb * n * 16), stage_in(dt, nb * 8),
+                                    stage_in(ob.n_obstacles, nb * 4), stage_in(ob.n_vertices, nb * O * 4), stage_in(ob.vertices, nb * O * V * 16), stage_in(ob.radius, nb * O * 8), stage_in(ob.velocity, nb * O * 16),
+                                    stage_out(out->objective, nb * 8), stage_out(out->eq_violation, nb * 8), stage_out(out->ineq_violation, nb * 8), stage_out(out->clearance, nb * 8), stage_out(out->closest, nb * 8)};
+    return staged_call(s, "mpc_evaluate_batch", false, false, pc, 17, [&](void** d) {
+        const mpc_obstacles dob = {(const int32_t*)d[7], (const int32_t*)d[8], (const double*)d[9], (const double*)d[10], (const double*)d[11]};
+        const mpc_eval_out dout = {(double*)d[12], (double*)d[13], (double*)d[14], (double*)d[15], (int32_t*)d[16]};
+        return mpc_evaluate_batch_device(s, B, (const double*)d[0], (const double*)d[1], (const double*)d[2], (const double*)d[3], (const double*)d[4], (const double*)d[5],
+                                         (const double*)d[6], &dob, &dout);
+    });
 }
 
 }  // extern "C"
@@ -1153,7 +1116,7 @@ int mpc_plan_inputs_batch_device(mpc_solver* s, int32_t B, const mpc_plan_params
     g_err[0] = 0;
     if (const char* e = plan_inputs_error(s, p, d_global_plan, d_n_global, gstride, d_robot_pose, d_plan, d_n_plan, plan_stride, d_n_via, d_via)) { set_err(e); return MPC_EINVAL; }
     if (B <= 0) return MPC_OK;
-    if (B > s->max_batch) { set_err("mpc_plan_inputs_batch: B exceeds max_batch"); return MPC_EBATCH; }
+    if (const int rc = refused(s, B, REF_MAX_BATCH, "mpc_plan_inputs_batch")) return rc;
     HIP_TRY(hipSetDevice(s->device));
     mpc::PlanInputsArgs a;
     memset(&a, 0, sizeof(a));
@@ -1175,7 +1138,7 @@ static int commands_device(mpc_solver* s, int32_t B, const double* d_u, int32_t 
     g_err[0] = 0;
     if (!s || !d_u || !d_status || !d_cmd || !d_result) { set_err("mpc_commands_batch: null argument (u_out, status, cmd, result)"); return MPC_EINVAL; }
     if (B <= 0) return MPC_OK;
-    if (B > s->max_batch) { set_err("mpc_commands_batch: B exceeds max_batch"); return MPC_EBATCH; }
+    if (const int rc = refused(s, B, REF_MAX_BATCH, "mpc_commands_batch")) return rc;
     HIP_TRY(hipSetDevice(s->device));
     const mpc::CommandsArgs a = {d_u, u_stride, B, d_status, d_feasible, d_plan_flags, d_cmd, d_result, d_reset_next, d_u_prev_next, d_infeasible_count};
     hipLaunchKernelGGL(mpc::commands_kernel, dim3((B + 63) / 64), dim3(64), 0, s->stream, a);
@@ -1192,30 +1155,6 @@ int mpc_commands_batch_device(mpc_solver* s, int32_t B, const double* d_u_out, c
 
 }  // extern "C"
 
-// One pinned block and one device block for the host variants: every given array goes in (in / out ones and outputs alike, so that what a kernel leaves alone comes back
-// as it was), the kernel runs, the arrays marked `back` come out.
-struct StagePiece { const void* src; void* dst; size_t bytes; };
-static int staged_call(mpc_solver* s, StagePiece* pc, int count, void** dev, int (*run)(void* ctx, void** dev), void* ctx) {
-    hipStream_t q = s->stream;
-    size_t off[24];
-    mpc::Packer pk;
-    for (int i = 0; i < count; ++i) off[i] = pk.take(pc[i].src || pc[i].dst ? pc[i].bytes : 0);
-    for (Buf* bf : {&s->bufs[BUF_PLAN_HSTAGE], &s->bufs[BUF_PLAN_DSTAGE]})
-        if (pk.off > bf->bytes) { HIP_TRY(hipStreamSynchronize(q)); HIP_TRY(buf_alloc(*bf, pk.off)); }
-    for (int i = 0; i < count; ++i) {
-        const void* from = pc[i].src ? pc[i].src : pc[i].dst;
-        dev[i] = from ? (void*)(s->d_plan_stage + off[i]) : nullptr;
-        if (from) memcpy(s->h_plan_stage + off[i], from, pc[i].bytes);
-    }
-    if (pk.off) HIP_TRY(hipMemcpyAsync(s->d_plan_stage, s->h_plan_stage, pk.off, hipMemcpyHostToDevice, q));
-    const int rc = run(ctx, dev);
-    if (rc != MPC_OK) return rc;
-    if (pk.off) HIP_TRY(hipMemcpyAsync(s->h_plan_stage, s->d_plan_stage, pk.off, hipMemcpyDeviceToHost, q));
-    HIP_TRY(hipStreamSynchronize(q));
-    for (int i = 0; i < count; ++i) if (pc[i].dst) memcpy(pc[i].dst, s->h_plan_stage + off[i], pc[i].bytes);
-    return MPC_OK;
-}
-
 extern "C" {
 
 int mpc_plan_inputs_batch(mpc_solver* s, int32_t B, const mpc_plan_params* p, const double* global_plan, const int32_t* n_global, int32_t gstride,
@@ -1224,19 +1163,16 @@ int mpc_plan_inputs_batch(mpc_solver* s, int32_t B, const mpc_plan_params* p, co
     g_err[0] = 0;
     if (const char* e = plan_inputs_error(s, p, global_plan, n_global, gstride, robot_pose, plan, n_plan, plan_stride, n_via, via)) { set_err(e); return MPC_EINVAL; }
     if (B <= 0) return MPC_OK;
-    if (B > s->max_batch) { set_err("mpc_plan_inputs_batch: B exceeds max_batch"); return MPC_EBATCH; }
+    if (const int rc = refused(s, B, REF_MAX_BATCH, "mpc_plan_inputs_batch")) return rc;
     HIP_TRY(hipSetDevice(s->device));
     const size_t nb = (size_t)B, mv = s->cfg.max_via_points > 0 ? (size_t)s->cfg.max_via_points : 0;
-    StagePiece pc[10] = {{global_plan, nullptr, nb * (size_t)gstride * 24}, {n_global, nullptr, nb * 4}, {robot_pose, nullptr, nb * 24}, {nullptr, plan_begin, nb * 4},
-                         {nullptr, plan, nb * (size_t)plan_stride * 24}, {nullptr, n_plan, nb * 4}, {nullptr, n_via, nb * 4}, {nullptr, via, nb * mv * 24},
-                         {nullptr, goal_idx, nb * 4}, {nullptr, flags, nb * 4}};
-    void* dev[10];
-    struct Ctx { mpc_solver* s; int32_t B, gstride, plan_stride; const mpc_plan_params* p; } ctx = {s, B, gstride, plan_stride, p};
-    return staged_call(s, pc, 10, dev, [](void* c, void** d) {
-        const Ctx& x = *(const Ctx*)c;
-        return mpc_plan_inputs_batch_device(x.s, x.B, x.p, (const double*)d[0], (const int32_t*)d[1], x.gstride, (const double*)d[2], (int32_t*)d[3], (double*)d[4], (int32_t*)d[5],
-                                            x.plan_stride, (int32_t*)d[6], (double*)d[7], (int32_t*)d[8], (int32_t*)d[9]);
-    }, &ctx);
+    // in / out: the front the caller keeps, and the arrays whose rows behind n_plan[b] and n_via[b] the kernel leaves alone
+    const mpc::StagePiece pc[10] = {stage_in(global_plan, nb * (size_t)gstride * 24), stage_in(n_global, nb * 4), stage_in(robot_pose, nb * 24), stage_inout(plan_begin, nb * 4),
+                                    stage_inout(plan, nb * (size_t)plan_stride * 24), stage_out(n_plan, nb * 4), stage_out(n_via, nb * 4), stage_inout(via, nb * mv * 24), stage_out(goal_idx, nb * 4), stage_out(flags, nb * 4)};
+    return staged_call(s, "mpc_plan_inputs_batch", false, false, pc, 10, [&](void** d) {
+        return mpc_plan_inputs_batch_device(s, B, p, (const double*)d[0], (const int32_t*)d[1], gstride, (const double*)d[2], (int32_t*)d[3], (double*)d[4], (int32_t*)d[5],
+                                            plan_stride, (int32_t*)d[6], (double*)d[7], (int32_t*)d[8], (int32_t*)d[9]);
+    });
 }
 
 int mpc_commands_batch(mpc_solver* s, int32_t B, const double* u_out, const int32_t* status, const int32_t* feasible, const int32_t* plan_flags,
@@ -1244,20 +1180,17 @@ int mpc_commands_batch(mpc_solver* s, int32_t B, const double* u_out, const int3
     g_err[0] = 0;
     if (!s || !u_out || !status || !cmd || !result) { set_err("mpc_commands_batch: null argument (u_out, status, cmd, result)"); return MPC_EINVAL; }
     if (B <= 0) return MPC_OK;
-    if (B > s->max_batch) { set_err("mpc_commands_batch: B exceeds max_batch"); return MPC_EBATCH; }
+    if (const int rc = refused(s, B, REF_MAX_BATCH, "mpc_commands_batch")) return rc;
     HIP_TRY(hipSetDevice(s->device));
     const size_t nb = (size_t)B;
     std::vector<double> u0(2 * nb);      // only the first control of every instance travels
     for (size_t b = 0; b < nb; ++b) { u0[2 * b] = u_out[b * (size_t)s->cfg.n * 2]; u0[2 * b + 1] = u_out[b * (size_t)s->cfg.n * 2 + 1]; }
-    StagePiece pc[9] = {{u0.data(), nullptr, nb * 16}, {status, nullptr, nb * 4}, {feasible, nullptr, nb * 4}, {plan_flags, nullptr, nb * 4},
-                        {nullptr, cmd, nb * 24}, {nullptr, result, nb * 4}, {nullptr, reset_next, nb * 4}, {nullptr, u_prev_next, nb * 16}, {nullptr, infeasible_count, nb * 4}};
-    void* dev[9];
-    struct Ctx { mpc_solver* s; int32_t B; } ctx = {s, B};
-    return staged_call(s, pc, 9, dev, [](void* c, void** d) {
-        const Ctx& x = *(const Ctx*)c;
-        return commands_device(x.s, x.B, (const double*)d[0], 1, (const int32_t*)d[1], (const int32_t*)d[2], (const int32_t*)d[3], (double*)d[4], (int32_t*)d[5],
+    const mpc::StagePiece pc[9] = {stage_in(u0.data(), nb * 16), stage_in(status, nb * 4), stage_in(feasible, nb * 4), stage_in(plan_flags, nb * 4), stage_out(cmd, nb * 24), stage_out(result, nb * 4),
+                                   stage_out(reset_next, nb * 4), stage_out(u_prev_next, nb * 16), stage_inout(infeasible_count, nb * 4)};      // (the count stays as it is at a goal reached or an empty plan)
+    return staged_call(s, "mpc_commands_batch", false, false, pc, 9, [&](void** d) {
+        return commands_device(s, B, (const double*)d[0], 1, (const int32_t*)d[1], (const int32_t*)d[2], (const int32_t*)d[3], (double*)d[4], (int32_t*)d[5],
                                (int32_t*)d[6], (double*)d[7], (int32_t*)d[8]);
-    }, &ctx);
+    });
 }
 
 }  // extern "C"

@@ -266,5 +266,39 @@ inline StepPieces step_pieces(const mpc_config& c, size_t B, bool u_prev, bool d
     return p;
 }
 
+// The pieces of any other host-pointer call (staged_call of mpc_capi.hip) in ONE block that exists once in pinned host memory and once on the device.  A piece is an
+// array of the caller's: STAGE_IN goes to the device only (src), STAGE_OUT comes back only (dst), STAGE_INOUT goes and comes back (src and dst, as a rule the same
+// array: what a kernel leaves alone returns as it was).  A piece without its pointer(s) or of zero bytes is absent: no room, no device address.  Whatever order the
+// caller lists them in, the block holds IN | INOUT | OUT, so that ONE copy [0, h2d_bytes) takes every input over and ONE copy [d2h_begin, d2h_begin + d2h_bytes)
+// brings every output back; neither moves the padding behind its last piece.  tests/test_stage_pieces.py walks piece lists through it.
+enum StageDir { STAGE_IN, STAGE_INOUT, STAGE_OUT };
+struct StagePiece { const void* src; void* dst; size_t bytes; int dir; };
+struct StageLayout {
+    enum { MAX_PIECES = 24 };
+    size_t off[MAX_PIECES];       // 256-byte aligned, 0 for an absent piece
+    bool present[MAX_PIECES];
+    size_t bytes;                 // the end of the last piece: what either block has to hold
+    size_t h2d_bytes, d2h_begin, d2h_bytes;
+    void* at(void* base, int i) const { return present[i] ? (char*)base + off[i] : nullptr; }      // piece i in a block at `base`, NULL for an absent one
+};
+inline StageLayout stage_layout(const StagePiece* pc, int count) {
+    StageLayout L{};
+    Packer pk;
+    size_t in_end = 0;
+    for (int dir = STAGE_IN; dir <= STAGE_OUT; ++dir) {
+        for (int i = 0; i < count; ++i) {
+            const StagePiece& p = pc[i];
+            if (p.dir != dir || !p.bytes || (dir != STAGE_OUT && !p.src) || (dir != STAGE_IN && !p.dst)) continue;
+            L.present[i] = true;
+            L.off[i] = pk.take(p.bytes);
+            L.bytes = L.off[i] + p.bytes;
+        }
+        if (dir == STAGE_IN) { in_end = L.bytes; L.d2h_begin = pk.off; }
+        if (dir == STAGE_INOUT) L.h2d_bytes = L.bytes;
+    }
+    if (L.bytes > in_end) L.d2h_bytes = L.bytes - L.d2h_begin; else L.d2h_begin = 0;      // (nothing comes back: an empty range at 0)
+    return L;
+}
+
 
 }  // namespace mpc

@@ -24,8 +24,8 @@
 extern "C" {
 #include "mpc_hip.h"
 
-// mpc_step_batch (all outer OCP iterations of a control cycle enqueued at once) is used when the linked C ABI has it: libmpc_hip.so does; the recording
-// stand-in ABI of the CPU tests (tests/host_harness/facade_step_host.cpp) does not, and the facade then iterates on the host as before
+// mpc_step_batch (all outer OCP iterations of a control cycle enqueued at once) is used when the linked C ABI has it: libmpc_hip.so does; a build
+// without it, such as the lazily linked harness of the CPU tests (tests/host_harness/controller_host.cpp), does not, and the facade then iterates on the host as before
 #ifndef MPC_FACADE_HOST_LOOP_ONLY      // (defined by builds on a stand-in ABI that live in one process with the real library)
 extern "C" int mpc_step_batch(mpc_solver* s, int32_t B, const double* x0, const double* xf, const double* u_prev, const double* dt_prev, const double* x_init,
                               const double* u_init, const double* dt_init, const mpc_obstacles* obstacles, int32_t outer_iterations, int32_t adapt, int32_t n_min,

@@ -1,4 +1,4 @@
-"""ctypes mirror of include/mpc_hip.h (struct mpc_config and the enum values).
+"""ctypes mirror of include/mpc_hip.h (its structs, its enum values and, in PROTOTYPES, its functions).
 
 Pure data definitions -- shared by the product binding (mpc_local_planner_amd/_lib.py)
 and by tests.  No solver code here.
@@ -182,6 +182,58 @@ class MpcPlanParams(C.Structure):
 PLAN_GOAL_REACHED, PLAN_EMPTY, PLAN_TRUNCATED, PLAN_VIA_DROPPED, PLAN_GOAL_INJECTED = 1, 2, 4, 8, 16
 # enum mpc_cmd_result: result[b] of mpc_commands_batch*
 CMD_SUCCESS, CMD_GOAL_REACHED, CMD_PLAN_EMPTY, CMD_SOLVE_FAILED, CMD_INFEASIBLE, CMD_NOT_FINITE = 0, 1, 2, 3, 4, 5
+
+
+# ---- the functions of include/mpc_hip.h: name -> (restype, argtypes), the one statement of the C ABI on the Python side.  _lib.load() assigns them, _lib.EXPORTS is
+# the names, tests/test_abi.py holds every row to the header's declaration.  A host / device pair shares one signature object.
+_p = C.c_void_p      # a raw address (host numpy buffer or device pointer) or the opaque mpc_solver*
+_i, _d, _rc = C.c_int32, C.c_double, C.c_int
+_SOLVE = (_rc, [_p, _i] + [_p] * 7 + [_p] + [_p] * 5)      # s, B, x0, xf, u_prev, dt_prev, x_init, u_init, dt_init, const mpc_obstacles*, x_out, u_out, dt_out, status, iters
+_STEP = [_p, _i] + [_p] * 7 + [_p] + [_i] * 4 + [_d] + [_p] * 5      # s, B, the seven inputs, obstacles, outer_iterations, adapt, n_min, n_max, dt_hyst_ratio, the five outputs
+# s, B, p, plan, n_plan, plan_stride, x_feedback, feedback_age, reset, u_prev, dt_prev, obstacles, x_out, u_out, dt_out, status, iters, reinit_out
+_CYCLE = [_p, _i, C.POINTER(MpcCycleParams), _p, _p, _i] + [_p] * 5 + [_p] + [_p] * 6
+# s, B, cost, size_x, size_y, resolution, origin, robot_pose, behind_robot_dist, n_obstacles, n_vertices, vertices, dropped
+_COSTMAP = (_rc, [_p, _i, _p, _i, _i, _d, _p, _p, _d, _p, _p, _p, _p])
+# s, B, x, cost, size_x, size_y, resolution, origin, footprint_spec, n_spec, inscribed_radius, min_resolution_collision_check_angular, look_ahead_idx, feasible
+_FEASIBLE = (_rc, [_p, _i, _p, _p, _i, _i, _d, _p, _p, _i, _d, _d, _i, _p])
+_EVALUATE = (_rc, [_p, _i] + [_p] * 7 + [_p, C.POINTER(MpcEvalOut)])      # s, B, x0, xf, u_prev, dt_prev, x, u, dt, const mpc_obstacles*, const mpc_eval_out*
+# s, B, p, global_plan, n_global, gstride, robot_pose, plan_begin, plan, n_plan, plan_stride, n_via, via, goal_idx, flags
+_PLAN_INPUTS = (_rc, [_p, _i, C.POINTER(MpcPlanParams), _p, _p, _i, _p, _p, _p, _p, _i] + [_p] * 4)
+_COMMANDS = (_rc, [_p, _i] + [_p] * 9)      # s, B, u_out, status, feasible, plan_flags, cmd, result, reset_next, u_prev_next, infeasible_count
+
+PROTOTYPES = {
+    "mpc_config_defaults": (None, [C.POINTER(MpcConfig)]),                                      # cfg
+    "mpc_create": (_rc, [C.POINTER(MpcConfig), _i, _i, C.POINTER(C.c_void_p)]),                  # cfg, max_batch, device, out
+    "mpc_reset": (_rc, [_p]),                                                                   # s
+    "mpc_destroy": (None, [_p]),                                                                # s
+    "mpc_solve_batch": _SOLVE, "mpc_solve_batch_device": _SOLVE,
+    "mpc_step_batch": (_rc, _STEP + [_p]),                                                      # ..., n_grid_out
+    "mpc_step_batch_device": (_rc, _STEP),
+    "mpc_cycle_params_defaults": (None, [C.POINTER(MpcCycleParams)]),                           # p
+    "mpc_controller_step_batch": (_rc, _CYCLE + [_p]),                                          # ..., n_grid_out
+    "mpc_controller_step_batch_device": (_rc, _CYCLE),
+    "mpc_controller_state": (_rc, [_p, _i, _p, _p, _p]),                                        # s, B, seq, empty, last_goal
+    "mpc_set_grid_sizes": (_rc, [_p, _p, _i]),                                                  # s, n_grid, B
+    "mpc_set_parameter_sets": (_rc, [_p, _i, _p, _i, _p]),                                      # s, n_sets, sets, B, set_of
+    "mpc_set_via_points": (_rc, [_p, _i, _p, _p]),                                              # s, B, n_via, via
+    "mpc_set_via_points_device": (_rc, [_p, _p, _p]),                                          # s, n_via, via
+    "mpc_costmap_to_obstacles": _COSTMAP, "mpc_costmap_to_obstacles_device": _COSTMAP,
+    "mpc_last_candidates": (_rc, [_p, _i, _p, _p]),                                             # s, B, winner, iters_total
+    "mpc_last_rows_dropped": (_rc, [_p, _i, _p]),                                               # s, B, rows_dropped
+    "mpc_check_feasibility": _FEASIBLE, "mpc_check_feasibility_device": _FEASIBLE,
+    "mpc_evaluate_batch": _EVALUATE, "mpc_evaluate_batch_device": _EVALUATE,
+    "mpc_plan_params_defaults": (None, [C.POINTER(MpcPlanParams)]),                             # p
+    "mpc_plan_inputs_batch": _PLAN_INPUTS, "mpc_plan_inputs_batch_device": _PLAN_INPUTS,
+    "mpc_commands_batch": _COMMANDS, "mpc_commands_batch_device": _COMMANDS,
+    "mpc_grid_update_device": (_rc, [_p, _i, _p, _p, _p, _p, _i, _i, _i, _d]),                  # s, B, x0_new, x, u, dt, adapt, n_min, n_max, dt_hyst_ratio
+    "mpc_get_grid_sizes": (_rc, [_p, _i, _p]),                                                  # s, B, n_grid
+    "mpc_synchronize": (_rc, [_p]),                                                             # s
+    "mpc_last_kernel_ms": (_rc, [_p, C.POINTER(C.c_float)]),                                    # s, ms
+    "mpc_lds_bytes": (_rc, [_p, C.POINTER(C.c_int64)]),                                         # s, bytes
+    "mpc_occupancy": (_rc, [_p, _i, C.POINTER(_i), C.POINTER(C.c_int64)]),                      # s, B, workgroups_per_cu, lds_bytes
+    "mpc_last_error": (C.c_char_p, []),
+    "mpc_version": (_i, []),
+}
 
 
 def _diag_offdiag(w, dim):

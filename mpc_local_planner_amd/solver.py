@@ -63,10 +63,15 @@ class Commands:
     infeasible_count: np.ndarray    # (B,) int32 failures in a row
 
 
+# ---- how each kind of argument reaches the C ABI ---------------------------------------------------------------------------------------------------------------------
 def _addr(a):
-    if a is None:
-        return None
-    return C.c_void_p(a.ctypes.data)
+    """address of a host array, None -> NULL"""
+    return None if a is None else C.c_void_p(a.ctypes.data)
+
+
+def _dev(p):
+    """a device address (int), 0 / None -> NULL"""
+    return C.c_void_p(p) if p else None
 
 
 def _as_f64(a, shape):
@@ -76,6 +81,36 @@ def _as_f64(a, shape):
     if a.shape != shape:
         raise ValueError(f"expected shape {shape}, got {a.shape}")
     return a
+
+
+def _as_i32(a, B, name=None):
+    """contiguous int32 of shape (B,), None -> None; a wrong shape raises under `name`, without a name whatever has B elements is taken as (B,)"""
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a, dtype=np.int32)
+    if name is None:
+        return a.reshape(B)
+    if a.shape != (B,):
+        raise ValueError(f"{name} must have shape (B,)")
+    return a
+
+
+def _dev_obstacles(obstacles):
+    """const mpc_obstacles* of up to five device addresses, None -> NULL"""
+    if obstacles is None:
+        return None
+    return C.byref(MpcObstacles(*(tuple(obstacles) + (None,) * (5 - len(obstacles)))))
+
+
+def _params(lib, name, struct, fields):
+    """a parameter struct with the library's defaults (<name>_defaults), then the given fields"""
+    p = struct()
+    getattr(lib, name + "_defaults")(C.byref(p))
+    for k, v in fields.items():
+        if k not in dict(struct._fields_):
+            raise ValueError(f"{name} has no field {k}")
+        setattr(p, k, v)
+    return p
 
 
 class BatchSolver:
@@ -126,6 +161,9 @@ class BatchSolver:
 
     # ---- host buffers (numpy) ------------------------------------------------
     def _pack_obstacles(self, obstacles, B):
+        """(const mpc_obstacles* of host arrays or NULL, the arrays: they have to outlive the call)"""
+        if obstacles is None:
+            return None, None
         O, V = int(self.cfg.max_obstacles), int(self.cfg.max_vertices)
         no = np.ascontiguousarray(obstacles[0], dtype=np.int32)
         nv = np.ascontiguousarray(obstacles[1], dtype=np.int32)
@@ -134,66 +172,47 @@ class BatchSolver:
         vel = _as_f64(obstacles[4], (B, O, 2)) if len(obstacles) > 4 and obstacles[4] is not None else None
         if no.shape != (B,) or nv.shape != (B, O):
             raise ValueError("obstacle arrays have the wrong shape")
-        keep = (no, nv, vv, rr, vel)       # the arrays must outlive the call
-        ob = MpcObstacles(no.ctypes.data, nv.ctypes.data, vv.ctypes.data, rr.ctypes.data if rr is not None else None,
-                          vel.ctypes.data if vel is not None else None)
-        return ob, keep
+        keep = (no, nv, vv, rr, vel)
+        return C.byref(MpcObstacles(*(a.ctypes.data if a is not None else None for a in keep))), keep
+
+    def _solve_inputs(self, x0, xf, u_prev, dt_prev, init):
+        """B and the seven input arrays solve() and step() share, checked: x0, xf, u_prev, dt_prev, x_init, u_init, dt_init"""
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        B, n = int(x0.shape[0]), self.n
+        cycle = (_as_f64(x0, (B, 3)), _as_f64(xf, (B, 3)), _as_f64(u_prev, (B, 2)), _as_f64(dt_prev, (B,)))
+        if init is None:
+            return B, cycle + (None, None, None)
+        return B, cycle + (_as_f64(init[0], (B, n, 3)), _as_f64(init[1], (B, n, 2)), _as_f64(init[2], (B,)))
+
+    def _outputs(self, B, alloc=np.zeros):
+        """(BatchResult of fresh arrays, their addresses in the order of the C ABI: x_out, u_out, dt_out, status, iters)"""
+        r = BatchResult(alloc((B, self.n, 3)), alloc((B, self.n, 2)), alloc(B), alloc(B, np.int32), alloc(B, np.int32))
+        return r, [_addr(r.x), _addr(r.u), _addr(r.dt), _addr(r.status), _addr(r.iters)]
 
     def solve(self, x0, xf, u_prev=None, dt_prev=None, init=None, obstacles=None) -> BatchResult:
         """One control cycle for B instances (Controller::step, src/controller.cpp:111-179).
         init = (x_init (B,n,3), u_init (B,n,2), dt_init (B,)) or None for the reference cold start.
         obstacles = (n_obstacles (B,), n_vertices (B,O), vertices (B,O,V,2)[, radius (B,O)[, velocity (B,O,2)]]) when the solver was
         created with max_obstacles > 0."""
-        x0 = np.ascontiguousarray(x0, dtype=np.float64)
-        B = x0.shape[0]
-        n = self.n
-        x0 = _as_f64(x0, (B, 3))
-        xf = _as_f64(xf, (B, 3))
-        u_prev = _as_f64(u_prev, (B, 2))
-        dt_prev = _as_f64(dt_prev, (B,))
-        xi = ui = di = None
-        if init is not None:
-            xi, ui, di = _as_f64(init[0], (B, n, 3)), _as_f64(init[1], (B, n, 2)), _as_f64(init[2], (B,))
-        xo = np.empty((B, n, 3))
-        uo = np.empty((B, n, 2))
-        do = np.empty(B)
-        st = np.empty(B, dtype=np.int32)
-        it = np.empty(B, dtype=np.int32)
-        ob, keep = self._pack_obstacles(obstacles, B) if obstacles is not None else (None, None)
-        rc = self._lib.mpc_solve_batch(self._h, B, _addr(x0), _addr(xf), _addr(u_prev), _addr(dt_prev), _addr(xi), _addr(ui),
-                                       _addr(di), C.byref(ob) if ob is not None else None, _addr(xo), _addr(uo), _addr(do),
-                                       _addr(st), _addr(it))
-        self._check(rc)
-        return BatchResult(xo, uo, do, st, it)
+        B, inputs = self._solve_inputs(x0, xf, u_prev, dt_prev, init)
+        ob, keep = self._pack_obstacles(obstacles, B)
+        r, outs = self._outputs(B, np.empty)
+        self._check(self._lib.mpc_solve_batch(self._h, B, *map(_addr, inputs), ob, *outs))
+        return r
 
     def step(self, x0, xf, u_prev=None, dt_prev=None, init=None, obstacles=None, outer_iterations=1, adapt=False, n_min=3, n_max=0, dt_hyst_ratio=0.1):
         """One control cycle = `outer_iterations` x (grid update -> solve) in ONE call (mpc_step_batch: PredictiveController::step's outer OCP iterations,
         src/controller.cpp:70-72,172, without a host round trip between them).  Returns (BatchResult of the last solve, grid sizes after the call)."""
-        B = int(np.asarray(x0).shape[0])
-        n = self.n
-        x0 = _as_f64(x0, (B, 3)); xf = _as_f64(xf, (B, 3))
-        u_prev = _as_f64(u_prev, (B, 2)) if u_prev is not None else None
-        dt_prev = _as_f64(dt_prev, (B,)) if dt_prev is not None else None
-        xi = ui = di = None
-        if init is not None:
-            xi, ui, di = _as_f64(init[0], (B, n, 3)), _as_f64(init[1], (B, n, 2)), _as_f64(init[2], (B,))
-        ob, keep = self._pack_obstacles(obstacles, B) if obstacles is not None else (None, None)
-        xo = np.zeros((B, n, 3)); uo = np.zeros((B, n, 2)); do = np.zeros(B); st = np.zeros(B, np.int32); it = np.zeros(B, np.int32); ng = np.zeros(B, np.int32)
-        rc = self._lib.mpc_step_batch(self._h, B, _addr(x0), _addr(xf), _addr(u_prev), _addr(dt_prev), _addr(xi), _addr(ui), _addr(di),
-                                      C.byref(ob) if ob is not None else None, int(outer_iterations), int(bool(adapt)), int(n_min), int(n_max if n_max > 0 else n),
-                                      float(dt_hyst_ratio), _addr(xo), _addr(uo), _addr(do), _addr(st), _addr(it), _addr(ng))
-        self._check(rc)
-        return BatchResult(xo, uo, do, st, it), ng
+        B, inputs = self._solve_inputs(x0, xf, u_prev, dt_prev, init)
+        ob, keep = self._pack_obstacles(obstacles, B)
+        (r, outs), ng = self._outputs(B), np.zeros(B, np.int32)
+        self._check(self._lib.mpc_step_batch(self._h, B, *map(_addr, inputs), ob, int(outer_iterations), int(bool(adapt)), int(n_min), int(n_max if n_max > 0 else self.n),
+                                             float(dt_hyst_ratio), *outs, _addr(ng)))
+        return r, ng
 
     def cycle_params(self, **fields) -> MpcCycleParams:
         """mpc_cycle_params with the reference's in-code defaults (mpc_cycle_params_defaults), then the given fields"""
-        p = MpcCycleParams()
-        self._lib.mpc_cycle_params_defaults(C.byref(p))
-        for k, v in fields.items():
-            if k not in dict(MpcCycleParams._fields_):
-                raise ValueError(f"mpc_cycle_params has no field {k}")
-            setattr(p, k, v)
-        return p
+        return _params(self._lib, "mpc_cycle_params", MpcCycleParams, fields)
 
     def controller_step(self, params: MpcCycleParams, plan, n_plan, x_feedback=None, feedback_age=None, reset=None, u_prev=None, dt_prev=None, obstacles=None):
         """One whole Controller::step cycle for B robots (mpc_controller_step_batch; src/controller.cpp:111-179): state estimate, re-initialisation decision, initial
@@ -203,36 +222,25 @@ class BatchSolver:
         plan = np.ascontiguousarray(plan, dtype=np.float64)
         B, stride = int(plan.shape[0]), int(plan.shape[1])
         plan = _as_f64(plan, (B, stride, 3))
-        n = self.n
-        npl = np.ascontiguousarray(n_plan, dtype=np.int32)
-        if npl.shape != (B,):
-            raise ValueError("n_plan must have shape (B,)")
-        fb, age = _as_f64(x_feedback, (B, 3)), _as_f64(feedback_age, (B,))
-        rs = np.ascontiguousarray(reset, dtype=np.int32) if reset is not None else None
-        u_prev = _as_f64(u_prev, (B, 2)); dt_prev = _as_f64(dt_prev, (B,))
-        ob, keep = self._pack_obstacles(obstacles, B) if obstacles is not None else (None, None)
-        xo = np.zeros((B, n, 3)); uo = np.zeros((B, n, 2)); do = np.zeros(B); st = np.zeros(B, np.int32); it = np.zeros(B, np.int32)
-        ri = np.zeros(B, np.int32); ng = np.zeros(B, np.int32)
-        rc = self._lib.mpc_controller_step_batch(self._h, B, C.byref(params), _addr(plan), _addr(npl), stride, _addr(fb), _addr(age), _addr(rs), _addr(u_prev), _addr(dt_prev),
-                                                 C.byref(ob) if ob is not None else None, _addr(xo), _addr(uo), _addr(do), _addr(st), _addr(it), _addr(ri), _addr(ng))
-        self._check(rc)
-        return BatchResult(xo, uo, do, st, it), ri, ng
+        npl = _as_i32(n_plan, B, "n_plan")
+        cycle = (_as_f64(x_feedback, (B, 3)), _as_f64(feedback_age, (B,)), _as_i32(reset, B), _as_f64(u_prev, (B, 2)), _as_f64(dt_prev, (B,)))
+        ob, keep = self._pack_obstacles(obstacles, B)
+        (r, outs), ri, ng = self._outputs(B), np.zeros(B, np.int32), np.zeros(B, np.int32)
+        self._check(self._lib.mpc_controller_step_batch(self._h, B, C.byref(params), _addr(plan), _addr(npl), stride, *map(_addr, cycle), ob, *outs, _addr(ri), _addr(ng)))
+        return r, ri, ng
 
     def controller_step_device(self, B: int, params: MpcCycleParams, plan: int, n_plan: int, plan_stride: int, x_feedback: Optional[int], feedback_age: Optional[int],
                                reset: Optional[int], u_prev: Optional[int], dt_prev: Optional[int], x_out: int, u_out: int, dt_out: int, status: Optional[int],
                                iters: Optional[int], reinit_out: Optional[int] = None, obstacles=None) -> None:
         """mpc_controller_step_batch_device: the same cycle with device addresses (ints), asynchronous on the solver's stream, no host round trip"""
-        v = lambda p: C.c_void_p(p) if p else None
-        ob = MpcObstacles(*(tuple(obstacles) + (None,) * (5 - len(obstacles)))) if obstacles is not None else None
-        rc = self._lib.mpc_controller_step_batch_device(self._h, int(B), C.byref(params), v(plan), v(n_plan), int(plan_stride), v(x_feedback), v(feedback_age), v(reset),
-                                                        v(u_prev), v(dt_prev), C.byref(ob) if ob is not None else None, v(x_out), v(u_out), v(dt_out), v(status), v(iters),
-                                                        v(reinit_out))
-        self._check(rc)
+        cycle, outs = (x_feedback, feedback_age, reset, u_prev, dt_prev), (x_out, u_out, dt_out, status, iters, reinit_out)
+        self._check(self._lib.mpc_controller_step_batch_device(self._h, int(B), C.byref(params), _dev(plan), _dev(n_plan), int(plan_stride), *map(_dev, cycle),
+                                                               _dev_obstacles(obstacles), *map(_dev, outs)))
 
     def controller_state(self, B: int):
         """(seq (B,), empty (B,), last_goal (B, 3)) of the controller slots (mpc_controller_state)"""
         seq = np.zeros(B, np.int32); empty = np.zeros(B, np.int32); goal = np.zeros((B, 3))
-        self._check(self._lib.mpc_controller_state(self._h, int(B), C.c_void_p(seq.ctypes.data), C.c_void_p(empty.ctypes.data), C.c_void_p(goal.ctypes.data)))
+        self._check(self._lib.mpc_controller_state(self._h, int(B), _addr(seq), _addr(empty), _addr(goal)))
         return seq, empty, goal
 
     # ---- device buffers (raw HBM addresses, e.g. torch tensors' data_ptr()) -----
@@ -240,12 +248,8 @@ class BatchSolver:
                      u_init: Optional[int], dt_init: Optional[int], x_out: int, u_out: int, dt_out: int,
                      status: Optional[int], iters: Optional[int], obstacles=None) -> None:
         """Asynchronous solve on the solver's stream; all arguments are device addresses (ints)."""
-        v = lambda p: C.c_void_p(p) if p else None
-        ob = MpcObstacles(*(tuple(obstacles) + (None,) * (5 - len(obstacles)))) if obstacles is not None else None     # up to 5 device addresses
-        rc = self._lib.mpc_solve_batch_device(self._h, B, v(x0), v(xf), v(u_prev), v(dt_prev), v(x_init), v(u_init), v(dt_init),
-                                              C.byref(ob) if ob is not None else None, v(x_out), v(u_out), v(dt_out), v(status),
-                                              v(iters))
-        self._check(rc)
+        self._check(self._lib.mpc_solve_batch_device(self._h, B, *map(_dev, (x0, xf, u_prev, dt_prev, x_init, u_init, dt_init)), _dev_obstacles(obstacles),
+                                                     *map(_dev, (x_out, u_out, dt_out, status, iters))))
 
     def evaluate(self, x0, xf, x, u, dt, u_prev=None, dt_prev=None, obstacles=None) -> TrajectoryEval:
         """Objective, largest equality / inequality violation and clearance to every obstacle of B trajectories under this solver's NLP (mpc_evaluate_batch), in
@@ -255,32 +259,22 @@ class BatchSolver:
         B, n = int(x.shape[0]), self.n
         x, u, dt = _as_f64(x, (B, n, 3)), _as_f64(u, (B, n, 2)), _as_f64(dt, (B,))
         x0, xf, u_prev, dt_prev = _as_f64(x0, (B, 3)), _as_f64(xf, (B, 3)), _as_f64(u_prev, (B, 2)), _as_f64(dt_prev, (B,))
-        ob, keep = self._pack_obstacles(obstacles, B) if obstacles is not None else (None, None)      # keep: the packed arrays have to outlive the call
+        ob, keep = self._pack_obstacles(obstacles, B)
         r = TrajectoryEval(np.empty(B), np.empty(B), np.empty(B), np.empty(B), np.empty((B, 2), np.int32))
         out = MpcEvalOut(r.objective.ctypes.data, r.eq_violation.ctypes.data, r.ineq_violation.ctypes.data, r.clearance.ctypes.data, r.closest.ctypes.data)
-        self._check(self._lib.mpc_evaluate_batch(self._h, B, _addr(x0), _addr(xf), _addr(u_prev), _addr(dt_prev), _addr(x), _addr(u), _addr(dt),
-                                                 C.byref(ob) if ob is not None else None, C.byref(out)))
+        self._check(self._lib.mpc_evaluate_batch(self._h, B, *map(_addr, (x0, xf, u_prev, dt_prev, x, u, dt)), ob, C.byref(out)))
         return r
 
     def evaluate_device(self, B: int, x0: Optional[int], xf: Optional[int], x: int, u: int, dt: Optional[int], objective: Optional[int] = None, eq_violation: Optional[int] = None,
                         ineq_violation: Optional[int] = None, clearance: Optional[int] = None, closest: Optional[int] = None, u_prev: Optional[int] = None,
                         dt_prev: Optional[int] = None, obstacles=None) -> None:
         """mpc_evaluate_batch_device: the same with device addresses (ints), asynchronous on the solver's stream -- e.g. right behind solve_device on its outputs"""
-        v = lambda p: C.c_void_p(p) if p else None
-        ob = MpcObstacles(*(tuple(obstacles) + (None,) * (5 - len(obstacles)))) if obstacles is not None else None
         out = MpcEvalOut(objective or None, eq_violation or None, ineq_violation or None, clearance or None, closest or None)
-        self._check(self._lib.mpc_evaluate_batch_device(self._h, int(B), v(x0), v(xf), v(u_prev), v(dt_prev), v(x), v(u), v(dt), C.byref(ob) if ob is not None else None,
-                                                        C.byref(out)))
+        self._check(self._lib.mpc_evaluate_batch_device(self._h, int(B), *map(_dev, (x0, xf, u_prev, dt_prev, x, u, dt)), _dev_obstacles(obstacles), C.byref(out)))
 
     def plan_params(self, **fields) -> MpcPlanParams:
         """mpc_plan_params with the reference's in-code defaults (mpc_plan_params_defaults), then the given fields"""
-        p = MpcPlanParams()
-        self._lib.mpc_plan_params_defaults(C.byref(p))
-        for k, v in fields.items():
-            if k not in dict(MpcPlanParams._fields_):
-                raise ValueError(f"mpc_plan_params has no field {k}")
-            setattr(p, k, v)
-        return p
+        return _params(self._lib, "mpc_plan_params", MpcPlanParams, fields)
 
     def plan_inputs(self, params: MpcPlanParams, global_plan, n_global, robot_pose, plan_stride: int, plan_begin=None, via_points: bool = False) -> PlanInputs:
         """What the plugin prepares before Controller::step, for B robots (mpc_plan_inputs_batch; src/mpc_local_planner_ros.cpp:294-354): prune, select, via-points,
@@ -289,9 +283,7 @@ class BatchSolver:
         gp = np.ascontiguousarray(global_plan, dtype=np.float64)
         B, gstride = int(gp.shape[0]), int(gp.shape[1])
         gp = _as_f64(gp, (B, gstride, 3))
-        ng = np.ascontiguousarray(n_global, dtype=np.int32)
-        if ng.shape != (B,):
-            raise ValueError("n_global must have shape (B,)")
+        ng = _as_i32(n_global, B, "n_global")
         rp = _as_f64(robot_pose, (B, 3))
         r = PlanInputs(np.zeros((B, int(plan_stride), 3)), np.zeros(B, np.int32),
                        np.zeros(B, np.int32) if plan_begin is None else np.array(plan_begin, dtype=np.int32).reshape(B),
@@ -306,9 +298,8 @@ class BatchSolver:
                            flags: Optional[int] = None) -> None:
         """mpc_plan_inputs_batch_device: the same with device addresses (ints), asynchronous on the solver's stream; plan / n_plan feed controller_step_device, n_via / via
         mpc_set_via_points_device"""
-        v = lambda p: C.c_void_p(p) if p else None
-        self._check(self._lib.mpc_plan_inputs_batch_device(self._h, int(B), C.byref(params), v(global_plan), v(n_global), int(gstride), v(robot_pose), v(plan_begin), v(plan),
-                                                           v(n_plan), int(plan_stride), v(n_via), v(via), v(goal_idx), v(flags)))
+        self._check(self._lib.mpc_plan_inputs_batch_device(self._h, int(B), C.byref(params), _dev(global_plan), _dev(n_global), int(gstride), _dev(robot_pose), _dev(plan_begin),
+                                                           _dev(plan), _dev(n_plan), int(plan_stride), _dev(n_via), _dev(via), _dev(goal_idx), _dev(flags)))
 
     def commands(self, u, status, feasible=None, plan_flags=None, infeasible_count=None) -> Commands:
         """What the plugin does with the step's result, for B robots (mpc_commands_batch; src/mpc_local_planner_ros.cpp:394-452): the velocity command, the result code,
@@ -317,29 +308,22 @@ class BatchSolver:
         u = np.ascontiguousarray(u, dtype=np.float64)
         B = int(u.shape[0])
         u = _as_f64(u, (B, self.n, 2))
-        i32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32).reshape(B)
-        st, fe, fl = i32(status), i32(feasible), i32(plan_flags)
+        st, fe, fl = _as_i32(status, B), _as_i32(feasible, B), _as_i32(plan_flags, B)
         r = Commands(np.zeros((B, 3)), np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros((B, 2)),
                      np.zeros(B, np.int32) if infeasible_count is None else np.array(infeasible_count, dtype=np.int32).reshape(B))
-        self._check(self._lib.mpc_commands_batch(self._h, B, _addr(u), _addr(st), _addr(fe), _addr(fl), _addr(r.cmd), _addr(r.result), _addr(r.reset_next), _addr(r.u_prev_next),
-                                                 _addr(r.infeasible_count)))
+        self._check(self._lib.mpc_commands_batch(self._h, B, *map(_addr, (u, st, fe, fl, r.cmd, r.result, r.reset_next, r.u_prev_next, r.infeasible_count))))
         return r
 
     def commands_device(self, B: int, u: int, status: int, feasible: Optional[int], plan_flags: Optional[int], cmd: int, result: int, reset_next: Optional[int] = None,
                         u_prev_next: Optional[int] = None, infeasible_count: Optional[int] = None) -> None:
         """mpc_commands_batch_device: the same with device addresses (ints), asynchronous on the solver's stream; reset_next / u_prev_next are the reset / u_prev of the
         next controller_step_device"""
-        v = lambda p: C.c_void_p(p) if p else None
-        self._check(self._lib.mpc_commands_batch_device(self._h, int(B), v(u), v(status), v(feasible), v(plan_flags), v(cmd), v(result), v(reset_next), v(u_prev_next),
-                                                        v(infeasible_count)))
+        self._check(self._lib.mpc_commands_batch_device(self._h, int(B), *map(_dev, (u, status, feasible, plan_flags, cmd, result, reset_next, u_prev_next, infeasible_count))))
 
     def set_grid_sizes(self, n_grid=None):
         """Per-instance grid sizes n_i <= cfg.n for the following solves (grid adaptation); None = uniform cfg.n."""
-        if n_grid is None:
-            self._check(self._lib.mpc_set_grid_sizes(self._h, None, 0))
-            return
-        a = np.ascontiguousarray(n_grid, dtype=np.int32)
-        self._check(self._lib.mpc_set_grid_sizes(self._h, C.c_void_p(a.ctypes.data), int(a.shape[0])))
+        a = None if n_grid is None else np.ascontiguousarray(n_grid, dtype=np.int32)
+        self._check(self._lib.mpc_set_grid_sizes(self._h, _addr(a), 0 if a is None else int(a.shape[0])))
 
     def set_parameter_sets(self, sets=None, set_of=None):
         """Per-instance parameter sets for the following solves (mpc_set_parameter_sets): instance b solves with sets[set_of[b]], a complete MpcConfig
@@ -351,7 +335,7 @@ class BatchSolver:
         sets = list(sets)
         arr = (MpcConfig * len(sets))(*sets)
         so = np.ascontiguousarray(np.arange(len(sets)) if set_of is None else set_of, dtype=np.int32)
-        self._check(self._lib.mpc_set_parameter_sets(self._h, len(sets), C.cast(arr, C.c_void_p), int(so.shape[0]), C.c_void_p(so.ctypes.data)))
+        self._check(self._lib.mpc_set_parameter_sets(self._h, len(sets), C.cast(arr, C.c_void_p), int(so.shape[0]), _addr(so)))
 
     def set_via_points(self, n_via=None, via=None):
         """Via-points of the minimum_time_via_points objective for the following solves: n_via[B], via[B][cfg.max_via_points][3]
@@ -362,7 +346,7 @@ class BatchSolver:
         nv = np.ascontiguousarray(n_via, dtype=np.int32)
         vp = np.ascontiguousarray(via, dtype=np.float64)
         assert vp.shape == (nv.shape[0], self.cfg.max_via_points, 3), vp.shape
-        self._check(self._lib.mpc_set_via_points(self._h, int(nv.shape[0]), C.c_void_p(nv.ctypes.data), C.c_void_p(vp.ctypes.data)))
+        self._check(self._lib.mpc_set_via_points(self._h, int(nv.shape[0]), _addr(nv), _addr(vp)))
 
     def costmap_to_obstacles(self, cost, resolution, origin, robot_pose, behind_robot_dist=1.5):
         """Lethal costmap cells -> point obstacles in this solver's obstacle layout (mpc_costmap_to_obstacles).
@@ -373,16 +357,15 @@ class BatchSolver:
         pose = np.ascontiguousarray(robot_pose, dtype=np.float64).reshape(B, 3)
         O, V = self.cfg.max_obstacles, max(1, self.cfg.max_vertices)
         no = np.zeros(B, np.int32); nv = np.zeros((B, O), np.int32); vt = np.zeros((B, O, V, 2)); dr = np.zeros(B, np.int32)
-        p = lambda a: C.c_void_p(a.ctypes.data)
-        self._check(self._lib.mpc_costmap_to_obstacles(self._h, B, p(cost), sx, sy, float(resolution), p(org), p(pose), float(behind_robot_dist),
-                                                       p(no), p(nv), p(vt), p(dr)))
+        self._check(self._lib.mpc_costmap_to_obstacles(self._h, B, _addr(cost), sx, sy, float(resolution), _addr(org), _addr(pose), float(behind_robot_dist),
+                                                       _addr(no), _addr(nv), _addr(vt), _addr(dr)))
         return no, nv, vt, dr
 
     def last_candidates(self, B: int):
         """(winner[B], iters_total[B]) of the most recent solve (mpc_last_candidates): index of the candidate initial trajectory that
         supplied each instance's result (-1: none converged) and the iterations spent over all candidates of the instance."""
         win = np.empty(B, np.int32); tot = np.empty(B, np.int32)
-        self._check(self._lib.mpc_last_candidates(self._h, int(B), C.c_void_p(win.ctypes.data), C.c_void_p(tot.ctypes.data)))
+        self._check(self._lib.mpc_last_candidates(self._h, int(B), _addr(win), _addr(tot)))
         return win, tot
 
     def check_feasibility(self, x, cost, resolution, origin, footprint_spec, inscribed_radius, min_resolution_collision_check_angular=0.3, look_ahead_idx=-1):
@@ -395,26 +378,24 @@ class BatchSolver:
         org = np.ascontiguousarray(origin, dtype=np.float64).reshape(B, 2)
         spec = np.ascontiguousarray(footprint_spec, dtype=np.float64).reshape(-1, 2)
         out = np.zeros(B, np.int32)
-        p = lambda a: C.c_void_p(a.ctypes.data)
-        self._check(self._lib.mpc_check_feasibility(self._h, B, p(x), p(cost), sx, sy, float(resolution), p(org), p(spec), int(spec.shape[0]),
-                                                    float(inscribed_radius), float(min_resolution_collision_check_angular), int(look_ahead_idx), p(out)))
+        self._check(self._lib.mpc_check_feasibility(self._h, B, _addr(x), _addr(cost), sx, sy, float(resolution), _addr(org), _addr(spec), int(spec.shape[0]),
+                                                    float(inscribed_radius), float(min_resolution_collision_check_angular), int(look_ahead_idx), _addr(out)))
         return out
 
     def grid_update_device(self, B: int, x0_new: Optional[int], x: int, u: int, dt: int, adapt: bool = False, n_min: int = 3, n_max: int = 0, dt_hyst_ratio: float = 0.1):
         """mpc_grid_update_device: warm-start shift (fixed grid) / single-step grid adaptation + resampling (variable grid) of a whole batch, in place
         on device arrays (addresses)."""
-        v = lambda p: C.c_void_p(p) if p else None
-        self._check(self._lib.mpc_grid_update_device(self._h, int(B), v(x0_new), v(x), v(u), v(dt), int(bool(adapt)), int(n_min), int(n_max or self.n), float(dt_hyst_ratio)))
+        self._check(self._lib.mpc_grid_update_device(self._h, int(B), _dev(x0_new), _dev(x), _dev(u), _dev(dt), int(bool(adapt)), int(n_min), int(n_max or self.n), float(dt_hyst_ratio)))
 
     def grid_sizes(self, B: int):
         out = np.zeros(B, np.int32)
-        self._check(self._lib.mpc_get_grid_sizes(self._h, int(B), C.c_void_p(out.ctypes.data)))
+        self._check(self._lib.mpc_get_grid_sizes(self._h, int(B), _addr(out)))
         return out
 
     def last_rows_dropped(self, B: int):
         """per instance: clearance rows that did not fit into max_obstacle_rows in the most recent solve (mpc_last_rows_dropped)"""
         out = np.zeros(B, np.int32)
-        self._check(self._lib.mpc_last_rows_dropped(self._h, int(B), C.c_void_p(out.ctypes.data)))
+        self._check(self._lib.mpc_last_rows_dropped(self._h, int(B), _addr(out)))
         return out
 
     def synchronize(self):

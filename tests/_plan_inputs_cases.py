@@ -4,35 +4,23 @@ one parameter set, one plan_stride, and the instances that run under them as one
 import ctypes as C
 import math
 import os
-import subprocess
 
 import numpy as np
 
+import _harness
 from mpc_local_planner_amd._abi import MpcPlanParams
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-SRC = os.path.join(HERE, "host_harness", "plan_inputs_host.cpp")
-BUILD = os.path.join(HERE, "host_harness", "_build")
-OUT = os.path.join(BUILD, "libmpc_plan_inputs.so")
-DEPS = [SRC, os.path.join(ROOT, "mpc_local_planner_amd", "csrc", "mpc_plan_inputs.hpp"), os.path.join(ROOT, "mpc_local_planner_amd", "csrc", "mpc_controller_cycle.hpp"),
-        os.path.join(ROOT, "include", "mpc_controller.hpp"), os.path.join(ROOT, "include", "mpc_hip.h")]
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BUILD = _harness.BUILD
 MAX_VIA = 4          # cfg.max_via_points of the handle the GPU tests create
 dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
 _lib = None
 
 
-def stale(out):
-    return not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in DEPS)
-
-
 def harness():
     global _lib
     if _lib is None:
-        if stale(OUT):
-            os.makedirs(BUILD, exist_ok=True)
-            subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", SRC, "-o", OUT], check=True)
-        lib = C.CDLL(OUT)
+        lib = C.CDLL(_harness.shared("plan_inputs_host"))
         pp = C.POINTER(MpcPlanParams)
         lib.pin_batch.argtypes = [C.c_int, pp, dp, ip, C.c_int, dp, ip, dp, ip, C.c_int, C.c_int, ip, dp, ip, ip]
         lib.pin_facade.argtypes = [pp, dp, C.c_int, dp, ip, dp, ip, C.c_int, C.c_int, ip, dp, ip, ip]

@@ -13,7 +13,6 @@ import ctypes as C
 import dataclasses
 import functools
 import os
-import subprocess
 from typing import Callable, Optional
 
 import numpy as np
@@ -24,6 +23,7 @@ from oracle import kkt_check as KC
 from oracle import se2_nlp as R
 from mpc_local_planner_amd import _abi as A
 from mpc_local_planner_amd import workloads as W
+import _harness
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 B = 12                      # instances per case (one launch on the device)
@@ -226,14 +226,7 @@ def history(name):
 # ---- the C oracle and the host build of the kernel core ---------------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def _host_lib():
-    src = os.path.join(HERE, "host_harness", "host_solver.cpp")
-    out = os.path.join(HERE, "host_harness", "_build", "libmpc_hostdbg.so")
-    csrc = os.path.join(HERE, "..", "mpc_local_planner_amd", "csrc")
-    deps = [src, os.path.join(HERE, "host_harness", "ipm_serial.hpp"), os.path.join(csrc, "mpc_core.hpp"), os.path.join(csrc, "mpc_problem.hpp"), os.path.join(HERE, "..", "include", "mpc_hip.h")]
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in deps):          # the rule of tests/test_host_core.py: one library for both
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", src, "-o", out], check=True)
-    return C.CDLL(out)
+    return C.CDLL(_harness.shared("host_solver"))          # the harness of tests/test_host_core.py: one library for both
 
 
 def _groups(ng):

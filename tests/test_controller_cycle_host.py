@@ -2,38 +2,24 @@
 tests-only harness (tests/host_harness/controller_cycle_host.cpp): the guess a re-initialised slot builds from its plan equals, bit for bit, two independent codes --
 oracle.se2_nlp (generate_initial_state_trajectory + initialize_sequences_xinit) and the facade's initial_state_trajectory (include/mpc_controller.hpp) --; the
 re-initialisation decision equals a numpy restatement of src/controller.cpp:152-158 on a scripted sequence that hits every cause just above and just below its
-threshold; struct mpc_cycle_params has the C layout; and the harness, built as a stand-alone program with -fsanitize=address,undefined, runs its own cases clean."""
+threshold; and the harness, built as a stand-alone program with -fsanitize=address,undefined, runs its own cases clean."""
 import ctypes as C
 import math
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import se2_nlp as R
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-SRC = os.path.join(HERE, "host_harness", "controller_cycle_host.cpp")
-BUILD = os.path.join(HERE, "host_harness", "_build")
-OUT = os.path.join(BUILD, "libmpc_controller_cycle.so")
-DEPS = [SRC, os.path.join(ROOT, "mpc_local_planner_amd", "csrc", "mpc_controller_cycle.hpp"), os.path.join(ROOT, "include", "mpc_controller.hpp")]
+import _harness
 
 FIRST, NUM_STEPS, GOAL_DIST, GOAL_ANGULAR, RESET = 1, 2, 4, 8, 16      # MPC_REINIT_* of include/mpc_hip.h
 dp = C.POINTER(C.c_double)
 
 
-def _stale(out):
-    return not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in DEPS)
-
-
 @pytest.fixture(scope="module")
 def h():
-    if _stale(OUT):
-        os.makedirs(BUILD, exist_ok=True)
-        subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", SRC, "-o", OUT], check=True)
-    lib = C.CDLL(OUT)
+    lib = C.CDLL(_harness.shared("controller_cycle_host"))
     lib.cyc_atan2.restype = C.c_double
     lib.cyc_atan2.argtypes = [C.c_double, C.c_double]
     lib.cyc_dt_sample.restype = C.c_double
@@ -202,21 +188,6 @@ def test_state_estimate_and_sampling_spacing(h):
         assert h.cyc_dt_sample(*args, 0.3) == 0.3, args
 
 
-def test_cycle_params_struct_layout_matches_c(tmp_path):
-    from mpc_local_planner_amd._abi import MpcCycleParams
-    fields = [f[0] for f in MpcCycleParams._fields_]
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "mpc_hip.h"\nint main(){\nprintf("%zu\\n", sizeof(mpc_cycle_params));\n' +
-                   "".join('printf("%%zu\\n", offsetof(mpc_cycle_params,%s));\n' % f for f in fields) + 'return 0;}\n')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    out = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert out[0] == C.sizeof(MpcCycleParams)
-    assert len(out) == 1 + len(fields) == 1 + 14
-    for f, o in zip(fields, out[1:]):
-        assert getattr(MpcCycleParams, f).offset == o, f
-
-
 def test_cycle_params_reader_fills_the_struct_from_the_reference_keys():
     from mpc_local_planner_amd import params
     p = params.cycle_params_from_dict({"controller": {"outer_ocp_iterations": 2, "force_reinit_num_steps": 7, "force_reinit_new_goal_dist": 0.8, "prefer_x_feedback": True},
@@ -234,11 +205,7 @@ def test_cycle_params_reader_fills_the_struct_from_the_reference_keys():
 
 def test_harness_runs_clean_under_address_and_undefined_sanitizers():
     """the stand-alone program (own main, own sampling and decision cases) built with -fsanitize=address,undefined; nothing sanitized is loaded into Python"""
-    exe = os.path.join(BUILD, "controller_cycle_sanitized")
-    if _stale(exe):
-        os.makedirs(BUILD, exist_ok=True)
-        subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-DCYC_MAIN", SRC, "-o", exe],
-                       check=True)
+    exe = _harness.sanitized("controller_cycle_host", ("CYC_MAIN",))
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "410 cases, 0 differ" in r.stdout and "runtime error" not in r.stderr

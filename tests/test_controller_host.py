@@ -1,25 +1,17 @@
 """CPU test of the C++ Controller facade's host logic (include/mpc_controller.hpp) against the oracle's restatement
 of Controller::generateInitialStateTrajectory + initializeSequences(xinit)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import se2_nlp as R
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "host_harness", "controller_host.cpp")
-OUT = os.path.join(HERE, "host_harness", "_build", "libctl_host.so")
+import _harness
 
 
 @pytest.fixture(scope="module")
 def lib():
-    os.makedirs(os.path.dirname(OUT), exist_ok=True)
-    # the facade only needs the ABI's declarations here: link lazily, the tested functions make no library calls
-    subprocess.run(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-Wl,--unresolved-symbols=ignore-all", SRC, "-o", OUT], check=True)
-    l = C.CDLL(OUT)
+    l = C.CDLL(_harness.shared("controller_host"))      # lazily linked: the facade only needs the ABI's declarations here, the tested functions make no library calls
     l.ctl_interpolate_angle.restype = C.c_double
     l.ctl_interpolate_angle.argtypes = [C.c_double] * 3
     l.ctl_resample.restype = C.c_double

@@ -12,27 +12,17 @@ import numpy as np
 import pytest
 
 import _evaluate_cases as E
+import _harness
 from mpc_local_planner_amd import _abi as A
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-SRC = os.path.join(HERE, "host_harness", "evaluate_host.cpp")
-BUILD = os.path.join(HERE, "host_harness", "_build")
-OUT = os.path.join(BUILD, "libmpc_evaluate_host.so")
 CSRC = os.path.join(ROOT, "mpc_local_planner_amd", "csrc")
-DEPS = [SRC, os.path.join(CSRC, "mpc_evaluate.hpp"), os.path.join(CSRC, "mpc_core.hpp"), os.path.join(ROOT, "include", "mpc_hip.h")]
-
-
-def _stale(out):
-    return not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in DEPS)
 
 
 @pytest.fixture(scope="module")
 def h():
-    if _stale(OUT):
-        os.makedirs(BUILD, exist_ok=True)
-        subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", SRC, "-o", OUT], check=True)
-    lib = C.CDLL(OUT)
+    lib = C.CDLL(_harness.shared("evaluate_host"))
     lib.evh_evaluate.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 8 + [C.POINTER(A.MpcObstacles), C.c_void_p, C.c_void_p, C.POINTER(A.MpcEvalOut)]
     lib.evh_evaluate.restype = C.c_int
     return lib
@@ -179,9 +169,8 @@ def test_a_nan_gives_nan_outputs_for_its_instance_only(h):
     assert (got["closest"][hit] == -1).all() and np.array_equal(got["closest"][~hit], clean["closest"][~hit])
 
 
-def test_stand_alone_harness_runs_clean_under_the_sanitizers(tmp_path):
-    exe = str(tmp_path / "evaluate_host")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DEVALUATE_HOST_MAIN", SRC, "-o", exe], check=True)
+def test_stand_alone_harness_runs_clean_under_the_sanitizers():
+    exe = _harness.sanitized("evaluate_host", ("EVALUATE_HOST_MAIN",), recover="all")
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0 and r.stderr == "", r.stderr
     rows = [l.split() for l in r.stdout.splitlines()]

@@ -428,8 +428,8 @@ def test_no_uninitialised_lds_reads(m, tmp_path):
     for a 0 * garbage = NaN bug that only showed up when a previous kernel had left NaN patterns in LDS)."""
     import subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    so = str(tmp_path / "libmpc_hip_poison.so")
     from mpc_local_planner_amd import _lib
+    so = os.path.join(_lib.CSRC, "libmpc_hip_poison.so")          # next to the product library: compiled when a source, a header or a flag changed, not on every run
     _lib.build(extra_flags=["-DMPC_POISON_LDS"], out=so)          # the split build of the product library with one more flag (parallel: ~25 s)
     # round-2 paths: candidates (kernel-generated seeds), kept multipliers, a turning footprint against polygons and a dynamic obstacle -- results of
     # the normal library (this process) must be reproduced bit for bit by the poisoned build (the subprocess)

@@ -4,7 +4,6 @@ This is a developer check of the kernel's arithmetic without a GPU -- the harnes
 package and is never loaded by it."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,21 +11,15 @@ import pytest
 from oracle import se2_nlp as R
 from mpc_local_planner_amd import _abi as A
 from mpc_local_planner_amd import workloads as W
+import _harness
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "host_harness", "host_solver.cpp")
-OUT = os.path.join(HERE, "host_harness", "_build", "libmpc_hostdbg.so")
 GOLD = os.path.join(HERE, "golden")
 
 
 @pytest.fixture(scope="module")
 def host():
-    csrc = os.path.join(HERE, "..", "mpc_local_planner_amd", "csrc")
-    deps = [SRC, os.path.join(HERE, "host_harness", "ipm_serial.hpp"), os.path.join(csrc, "mpc_core.hpp"), os.path.join(csrc, "mpc_problem.hpp"), os.path.join(HERE, "..", "include", "mpc_hip.h")]
-    if not os.path.exists(OUT) or os.path.getmtime(OUT) < max(os.path.getmtime(d) for d in deps):
-        os.makedirs(os.path.dirname(OUT), exist_ok=True)
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", SRC, "-o", OUT], check=True)
-    return C.CDLL(OUT)
+    return C.CDLL(_harness.shared("host_solver"))
 
 
 def host_solve(lib, cfg, x0, xf, up, dtp, init=None):

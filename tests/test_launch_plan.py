@@ -3,17 +3,11 @@ by a tests-only harness (tests/host_harness/launch_plan_host.cpp): for every con
 handle launches, the two-wave choice at 4095 / 4096 instances and the pool size on a fake device, or the text mpc_create refuses it with.  The table was recorded from
 the decision code of mpc_capi.hip before the plan existed; it changes only when a rule does."""
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 
 from mpc_local_planner_amd import _abi as A
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "host_harness", "launch_plan_host.cpp")
-OUT = os.path.join(HERE, "host_harness", "_build", "libmpc_launch_plan.so")
-CSRC = os.path.join(HERE, "..", "mpc_local_planner_amd", "csrc")
+import _harness
 
 CANDS = dict(candidates=(A.CAND_REFERENCE, A.CAND_HERMITE_FF, A.CAND_HERMITE_FR), candidate_max_iter=(40, 40, 40), candidate_param=(0.0, 2.0, 1.5))
 LINE_MOVING = dict(footprint_kind=2, footprint_params=(0.0, 0.0, 0.4, 0.0), enable_dynamic_obstacles=True, max_obstacles=3, max_vertices=1, max_obstacle_rows=4)
@@ -125,11 +119,7 @@ TABLE = {
 
 @pytest.fixture(scope="module")
 def plan():
-    deps = [SRC] + [os.path.join(CSRC, f) for f in ("mpc_launch_plan.hpp", "mpc_layout.hpp", "mpc_problem.hpp", "mpc_core.hpp")] + [os.path.join(HERE, "..", "include", "mpc_hip.h")]
-    if not os.path.exists(OUT) or os.path.getmtime(OUT) < max(os.path.getmtime(d) for d in deps):
-        os.makedirs(os.path.dirname(OUT), exist_ok=True)
-        subprocess.run(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", SRC, "-o", OUT], check=True)
-    lib = C.CDLL(OUT)
+    lib = C.CDLL(_harness.shared("launch_plan_host"))
     lib.plan_row.restype = C.c_int
     return lib
 

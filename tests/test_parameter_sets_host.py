@@ -4,16 +4,11 @@ mpc_create keeps for the handle and mpc_set_parameter_sets uploads for every set
 import ctypes as C
 import os
 import shutil
-import subprocess
 
 import pytest
 
 from mpc_local_planner_amd import _abi as A
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "host_harness", "parameter_sets_host.cpp")
-OUT = os.path.join(HERE, "host_harness", "_build", "libmpc_parameter_sets.so")
-CSRC = os.path.join(HERE, "..", "mpc_local_planner_amd", "csrc")
+import _harness
 
 CANDS = dict(candidates=(A.CAND_REFERENCE, A.CAND_HERMITE_FF, A.CAND_HERMITE_FR), candidate_max_iter=(40, 40, 40), candidate_param=(0.0, 2.0, 1.5))
 CIRCLE = dict(footprint_kind=1, footprint_radius=0.3, max_obstacles=6, max_vertices=1, max_obstacle_rows=4)
@@ -65,11 +60,7 @@ WALK = {
 
 @pytest.fixture(scope="module")
 def h():
-    deps = [SRC] + [os.path.join(CSRC, f) for f in ("mpc_launch_plan.hpp", "mpc_layout.hpp", "mpc_problem.hpp", "mpc_core.hpp")] + [os.path.join(HERE, "..", "include", "mpc_hip.h")]
-    if not os.path.exists(OUT) or os.path.getmtime(OUT) < max(os.path.getmtime(d) for d in deps):
-        os.makedirs(os.path.dirname(OUT), exist_ok=True)
-        subprocess.run(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", SRC, "-o", OUT], check=True)
-    lib = C.CDLL(OUT)
+    lib = C.CDLL(_harness.shared("parameter_sets_host"))
     lib.named_bytes.restype = C.c_int64
     lib.record_bytes.restype = C.c_int64
     return lib

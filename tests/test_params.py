@@ -259,15 +259,11 @@ OPT_NAMES = ["grid_adaptation", "max_grid_size", "dt_hyst_ratio", "min_grid_size
 
 @pytest.fixture(scope="module")
 def cpp():
-    import subprocess
     from mpc_local_planner_amd import _lib
     _lib.load()
     C.CDLL(_lib.LIB_PATH, mode=C.RTLD_GLOBAL)          # mpc_config_defaults for the lazily linked harness
-    src = os.path.join(HERE, "host_harness", "params_host.cpp")
-    out = os.path.join(HERE, "host_harness", "_build", "libctl_params.so")
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    subprocess.run(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-Wl,--unresolved-symbols=ignore-all", src, "-o", out], check=True)
-    lib = C.CDLL(out)
+    import _harness
+    lib = C.CDLL(_harness.shared("params_host"))
     lib.ctl_config_from_params.restype = C.c_int
     lib.ctl_config_from_params.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(A.MpcConfig), C.c_void_p, C.c_char_p, C.c_int]
     return lib

@@ -2,7 +2,7 @@
 a tests-only harness (tests/host_harness/plan_inputs_host.cpp): on scripted and random plans every discrete output (front, goal index, n_plan, n_via, flags) and every copied
 pose equals, exactly, what the facade's prune_global_plan, transform_global_plan and via_points_from_plan (include/mpc_controller.hpp) plus a literal restatement of
 src/mpc_local_planner_ros.cpp:312-354 give; the local goal's heading is held to the facade's estimate_local_goal_orientation (libm) within a bound measured here; the
-double-double atan2 of this header equals cc_atan2 bit for bit; struct mpc_plan_params has the C layout; and the harness, built as a stand-alone program with
+double-double atan2 of this header equals cc_atan2 bit for bit; and the harness, built as a stand-alone program with
 -fsanitize=address,undefined, runs its own cases clean."""
 import ctypes as C
 import math
@@ -12,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import _harness
 import _plan_inputs_cases as K
 from mpc_local_planner_amd._abi import (PLAN_EMPTY, PLAN_GOAL_INJECTED, PLAN_GOAL_REACHED, PLAN_TRUNCATED, PLAN_VIA_DROPPED, CMD_GOAL_REACHED, CMD_INFEASIBLE, CMD_NOT_FINITE,
                                         CMD_PLAN_EMPTY, CMD_SOLVE_FAILED, CMD_SUCCESS)
@@ -223,25 +224,6 @@ def test_commands_equal_the_restatement_over_three_calls(h):
     assert all(int(res[b]) == _commands_numpy(tuple(u[b, 0]), int(st[b]), 1, 0, 0)[1] for b in range(B))
 
 
-def test_plan_params_struct_layout_matches_c(tmp_path):
-    from mpc_local_planner_amd._abi import MpcPlanParams
-    fields = [f[0] for f in MpcPlanParams._fields_]
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "mpc_hip.h"\nint main(){\nprintf("%zu\\n", sizeof(mpc_plan_params));\n' +
-                   "".join('printf("%%zu\\n", offsetof(mpc_plan_params,%s));\n' % f for f in fields) +
-                   'printf("%d %d %d %d %d\\n", MPC_PLAN_GOAL_REACHED, MPC_PLAN_EMPTY, MPC_PLAN_TRUNCATED, MPC_PLAN_VIA_DROPPED, MPC_PLAN_GOAL_INJECTED);\n'
-                   'printf("%d %d %d %d %d %d\\n", MPC_CMD_SUCCESS, MPC_CMD_GOAL_REACHED, MPC_CMD_PLAN_EMPTY, MPC_CMD_SOLVE_FAILED, MPC_CMD_INFEASIBLE, MPC_CMD_NOT_FINITE);\nreturn 0;}\n')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", os.path.join(K.ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    out = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert out[0] == C.sizeof(MpcPlanParams)
-    assert len(out) == 1 + len(fields) + 11 and len(fields) == 10
-    for f, o in zip(fields, out[1:]):
-        assert getattr(MpcPlanParams, f).offset == o, f
-    assert out[1 + len(fields):] == [PLAN_GOAL_REACHED, PLAN_EMPTY, PLAN_TRUNCATED, PLAN_VIA_DROPPED, PLAN_GOAL_INJECTED, CMD_SUCCESS, CMD_GOAL_REACHED, CMD_PLAN_EMPTY,
-                                     CMD_SOLVE_FAILED, CMD_INFEASIBLE, CMD_NOT_FINITE]
-
-
 def test_plan_params_readers_fill_the_struct_from_the_plugin_options():
     from mpc_local_planner_amd import params
     o = params.plugin_options_from_params({"controller": {"xy_goal_tolerance": 0.3, "global_plan_viapoint_sep": 0.5, "global_plan_overwrite_orientation": False}})
@@ -264,11 +246,7 @@ def test_plan_params_readers_fill_the_struct_from_the_plugin_options():
 
 def test_harness_runs_clean_under_address_and_undefined_sanitizers():
     """the stand-alone program (own main, own scripted and random plans, commands) built with -fsanitize=address,undefined; nothing sanitized is loaded into Python"""
-    exe = os.path.join(K.BUILD, "plan_inputs_sanitized")
-    if K.stale(exe):
-        os.makedirs(K.BUILD, exist_ok=True)
-        subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-DPIN_MAIN", K.SRC, "-o", exe],
-                       check=True)
+    exe = _harness.sanitized("plan_inputs_host", ("PIN_MAIN",))
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "333 cases, 0 differ" in r.stdout and "runtime error" not in r.stderr

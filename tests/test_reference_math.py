@@ -5,13 +5,13 @@ computes (generator: tests/golden/make_ref_math_vectors.py).  Held to it bit for
 image lacks: the oracle's restatements of those files are UNPINNED.  CPU only."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import se2_nlp as R
 from oracle import ref_math as RM
+import _harness
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 G = np.load(os.path.join(HERE, "golden", "ref_math_utils.npz"))
@@ -50,11 +50,7 @@ def test_angle_helpers_reproduce_the_reference_bit_for_bit():
 
 @pytest.fixture(scope="module")
 def host():
-    src = os.path.join(HERE, "host_harness", "host_solver.cpp")
-    out = os.path.join(HERE, "host_harness", "_build", "libmpc_hostdbg_pin.so")
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", src, "-o", out], check=True)
-    lib = C.CDLL(out)
+    lib = C.CDLL(_harness.shared("host_solver"))
     lib.hostdbg_normalize_theta.restype = C.c_double
     lib.hostdbg_normalize_theta.argtypes = [C.c_double]
     return lib
@@ -68,11 +64,7 @@ def test_kernel_core_angle_wrap_reproduces_the_reference(host):
 
 def test_facade_interpolate_angle_reproduces_the_reference():
     """include/mpc_controller.hpp::interpolate_angle (the facade's resampling / warm-start extrapolation)"""
-    src = os.path.join(HERE, "host_harness", "controller_host.cpp")
-    out = os.path.join(HERE, "host_harness", "_build", "libctl_host_pin.so")
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    subprocess.run(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-Wl,--unresolved-symbols=ignore-all", src, "-o", out], check=True)
-    lib = C.CDLL(out)
+    lib = C.CDLL(_harness.shared("controller_host"))
     lib.ctl_interpolate_angle.restype = C.c_double
     lib.ctl_interpolate_angle.argtypes = [C.c_double] * 3
     ours = np.array([lib.ctl_interpolate_angle(float(a), float(b), float(f)) for a, b, f in zip(G["a1"], G["a2"], G["factor"])])

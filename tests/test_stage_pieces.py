@@ -6,16 +6,12 @@ INOUT piece (and no OUT piece) inside the range of the one copy to the device, e
 NULL for an absent piece, and a total that is the end of the last piece."""
 import ctypes as C
 import itertools
-import os
 import random
-import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "host_harness", "stage_pieces_host.cpp")
-OUT = os.path.join(HERE, "host_harness", "_build", "libmpc_stage_pieces.so")
-CSRC = os.path.join(HERE, "..", "mpc_local_planner_amd", "csrc")
+import _harness
+
 
 IN, INOUT, OUT_ = 0, 1, 2
 SIZES = (0, 1, 255, 256, 257, 16384 * 24)
@@ -25,11 +21,7 @@ ONE = [(d, g, b) for d in (IN, INOUT, OUT_) for g in (0, 1) for b in SIZES]     
 
 @pytest.fixture(scope="module")
 def h():
-    deps = [SRC] + [os.path.join(CSRC, f) for f in ("mpc_problem.hpp", "mpc_core.hpp")] + [os.path.join(HERE, "..", "include", "mpc_hip.h")]
-    if not os.path.exists(OUT) or os.path.getmtime(OUT) < max(os.path.getmtime(d) for d in deps):
-        os.makedirs(os.path.dirname(OUT), exist_ok=True)
-        subprocess.run(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", SRC, "-o", OUT], check=True)
-    lib = C.CDLL(OUT)
+    lib = C.CDLL(_harness.shared("stage_pieces_host"))
     lib.check_list.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.c_int, C.c_char_p, C.c_int]
     lib.check_list.restype = C.c_int
     return lib

@@ -4,17 +4,12 @@ present; mpc_solve_batch / mpc_step_batch pack with the same function.  For ever
 and every piece starts on a 256-byte boundary."""
 import ctypes as C
 import itertools
-import os
-import subprocess
 
 import pytest
 
 from mpc_local_planner_amd import _abi as A
+import _harness
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "host_harness", "step_pieces_host.cpp")
-OUT = os.path.join(HERE, "host_harness", "_build", "libmpc_step_pieces.so")
-CSRC = os.path.join(HERE, "..", "mpc_local_planner_amd", "csrc")
 
 MAX_BATCH = 16384
 OPTIONAL = ("u_prev", "dt_prev", "init", "radius", "velocity")      # bit i of the flags: the call passes that array (init: x_init, u_init and dt_init)
@@ -23,11 +18,7 @@ OBSTACLES = {"O0": dict(), "O1_V1": dict(max_obstacles=1, max_vertices=1), "O3_V
 
 @pytest.fixture(scope="module")
 def h():
-    deps = [SRC] + [os.path.join(CSRC, f) for f in ("mpc_problem.hpp", "mpc_core.hpp")] + [os.path.join(HERE, "..", "include", "mpc_hip.h")]
-    if not os.path.exists(OUT) or os.path.getmtime(OUT) < max(os.path.getmtime(d) for d in deps):
-        os.makedirs(os.path.dirname(OUT), exist_ok=True)
-        subprocess.run(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", SRC, "-o", OUT], check=True)
-    lib = C.CDLL(OUT)
+    lib = C.CDLL(_harness.shared("step_pieces_host"))
     lib.check_call.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_char_p, C.c_int]
     lib.check_call.restype = C.c_int
     return lib

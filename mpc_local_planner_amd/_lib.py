@@ -26,6 +26,17 @@ def _hipcc() -> str:
     return "hipcc"      # none here: an up-to-date library still loads (the stamp does not hold the compiler's path); a build that is needed fails in _make
 
 
+# the compile flags of every object of the split build.  -disable-lsr: LLVM's loop strength reduction gives every LDS pointer of the (manually software-pipelined) stage
+# loops two or three induction variables plus a re-materialised base; without it the loops keep the one pointer per stream the source has (headline kernel -3.8 %,
+# profiles/r03_lsr_ab.log)
+SPLIT_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-DMPC_SPLIT_BUILD", "-mllvm", "-disable-lsr"]
+
+
+def inst_flags(t: str, model: int) -> list:
+    """what makes mpc_solve_inst.hip the object of one (arithmetic type, model) pair"""
+    return ["-DMPC_SOLVE_INST", f"-DMPC_INST_T={t}", f"-DMPC_INST_MODEL={model}"]
+
+
 def _make(out, commands, force, verbose) -> str:
     try:
         _build.build(out, commands, CSRC, force=force, verbose=verbose)
@@ -38,8 +49,9 @@ def build(force: bool = False, verbose: bool = False, extra_flags=(), out: str |
     """hipcc --offload-arch=gfx950 -> csrc/libmpc_hip.so (cross-compiles without a GPU).
 
     Split build: the ABI + the small kernels (mpc_capi.hip) and one object per (arithmetic type, model) pair of the solve kernel
-    (mpc_solve_inst.hip, three kernel instantiations each) are compiled in parallel, then linked.  A plain
-    `hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared mpc_capi.hip -o libmpc_hip.so` gives the same library from one translation unit."""
+    (mpc_solve_inst.hip, three kernel instantiations each) are compiled in parallel, then linked.  Nothing else writes libmpc_hip.so.
+    mpc_capi.hip without -DMPC_SPLIT_BUILD still compiles as ONE translation unit: a developer build (-DMPC_DEV_ONE_MODEL=<model> for a quick compile,
+    assembly inspection) under another output name, not the same library (no -disable-lsr unless given, everything inlined in one module)."""
     if out is None:      # the measurement-only micro-benchmark rides along with the product library, but never stands in its way (ADVICE r04)
         try:
             build_ubench(force=force, verbose=verbose)
@@ -47,14 +59,11 @@ def build(force: bool = False, verbose: bool = False, extra_flags=(), out: str |
             print(f"mpc_local_planner_amd: libmpc_ubench.so not built ({e}); bench.py will report the data-sheet peaks only")
     out = out or LIB_PATH                      # another `out` (+ extra_flags): an instrumented copy next to the product library (tests), rebuilt by the same rule
     objdir = os.path.join(CSRC, "_obj") if out == LIB_PATH else out + ".obj"
-    # -disable-lsr: LLVM's loop strength reduction gives every LDS pointer of the (manually software-pipelined) stage loops two or three induction variables plus a
-    # re-materialised base; without it the loops keep the one pointer per stream the source has (headline kernel -3.8 %, profiles/r03_lsr_ab.log)
-    base = [_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-DMPC_SPLIT_BUILD", "-mllvm", "-disable-lsr"] + list(extra_flags)
+    base = [_hipcc()] + SPLIT_FLAGS + list(extra_flags)
     jobs = [(base + ["-c", os.path.join(CSRC, "mpc_capi.hip"), "-o", os.path.join(objdir, "mpc_capi.o")])]
     for t in ("double", "float"):
         for model in range(4):
-            jobs.append(base + ["-DMPC_SOLVE_INST", f"-DMPC_INST_T={t}", f"-DMPC_INST_MODEL={model}", "-c", os.path.join(CSRC, "mpc_solve_inst.hip"),
-                                "-o", os.path.join(objdir, f"mpc_solve_{t}_{model}.o")])
+            jobs.append(base + inst_flags(t, model) + ["-c", os.path.join(CSRC, "mpc_solve_inst.hip"), "-o", os.path.join(objdir, f"mpc_solve_{t}_{model}.o")])
     link = [_hipcc(), "--offload-arch=gfx950", "-fPIC", "-shared"] + [j[-1] for j in jobs] + ["-o", out]
     return _make(out, jobs + [link], force, verbose)      # all or nothing: the nine objects and the link, when any dependency of any of them moved
 

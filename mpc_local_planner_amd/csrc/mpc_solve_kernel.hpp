@@ -74,10 +74,7 @@ void mpc_ipm_wave_kernel(
     if (run) {
         mpc::WaveLayout Lv = L;            // from the kernel arguments: wave-uniform, lives in SGPRs
         Lv.n = __builtin_amdgcn_readfirstlane(n);
-#ifdef MPC_POISON_LDS      // developer check: any read of an LDS word the solver did not write first turns into NaN
-        for (int e = lane; e < L.total; e += mpc::kWave) sm[e] = T(NAN);
-        __syncthreads();
-#endif
+        MPC_DBG_POISON(sm, L.total, lane);      // (developer check: any read of an LDS word the solver did not write first turns into NaN)
         if (set_of) {
             // parameter sets in force: the instance's problem record is entry set_of[inst] of the handle's table, copied by the wave in 16-byte pieces; lane 0
             // puts the instance's grid size into its piece on the way.  Without sets: the by-value record of the handle's own configuration, as before

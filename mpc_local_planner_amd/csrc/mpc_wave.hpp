@@ -22,6 +22,7 @@
 // File map (r05: one struct, six parts -- the .inc files are included INSIDE struct IpmWave):
 //   mpc_layout.hpp        WaveLayout / FixedLayout / GlobalStage (plain C++: the host plans launches with them, mpc_launch_plan.hpp)
 //   mpc_wave_layout.hpp   stage-record slot tables, wavefront reductions
+//   mpc_wave_debug.hpp    every developer switch (profile counters, NaN census, sweep cross-check, LDS poison, assembly markers) as macros that are empty in the product build
 //   mpc_wave.hpp          this file: members, accessors, sweep-pointer abstraction (LDS or global memory)
 //   mpc_wave_rows.inc     terminal ball, via-points, clearance rows (geometry, footprints, association)
 //   mpc_wave_passes.inc   point evaluation, line-search trials, KKT error + stage records, condensed barrier terms
@@ -36,13 +37,8 @@
 #include "mpc_core.hpp"
 #include "mpc_dpp_blocks.inc"
 
-#ifdef MPC_PROFILE
-namespace mpc { constexpr int kProfCols = 26, kProfTicks = 14; }      // words per workgroup / phase + glue counters among them (mpc_wave_debug.hpp has the map)
-__device__ long long g_mpc_prof[4096][mpc::kProfCols];
-#endif
-
-#include "mpc_wave_layout.hpp"
 #include "mpc_wave_debug.hpp"
+#include "mpc_wave_layout.hpp"
 
 namespace mpc {
 
@@ -78,11 +74,7 @@ struct IpmWave {
     int nvia = 0;   // via-points of this instance
     int flags;      // bits 0..2 xf_fixed, 3 dt_free, 4 quadratic objective, 5 has_Qf, 6..9 rate_on, 10 terminal ball, 11 via-points, 12 footprint that turns with the pose (line, two circles), 13 integral form with dt free, 14 dynamic obstacles: the problem record lives in LDS and every
                     // P.x costs a ds_read (+ wait) that the compiler cannot hoist over LDS stores; one scalar register holds the switches
-#ifdef MPC_PROFILE
-    mutable long long prof_mult = 0;
-    mutable long long prof_loop = 0, prof_setup = 0, prof_fwd_loop = 0;    // ticks inside the backward stage loop / before it / inside the forward loop
-    mutable long long prof_pit_pre = 0, prof_fwd_pre = 0, prof_fwd_post = 0;    // partitioned sweeps: backward_pit up to its first stage / forward_pit before and behind its segment loop
-#endif
+    MPC_PROF_MEMBERS     // (developer builds: the sweeps' inner tick counters, mpc_wave_debug.hpp)
     int nfix;
     // candidate initial trajectories: this wave's candidate index, its iteration cap and the instance's winner word (global memory; NULL when
     // the solver runs a single candidate).  A lower winner index than ours = a higher-priority candidate has converged: we stop.

@@ -252,16 +252,8 @@
         for (int i = 0; i < 6; ++i) Vp[i] = Ra[i] * cl.keep;
     }
 
-#ifdef MPC_PIT_VERBOSE
-#define PIT_DBG_W(tag) if (blockIdx.x == MPC_PIT_CHECK) { const double q00 = rd_lane(Wp[0], 9), q01 = rd_lane(Wp[0], 10), q02 = rd_lane(Wp[0], 11), q10 = rd_lane(Wp[1], 9), q11 = rd_lane(Wp[1], 10), q12 = rd_lane(Wp[1], 11), q20 = rd_lane(Wp[2], 9), q22 = rd_lane(Wp[2], 11), o0 = rd_lane(omp, 9); \
-            if (lane == 0) printf("   [%s] Wp0 %.9e %.9e %.9e Wp1 %.9e %.9e %.9e Wp2 %.9e .. %.9e om0 %.9e\n", tag, q00, q01, q02, q10, q11, q12, q20, q22, o0); }
-#else
-#define PIT_DBG_W(tag)
-#endif
     __device__ __forceinline__ int backward_pit(const PitLaneConsts& PC, T delta, T dc, T& dd_out, T nu_out[3]) const {
-#ifdef MPC_PROFILE
-        const long long tp_in = __builtin_readcyclecounter();
-#endif
+        MPC_LAP_BEGIN(t_lap)
         const int n = L.n, N = n - 1, Lm = N >> 2, rem = N - 4 * Lm;
         const T d = SCL(SC_D);
         const int ZC = W_ZC();
@@ -377,10 +369,7 @@
             MPC_DPP_BLOCK_V5
         };
         T Ga[3], Aa[8], Gb[3], Ab[8];
-#ifdef MPC_PROFILE
-        const long long tp0 = __builtin_readcyclecounter();
-        prof_pit_pre += tp0 - tp_in;
-#endif
+        MPC_LAP(pit_pre, t_lap);
         // ---- the N mod 4 leftover stages at the end of the horizon: all rows together (k = N-1 .. 4 Lm)
         if (rem > 0) {
             point_at(N - 1, true);
@@ -414,10 +403,7 @@
             const T w4 = t_fmin(t_fmin(rd_lane(worst, 0), rd_lane(worst, 16)), t_fmin(rd_lane(worst, 32), rd_lane(worst, 48)));
             if (!(w4 > T(0))) return 0;
         }
-#ifdef MPC_PROFILE
-        const long long tp1 = __builtin_readcyclecounter();
-        prof_loop += tp1 - tp0;
-#endif
+        MPC_LAP(bwd_loop, t_lap);
         // ---- hand-off + combine.  Tile (words from TB): [i][lane] V rows 0..5 | [a][lane] wn rows 0..4 | [lane] om
         const int TB = L.DX;
         // (the sync() on either side is what makes the hand-off visible ACROSS lanes: without it the compiler treats the tile as per-thread memory and
@@ -446,22 +432,20 @@
             for (int a = 0; a < 3; ++a) Wp[a] = sm[TB + 96 + 16 * a + c];
             omp = sm[TB + 176 + c];
         }
-        PIT_DBG_W("V3")
+        MPC_DBG_PIT_W("V3")
         const int lm = c < 6 ? c : 0;
         put_tile(2);
         combine<true>(TB, pit_tile(2), comb_of<true>(PC, c, TB), lm, Vp, Wp, omp, wpiv, inert, iok);      // (run-time layout: the per-lane constants are recomputed per step, cheaper than keeping them)
-        PIT_DBG_W("V2")
+        MPC_DBG_PIT_W("V2")
         put_tile(1);
         combine<false>(TB, pit_tile(1), comb_of<false>(PC, c, TB), lm, Vp, Wp, omp, wpiv, inert, iok);
-        PIT_DBG_W("V1")
+        MPC_DBG_PIT_W("V1")
         put_tile(0);
         combine<true>(TB, pit_tile(0), comb_of<true>(PC, c, TB), lm, Vp, Wp, omp, wpiv, inert, iok);
-        PIT_DBG_W("V0")
+        MPC_DBG_PIT_W("V0")
         if constexpr (NSC != 0) inert += pit_combine_inertia(PC, wn, iok);
         MPC_MARK("PIT_COMBINE_END");
-#ifdef MPC_PROFILE
-        prof_setup += __builtin_readcyclecounter() - tp1;
-#endif
+        MPC_LAP(bwd_setup, t_lap);
         if (!(rd_lane(wpiv, 0) > T(1e-9)) || !iok) return 0;           // a pivot of I - W P+ (or of the inertia count) broke down: the caller repeats this factorisation with the serial sweep
         // ---- root: the value function at stage 0 has its P columns in lane set B (lane 15 = column 5)
         RicState<T> Vr;
@@ -479,19 +463,13 @@
             Vr.W[0][2] = Vr.W[2][0] = T(0.5) * (w02 + w20);
             Vr.W[1][2] = Vr.W[2][1] = T(0.5) * (w12 + w21);
         }
-#ifdef MPC_PIT_VERBOSE
-        if (blockIdx.x == MPC_PIT_CHECK && lane == 0)
-            printf("  %s root: P55 %.10e p5 %.10e S5 %.10e %.10e %.10e om %.10e %.10e %.10e W %.10e %.10e %.10e %.10e %.10e %.10e\n", "pit   ", (double)Vr.P[5][5], (double)Vr.p[5],
-                   (double)Vr.S[5][0], (double)Vr.S[5][1], (double)Vr.S[5][2], (double)Vr.om[0], (double)Vr.om[1], (double)Vr.om[2],
-                   (double)Vr.W[0][0], (double)Vr.W[0][1], (double)Vr.W[0][2], (double)Vr.W[1][1], (double)Vr.W[1][2], (double)Vr.W[2][2]);
-#endif
-        return riccati_root(Vr, P, dd_out, nu_out);       // 1 good, -1 wrong inertia (no point in repeating the sweep), 0 breakdown
+        const int okr = riccati_root(Vr, P, dd_out, nu_out);       // 1 good, -1 wrong inertia (no point in repeating the sweep), 0 breakdown
+        MPC_DBG_ROOT("pit   ", okr, rd_lane(wpiv, 0))
+        return okr;
     }
 
     __device__ __forceinline__ void forward_pit(const PitLaneConsts& PC, T dd, const T nu[3], T delta) const {
-#ifdef MPC_PROFILE
-        const long long tf_in = __builtin_readcyclecounter();
-#endif
+        MPC_LAP_BEGIN(t_lap)
         const int n = L.n, N = n - 1, Lm = N >> 2;
         const int ll = local_lane();
         const int c = ll & 15, row = ll >> 4;
@@ -614,10 +592,7 @@
                 xi = xn;
             };
             T qa[8], qb[8];
-#ifdef MPC_PROFILE
-            const long long tf0 = __builtin_readcyclecounter();
-            prof_fwd_pre += tf0 - tf_in;
-#endif
+            MPC_LAP(fwd_pre, t_lap);
             if constexpr (GS) {
                 // coefficients from global memory: three stages ahead (see forward_states); every row runs Lm + (N mod 4) stages, the rows below 3 turn to the dummy
                 // word after their own Lm (row 3's pointers simply go on into the leftover stages)
@@ -651,16 +626,10 @@
 #pragma unroll
                                            for (int j = 0; j < 8; ++j) qa[j] = qb[j]; }
             }
-#ifdef MPC_PROFILE
-            prof_fwd_loop += __builtin_readcyclecounter() - tf0;
-#endif
+            MPC_LAP(fwd_loop, t_lap);
         }
-#ifdef MPC_PROFILE
-        const long long tf1 = __builtin_readcyclecounter();
-#endif
+        MPC_LAP_BEGIN(t_post)
         multipliers(dd, nu, delta);
-#ifdef MPC_PROFILE
-        prof_fwd_post += __builtin_readcyclecounter() - tf1;
-#endif
+        MPC_LAP(fwd_post, t_post);
     }
 

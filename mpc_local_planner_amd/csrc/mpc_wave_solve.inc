@@ -77,12 +77,12 @@
         T fstate = T(-1);
         int nfilt = 0, fpos = 0;
         static_assert(Algo<T>::flt_cap == 16, "the filter's pairs sit in DPP rows 0 and 1");
-        MPC_PROFILE_BEGIN
+        MPC_PROF_BEGIN
         while (true) {
             Err er;
-            MPC_GAP_END(13);
+            MPC_GAP_END(GLUE_BACK_EDGE);
             MPC_MARK("KKT_BEGIN");
-            MPC_TICK(0, er = kkt_pass());
+            MPC_TICK(KKT, er = kkt_pass());
             U(er.rd, er.rp, er.cmin, er.cmax); U(er.csum, er.sum_mult, er.sum_bmult, er.theta); U(inv_cnt_mult, inv_cnt_bmult);
             MPC_MARK("KKT_END");
             if constexpr (OBST) {
@@ -137,9 +137,9 @@
                 if (mu_new != mu) { mu = mu_new; rho = T(0); }
             }
             U(mu, rho);
-            MPC_GAP_END(9);
+            MPC_GAP_END(GLUE_KKT_TO_BARRIER);
             MPC_MARK("BARRIER_BEGIN");
-            MPC_TICK(1, stage_barrier_terms(); sync());
+            MPC_TICK(BARRIER_TERMS, stage_barrier_terms(); sync());
             MPC_MARK("BARRIER_END");
             T tau = t_max(Algo<T>::tau_min, T(1) - mu);
             if (mu != dc_mu) { dc_mu = mu; dc_val = nfix > 0 ? Algo<T>::delta_c * pow_(mu, Algo<T>::kappa_c) : T(0); }   // pow() only when mu moved
@@ -155,24 +155,24 @@
             for (int ntry = 0; ntry <= 40; ++ntry) {
                 bool good, used_pit = false;
                 MPC_DBG_PIT_CHECK
-                MPC_GAP_END(10);
+                MPC_GAP_END(GLUE_BARRIER_TO_FAC);
                 if (pit && mu > pit_floor()) {        // partitioned sweep; a broken-down combine pivot (or a singular stage pivot) falls back to the serial sweep; below pit_floor() the end game takes the serial sweeps
                     int gp_;
-                    MPC_TICK(2, gp_ = backward_pit(plc, delta, dc, dd, nu); sync());
+                    MPC_TICK(BACKWARD, gp_ = backward_pit(plc, delta, dc, dd, nu); sync());
                     good = used_pit = gp_ > 0;
-                    if (gp_ == 0) { MPC_GAP_END(10); MPC_TICK(2, good = backward_dpp(delta, dc, dd, nu); sync()); }
-                } else { MPC_TICK(2, good = backward_dpp(delta, dc, dd, nu); sync()); }
-                MPC_PROFILE_COUNT(nfac);
+                    if (gp_ == 0) { MPC_GAP_END(GLUE_BARRIER_TO_FAC); MPC_TICK(BACKWARD, good = backward_dpp(delta, dc, dd, nu); sync()); }
+                } else { MPC_TICK(BACKWARD, good = backward_dpp(delta, dc, dd, nu); sync()); }
+                MPC_PROF_COUNT(nfac);
                 MPC_DBG_NANCHECK_FIELDS
                 U(dd, nu[0], nu[1], nu[2]);
                 if (good) {
-                    MPC_GAP_END(10);
-                    if (used_pit) { MPC_TICK(3, forward_pit(plc, dd, nu, delta); sync()); }
-                    else { MPC_TICK(3, forward_states(dd, nu, delta); sync()); }
+                    MPC_GAP_END(GLUE_BARRIER_TO_FAC);
+                    if (used_pit) { MPC_TICK(FORWARD, forward_pit(plc, dd, nu, delta); sync()); }
+                    else { MPC_TICK(FORWARD, forward_states(dd, nu, delta); sync()); }
                     MPC_DBG_NANCHECK_STEP
-                    MPC_GAP_END(10);
+                    MPC_GAP_END(GLUE_BARRIER_TO_FAC);
                     MPC_MARK("POST_BEGIN");
-                    MPC_TICK(4, fw = post_pass<kFusedPasses>(dd, nu, tau, tregs));
+                    MPC_TICK(POST, fw = post_pass<kFusedPasses>(dd, nu, tau, tregs));
                     U(fw.hdz, fw.clam, fw.dz2, fw.dphi); U(fw.a_p, fw.a_d, fw.dzmax, fw.nunu);
                     MPC_MARK("POST_END");
                     good = fw.finite;
@@ -205,7 +205,7 @@
             }
             T phi0;
             // sum of the barrier logs at the current point: it is the value of the last accepted trial (same point, mu-independent)
-            if (!have_logs) { MPC_GAP_END(11); MPC_TICK(5, logs_cur = barrier_logs(SCL(SC_D), T(0), false, dd)); have_logs = true; U(logs_cur); }
+            if (!have_logs) { MPC_GAP_END(GLUE_LS_SETUP); MPC_TICK(LOGS0, logs_cur = barrier_logs(SCL(SC_D), T(0), false, dd)); have_logs = true; U(logs_cur); }
             const T rho_ls = filter ? T(0) : rho;       // the filter compares the barrier function itself
             phi0 = fobj - mu * logs_cur + rho_ls * theta;
             T Dm = fw.dphi - rho_ls * theta;
@@ -233,9 +233,9 @@
             }
             bool accepted = false, sw_arm = false;
             const bool fast_trials = trial_fast_ok();
-            MPC_GAP_END(11);
+            MPC_GAP_END(GLUE_LS_SETUP);
             MPC_MARK("TSETUP_BEGIN");
-            if (fast_trials && !kFusedPasses) { MPC_TICK(8, trial_setup(tregs, dd)); }      // (kFusedPasses: post_pass has filled them)
+            if (fast_trials && !kFusedPasses) { MPC_TICK(TRIAL_SETUP, trial_setup(tregs, dd)); }      // (kFusedPasses: post_pass has filled them)
             MPC_MARK("TSETUP_END");
             T th_t = T(0), f_t = T(0), lg_t = T(0);
             for (int ls = 0; ls < Algo<T>::max_ls; ++ls) {
@@ -243,20 +243,20 @@
                 const bool below = filter && ls > 0 && alpha < a_min;      // below the shortest step worth trying: this trial point is the one taken with an emptied filter
                 T phit, tht;
                 T d_t = SCL(SC_D) + (dtf() ? alpha * SCL(SC_DD) : T(0)); U(d_t);
-                MPC_GAP_END(11);
+                MPC_GAP_END(GLUE_LS_SETUP);
                 MPC_MARK("TRIAL_BEGIN");
                 if (fast_trials) {
-                    MPC_TICK(6, trial_eval(tregs, alpha, d_t, th_t, f_t, lg_t);
+                    MPC_TICK(TRIAL, trial_eval(tregs, alpha, d_t, th_t, f_t, lg_t);
                              tht = th_t + (T(1) - alpha) * theta_rows;
                              phit = f_t - mu * lg_t + rho_ls * tht; sync());
                 } else {
-                    MPC_TICK(6, eval_point(d_t, th_t, f_t, alpha, true);
+                    MPC_TICK(TRIAL, eval_point(d_t, th_t, f_t, alpha, true);
                              tht = th_t + (T(1) - alpha) * theta_rows;
                              lg_t = barrier_logs(d_t, alpha, true, dd);
                              phit = f_t - mu * lg_t + rho_ls * tht; sync());
                 }
                 MPC_MARK("TRIAL_END");
-                MPC_PROFILE_COUNT(ntrial);
+                MPC_PROF_COUNT(ntrial);
                 U(th_t, f_t, lg_t, phit);
                 if (!filter) {
                     if (t_finite(phit) && phit - phi0 - Algo<T>::ls_eps * t_abs(phi0) <= Algo<T>::eta_armijo * alpha * Dm) { accepted = true; break; }
@@ -296,16 +296,16 @@
             if (acc_tol > T(0) && (!accepted || alpha < T(1e-6) * fw.a_p) && e0 <= acc_tol) { status = ST_CONVERGED; break; }
             if (!accepted && alpha * fw.dzmax < T(1e-14)) { status = ST_LINESEARCH; break; }
             MPC_DBG_NANCHECK_LS
-            MPC_GAP_END(12);
+            MPC_GAP_END(GLUE_TRIAL_TO_ACCEPT);
             MPC_MARK("ACCEPT_BEGIN");
-            MPC_TICK(7, accept(alpha, fw.a_d); sync());
+            MPC_TICK(ACCEPT, accept(alpha, fw.a_d); sync());
             MPC_MARK("ACCEPT_END");
             theta_c = th_t; fobj = f_t; logs_cur = lg_t;
             last_alpha = alpha; last_ad = fw.a_d;
             U(theta_c, fobj, logs_cur); U(last_alpha, last_ad);
             ++it;
         }
-        MPC_PROFILE_END
+        MPC_PROF_END
         out.status = status; out.iters = it; out.kkt_error = e0; out.objective = fobj;
         return out;
     }

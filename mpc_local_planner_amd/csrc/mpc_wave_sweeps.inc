@@ -78,22 +78,9 @@
     //      the instruction count.  The DPP arithmetic lives in four inline-asm blocks per stage (mpc_dpp_blocks.inc, generated
     //      by scripts/gen_dpp_blocks.py): the compiler cannot see a DPP operand inside inline asm and therefore does not insert
     //      the 2 wait states of the VALU-write -> DPP-read hazard; each block opens with s_nop 1 and orders its own instructions.
-#ifdef MPC_DPP_DEBUG     // developer aid: single-instruction DPP helpers to bisect the generated blocks (each pays its own s_nop)
-#define MPC_BC_CASE(N) else if constexpr (LANE == N) { \
-        if constexpr (sizeof(T) == 8) asm("s_nop 1\n\tv_fmac_f64_dpp %0, %1, %2 row_newbcast:" #N " row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(src), "v"(own)); \
-        else asm("s_nop 1\n\tv_fmac_f32_dpp %0, %1, %2 row_newbcast:" #N " row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(src), "v"(own)); }
-    template <int LANE> __device__ __forceinline__ static void fmac_bc(T& acc, T src, T own) {
-        if constexpr (LANE < 0) {}
-        MPC_BC_CASE(0) MPC_BC_CASE(1) MPC_BC_CASE(2) MPC_BC_CASE(3) MPC_BC_CASE(4) MPC_BC_CASE(5)
-        MPC_BC_CASE(6) MPC_BC_CASE(7) MPC_BC_CASE(8) MPC_BC_CASE(9) MPC_BC_CASE(10) MPC_BC_CASE(11)
-    }
-#undef MPC_BC_CASE
-#endif
     __device__ __forceinline__ bool backward_dpp(T delta, T dc, T& dd_out, T nu_out[3]) const {
         MPC_PHASE_LANE
-#ifdef MPC_PROFILE
-        const long long ts0 = __builtin_readcyclecounter();
-#endif
+        MPC_LAP_BEGIN(t_lap)
         MPC_MARK("BWD_SETUP_BEGIN");
         const int n = L.n;
         const T d = SCL(SC_D);
@@ -170,30 +157,14 @@
             // ---- T1 = V+ Ghat (own column, then the five broadcast columns) and
             //      omega[b] += S+[0][b] c0 + S+[1][b] c1 + S+[2][b] c2  (lanes 9..11; c_k is lane 8's coefficient triple)
             T t[6];
-#if defined(MPC_DPP_DEBUG) && (MPC_DPP_DEBUG & 1)
-            for (int i = 0; i < 6; ++i) t[i] = V[i] * ec;
-            for (int i = 0; i < 6; ++i) fmac_bc<0>(t[i], V[i], G[0]);
-            for (int i = 0; i < 6; ++i) fmac_bc<1>(t[i], V[i], G[1]);
-            for (int i = 0; i < 6; ++i) fmac_bc<2>(t[i], V[i], G[2]);
-            for (int i = 0; i < 6; ++i) fmac_bc<3>(t[i], V[i], E3);
-            for (int i = 0; i < 6; ++i) fmac_bc<4>(t[i], V[i], E4);
-            fmac_bc<8>(om, G[0], V[0]); fmac_bc<8>(om, G[1], V[1]); fmac_bc<8>(om, G[2], V[2]);
-#else
             MPC_DPP_BLOCK_T1
-#endif
             // ---- Hhat = Ghat' T1 + cost entries (+ regularisation on this lane's diagonal entry)
             T h[8];
             h[0] = (A[0] + dk0) + t[0]; h[1] = (A[1] + dk1) + t[1]; h[2] = (A[2] + dk2) + t[2];
             h[3] = A[3]; h[4] = A[4];
             h[5] = (A[5] + s5) + t[5];
             h[6] = (A[6] + dA6) + t[3]; h[7] = (A[7] + dA7) + t[4];
-#if defined(MPC_DPP_DEBUG) && (MPC_DPP_DEBUG & 2)
-            fmac_bc<6>(h[6], G[0], t[0]); fmac_bc<7>(h[7], G[0], t[0]); fmac_bc<5>(h[5], G[0], t[0]); fmac_bc<2>(h[2], G[0], t[0]);
-            fmac_bc<6>(h[6], G[1], t[1]); fmac_bc<7>(h[7], G[1], t[1]); fmac_bc<5>(h[5], G[1], t[1]); fmac_bc<2>(h[2], G[1], t[1]);
-            fmac_bc<6>(h[6], G[2], t[2]); fmac_bc<7>(h[7], G[2], t[2]); fmac_bc<5>(h[5], G[2], t[2]);
-#else
             MPC_DPP_BLOCK_H
-#endif
             // ---- Schur complement on the control block
             T R00, R01, R11;
             MPC_DPP_BLOCK_R
@@ -209,22 +180,10 @@
             // W[a][b] -= Su[:,a]' Knu[:,b] in lane 9+b, omega[a] -= Su[:,a]' kappa in lane 8 (Su[j][a] = Hhat[6+j][9+a]);
             // V = Hhat_xx + Hhat_xu nK   (row i of Hhat[:,6:8] = lane i's Hhat[6:8][.])
             V[0] = h[0]; V[1] = h[1]; V[2] = h[2]; V[3] = h[3]; V[4] = h[4]; V[5] = h[5];
-#if defined(MPC_DPP_DEBUG) && (MPC_DPP_DEBUG & 4)
-            fmac_bc<9>(wn[0], h[6], nK0); fmac_bc<10>(wn[1], h[6], nK0); fmac_bc<11>(wn[2], h[6], nK0);
-            fmac_bc<9>(wn[0], h[7], nK1); fmac_bc<10>(wn[1], h[7], nK1); fmac_bc<11>(wn[2], h[7], nK1);
-            fmac_bc<0>(V[0], h[6], nK0); fmac_bc<1>(V[1], h[6], nK0); fmac_bc<2>(V[2], h[6], nK0);
-            fmac_bc<3>(V[3], h[6], nK0); fmac_bc<4>(V[4], h[6], nK0); fmac_bc<5>(V[5], h[6], nK0);
-            fmac_bc<0>(V[0], h[7], nK1); fmac_bc<1>(V[1], h[7], nK1); fmac_bc<2>(V[2], h[7], nK1);
-            fmac_bc<3>(V[3], h[7], nK1); fmac_bc<4>(V[4], h[7], nK1); fmac_bc<5>(V[5], h[7], nK1);
-#else
             MPC_DPP_BLOCK_V
-#endif
         };
         T Ga[3], Aa[8], Gb[3], Ab[8];
-#ifdef MPC_PROFILE
-        const long long tl0 = __builtin_readcyclecounter();
-        prof_setup += tl0 - ts0;
-#endif
+        MPC_LAP(bwd_setup, t_lap);
         load_stage(Ga, Aa);
         int k = n - 2;
         if constexpr (GS && !(OBST && MODEL == MODEL_KINEMATIC_BICYCLE)) {      // (that one kernel has no registers left for the third set)
@@ -250,9 +209,7 @@
         if (k == 1) { stage(dA0, dA1, dA2, T(0), Ga, Aa, Gb, Ab); stage(T(0), T(0), T(0), s05, Gb, Ab, Ga, Aa); }
         else stage(T(0), T(0), T(0), s05, Ga, Aa, Gb, Ab);
         }
-#ifdef MPC_PROFILE
-        prof_loop += __builtin_readcyclecounter() - tl0;
-#endif
+        MPC_LAP(bwd_loop, t_lap);
         // row 5 of the value block, omega and the W / omega corrections are gathered with v_readlane (no LDS round trip)
         if (!(rd_lane(worst, 0) > T(0))) return false;
         RicState<T> Vr;
@@ -273,23 +230,9 @@
             Vr.W[0][2] = Vr.W[2][0] = T(0.5) * (w02 + w20);
             Vr.W[1][2] = Vr.W[2][1] = T(0.5) * (w12 + w21);
         }
-#ifdef MPC_PIT_VERBOSE
-        if (blockIdx.x == MPC_PIT_CHECK && lane == 0)
-            printf("  %s root: P55 %.10e p5 %.10e S5 %.10e %.10e %.10e om %.10e %.10e %.10e W %.10e %.10e %.10e %.10e %.10e %.10e\n", "serial", (double)Vr.P[5][5], (double)Vr.p[5],
-                   (double)Vr.S[5][0], (double)Vr.S[5][1], (double)Vr.S[5][2], (double)Vr.om[0], (double)Vr.om[1], (double)Vr.om[2],
-                   (double)Vr.W[0][0], (double)Vr.W[0][1], (double)Vr.W[0][2], (double)Vr.W[1][1], (double)Vr.W[1][2], (double)Vr.W[2][2]);
-#endif
-#ifdef MPC_NANCHECK
-        {
-            const bool okr = riccati_root(Vr, P, dd_out, nu_out) > 0;
-            if (blockIdx.x == MPC_NANCHECK && lane == 0)
-                printf("  root: ok %d worst %g P55 %g p5 %g S5 %g %g %g om %g %g %g W %g %g %g %g %g %g\n", (int)okr, (double)rd_lane(worst, 0), (double)Vr.P[5][5], (double)Vr.p[5],
-                       (double)Vr.S[5][0], (double)Vr.S[5][1], (double)Vr.S[5][2], (double)Vr.om[0], (double)Vr.om[1], (double)Vr.om[2],
-                       (double)Vr.W[0][0], (double)Vr.W[0][1], (double)Vr.W[0][2], (double)Vr.W[1][1], (double)Vr.W[1][2], (double)Vr.W[2][2]);
-            return okr;
-        }
-#endif
-        return riccati_root(Vr, P, dd_out, nu_out) > 0;
+        const bool okr = riccati_root(Vr, P, dd_out, nu_out) > 0;
+        MPC_DBG_ROOT("serial", okr, rd_lane(worst, 0))
+        return okr;
     }
 
     // inclusive suffix sum over the wave (lane i gets sum_{j >= i} v_j): Hillis-Steele inside each 16-lane row with DPP row
@@ -393,20 +336,11 @@
             auto stage = [&](T (&q)[8], T (&qn)[8]) {
                 load_q(qn);
                 T s = q[0], s2 = T(0), xn;
-#if defined(MPC_DPP_DEBUG) && (MPC_DPP_DEBUG & 8)
-                fmac_bc<0>(s, xi, q[1]); fmac_bc<1>(s2, xi, q[2]); fmac_bc<2>(s, xi, q[3]); fmac_bc<3>(s2, xi, q[4]); fmac_bc<4>(s, xi, q[5]);
-                s += s2;
-                xn = s;
-                fmac_bc<3>(xn, s, q[6]); fmac_bc<4>(xn, s, q[7]);
-#else
                 MPC_DPP_BLOCK_FWD
-#endif
                 *op = xn; op += os;
                 xi = xn;
             };
-#ifdef MPC_PROFILE
-            const long long tf0 = __builtin_readcyclecounter();
-#endif
+            MPC_LAP_BEGIN(t_lap)
             if constexpr (GS) {
                 // coefficients from global memory: three stages ahead instead of one (a stage is ~250 cycles of work, an L2 hit under load several times that: measured
                 // 690 cycles per stage with the one-stage prefetch of the LDS form, profiles/r05_phase_profile_gs.log); four register sets in rotation
@@ -435,9 +369,7 @@
             }
             if (k < n - 1) stage(qa, qb);
             }
-#ifdef MPC_PROFILE
-            prof_fwd_loop += __builtin_readcyclecounter() - tf0;
-#endif
+            MPC_LAP(fwd_loop, t_lap);
         }
         multipliers(dd, nu, delta);
     }
@@ -447,9 +379,7 @@
     __device__ __forceinline__ void multipliers(T dd, const T nu[3], T delta) const {
         MPC_PHASE_LANE
         const int n = L.n;
-#if defined(MPC_PROFILE) && defined(MPC_PROFILE_MULT)      // developer counter: the ticks of this function take the place of `logs0` in mpc_debug_profile
-        struct Tick { long long& acc; long long t0; __device__ Tick(long long& a) : acc(a), t0(__builtin_readcyclecounter()) {} __device__ ~Tick() { acc += __builtin_readcyclecounter() - t0; } } tick_(prof_mult);
-#endif
+        MPC_PROF_SCOPE_MULT
         sync();
         const T xi[3] = {F(L.DX, 0, n - 1), F(L.DX, 1, n - 1), F(L.DX, 2, n - 1)};
         // ---- multipliers: lam+_{k-1} = lam+_k + t_k + e_theta (a0_k lam+_k[0] + a1_k lam+_k[1]),  k = n-2 .. 1,

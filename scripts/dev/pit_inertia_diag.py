@@ -1,5 +1,5 @@
-"""developer tool: run one batch on a -DMPC_PIT_CHECK=64 build (MPC_HIP_LIB): the kernel prints every factorisation on which the partitioned and the serial sweep differ
-(verdict on the inertia, or the step beyond 1e-7 relative)"""
+"""developer tool: run one batch on the `pit_check` variant of the library (python scripts/dev/variants.py pit_check python scripts/dev/pit_inertia_diag.py): the kernel
+prints every factorisation on which the partitioned and the serial sweep differ (verdict on the inertia, or the step beyond 1e-7 relative)"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np

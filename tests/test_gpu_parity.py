@@ -428,9 +428,9 @@ def test_no_uninitialised_lds_reads(m, tmp_path):
     for a 0 * garbage = NaN bug that only showed up when a previous kernel had left NaN patterns in LDS)."""
     import subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    from mpc_local_planner_amd import _lib
-    so = os.path.join(_lib.CSRC, "libmpc_hip_poison.so")          # next to the product library: compiled when a source, a header or a flag changed, not on every run
-    _lib.build(extra_flags=["-DMPC_POISON_LDS"], out=so)          # the split build of the product library with one more flag (parallel: ~25 s)
+    sys.path.insert(0, os.path.join(root, "scripts", "dev"))
+    import variants
+    so = variants.build("poison")          # csrc/libmpc_hip_poison.so, next to the product library: the product's split build with one more flag, compiled when a source, a header or a flag changed, not on every run
     # round-2 paths: candidates (kernel-generated seeds), kept multipliers, a turning footprint against polygons and a dynamic obstacle -- results of
     # the normal library (this process) must be reproduced bit for bit by the poisoned build (the subprocess)
     x0, xf, up, dtp = m.workloads.carlike_min_time_inputs(16, seed=77, goal_range=(2.0, 4.0))

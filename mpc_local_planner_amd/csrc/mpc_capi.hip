@@ -835,6 +835,23 @@ int mpc_occupancy(mpc_solver* s, int32_t B, int32_t* workgroups_per_cu, int64_t*
     return MPC_OK;
 }
 
+// developer observation (not part of include/mpc_hip.h, like mpc_debug_profile): what the launch plan decided for a launch of B instances of this handle -- the handle's
+// shape word (mpc_core.hpp::shape_flags) and the shape word compiled into the kernel such a launch runs (0: a kernel that reads the word at run time).  Asks plan_launch, as
+// the launch and mpc_occupancy do; tests/test_gpu_shape_kernel.py asserts on it.
+int mpc_debug_kernel_shape(mpc_solver* s, int32_t B, int32_t* handle_flags, int32_t* kernel_shape) {
+    if (!s || !handle_flags || !kernel_shape || B <= 0) return MPC_EINVAL;
+    *handle_flags = s->plan.flags;
+    *kernel_shape = mpc::plan_launch(s->plan, s->cfg.precision == MPC_FP32, B).shape;
+    return MPC_OK;
+}
+// ... and the developer switch that goes with it: on = 0 keeps this handle on the kernels that read the shape word at run time (the same problem through the run-time-flags
+// fixed-layout kernel: what the test compares the shape-known kernel with), on != 0 gives it back what make_launch_plan decided
+int mpc_debug_use_shape_kernel(mpc_solver* s, int32_t on) {
+    if (!s) return MPC_EINVAL;
+    s->plan.shape_ok = on != 0 && mpc::make_launch_plan(s->cfg).shape_ok;
+    return MPC_OK;
+}
+
 int mpc_last_kernel_ms(mpc_solver* s, float* ms) {
     if (!s || !ms) return MPC_EINVAL;
     if (!s->timed) { *ms = 0.f; return MPC_OK; }

@@ -100,6 +100,31 @@ struct Problem {
     long long max_ticks; // mpc_config.max_time_us in ticks of the device's constant 100 MHz clock (wall_clock64); 0 = no limit
 };
 
+// The problem's shape in one word: the switches the wave kernel tests on every use (IpmWave::flags, mpc_wave.hpp).  Bits 0..2 xf_fixed, 3 dt_free, 4 quadratic objective,
+// 5 has_Qf, 6..9 rate_on, 10 terminal ball, 11 via-points, 12 footprint that turns with the pose, 13 integral form with dt free, 14 dynamic obstacles, 15 convexified
+// Hessian, 16 minimum-time term in the objective, 17 cost variants.  Computed by the kernel (solve()) and by the host (mpc_launch_plan.hpp) from this one expression; every
+// field it reads is an int32 that parameter sets must share with their handle (parameter_set_error), so the word is the handle's.
+// (a macro because the kernel keeps the expression in place in solve(): behind a function call the same expression compiles to other instructions in every wave kernel)
+#define MPC_SHAPE_FLAGS(P) \
+    ((P.xf_fixed[0] ? 1 : 0) | (P.xf_fixed[1] ? 2 : 0) | (P.xf_fixed[2] ? 4 : 0) | (P.dt_free ? 8 : 0) | (P.objective == OBJ_QUADRATIC ? 16 : 0) | \
+                (P.has_Qf ? 32 : 0) | (P.rate_on[0] ? 64 : 0) | (P.rate_on[1] ? 128 : 0) | (P.rate_on[2] ? 256 : 0) | (P.rate_on[3] ? 512 : 0) | (P.ball ? 1024 : 0) | (P.via ? 2048 : 0) | ((P.n_obst > 0 && (P.footprint_kind == 2 || P.footprint_kind == 3 || P.footprint_kind == 4)) ? 4096 : 0) | (P.integral_form ? 8192 : 0) | (P.dyn_obst ? 16384 : 0) | (P.hess_mode ? 32768 : 0) | ((P.objective != OBJ_QUADRATIC || P.hybrid) ? 65536 : 0) | (P.costx ? 131072 : 0))
+template <typename T>
+constexpr int shape_flags(const Problem<T>& P) { return MPC_SHAPE_FLAGS(P); }      // the host's form (mpc_launch_plan.hpp; headline_shape below)
+// The shape the fixed-layout kernel is also compiled for (IpmWave's SHAPE): the car-like minimum-time problem of BASELINE configs[1] / [3] -- goal fixed in all three
+// components, dt free, minimum time alone in the objective, no terminal cost, the four control-rate rows on.  Stated as the fields the word is made of, so that it cannot
+// drift from shape_flags(); mpc_launch_plan.hpp hands the kernel to a handle whose word EQUALS this one.
+constexpr int headline_shape() {
+    Problem<double> P{};
+    P.xf_fixed[0] = P.xf_fixed[1] = P.xf_fixed[2] = 1;
+    P.dt_free = 1;
+    P.objective = OBJ_MIN_TIME;
+    P.has_Qf = 0;
+    P.rate_on[0] = P.rate_on[1] = P.rate_on[2] = P.rate_on[3] = 1;
+    return shape_flags(P);
+}
+constexpr int kHeadlineShape = headline_shape();
+static_assert(kHeadlineShape == 0x103cf, "bits 0..3, 6..9 and 16");
+
 // Algorithm constants (Waechter & Biegler 2006 names).  Compile-time so that they live in
 // instruction immediates instead of scalar registers.
 #ifndef MPC_ELASTIC_TRIGGER
@@ -842,6 +867,105 @@ MPC_HD int riccati_root(const RicState<T>& V, const Problem<T>& P_, T& dd_out, T
     dd_out = sol[0];
     nu_out[0] = sol[1]; nu_out[1] = sol[2]; nu_out[2] = sol[3];
     return (t_finite(sol[0]) && t_finite(sol[1]) && t_finite(sol[2]) && t_finite(sol[3])) ? 1 : 0;
+}
+
+// riccati_root with the shape known at compile time (DTF: dt free; FXM: bits 0..2 = the fixed goal components): the system over the unknowns that exist alone, in
+// riccati_root's order -- dt first, then the fixed components' nu ascending; the inertia count over nu ascending, then dt.  An identity row of riccati_root is never the
+// row a column's exchange brings up before its own column (it holds one entry, on its diagonal), multiplies its neighbours by +-0 only and solves to 0: leaving it out
+// leaves every other operation with the same operands in the same order.  Same return codes, same dd / nu bit for bit (tests/test_shape_root_host.py) -- for a shape with
+// identity rows with one exception: what is left in dd / nu behind an answer of 0, where riccati_root drags a NaN through those rows (0 x NaN) and no caller reads the
+// values.  The headline shape has no identity rows and no exception.  The shape-known instantiation of the wave kernel calls it (mpc_wave.hpp, SHAPE).
+template <bool DTF, int FXM, typename T>
+MPC_HD int riccati_root_shape(const RicState<T>& V, T& dd_out, T nu_out[3]) {
+    constexpr int NF = (FXM & 1) + ((FXM >> 1) & 1) + ((FXM >> 2) & 1);      // fixed components = rows of nu = what the inertia asks for
+    constexpr int N = NF + (DTF ? 1 : 0);
+    if constexpr (N == 0) {
+        if (V.neg != 0) return -1;
+        dd_out = T(0); nu_out[0] = T(0); nu_out[1] = T(0); nu_out[2] = T(0);
+        return 1;
+    } else {
+        // unknown u of the solve order -> column of riccati_root's 4 x 4 system (0 dt, 1 + a: nu_a)
+        constexpr int f0 = (FXM & 1) ? 0 : ((FXM & 2) ? 1 : 2), f1 = (FXM & 1) ? ((FXM & 2) ? 1 : 2) : 2;
+        constexpr int idx[4] = {DTF ? 0 : 1 + f0, DTF ? 1 + f0 : 1 + f1, DTF ? 1 + f1 : 3, 3};
+        // entry (row r, column c) of riccati_root's tableau between unknowns that exist; c == 4: the right-hand side
+        auto ent = [&](int r, int c) -> T {
+            if (r == 0) return c == 0 ? V.P[5][5] : (c == 4 ? -V.p[5] : V.S[5][c - 1]);
+            return c == 0 ? V.S[5][r - 1] : (c == 4 ? -V.om[r - 1] : V.W[r - 1][c - 1]);
+        };
+        T A[N][N + 1];
+#pragma unroll
+        for (int a = 0; a < N; ++a) {
+#pragma unroll
+            for (int b = 0; b < N; ++b) A[a][b] = ent(idx[a], idx[b]);
+            A[a][N] = ent(idx[a], 4);
+        }
+        {   // ---- inertia: order nu ascending, then dt (riccati_root's rotation)
+            T B[N][N];
+            T scl = T(0);
+#pragma unroll
+            for (int a = 0; a < N; ++a)
+#pragma unroll
+                for (int b = 0; b < N; ++b) { B[a][b] = A[(a + (DTF ? 1 : 0)) % N][(b + (DTF ? 1 : 0)) % N]; scl = t_max(scl, t_abs(B[a][b])); }
+            int neg = V.neg;
+            bool okp = t_finite(scl);
+#pragma unroll
+            for (int c = 0; c < N; ++c) {
+                const T pv = B[c][c];
+                T rs = t_abs(pv);
+#pragma unroll
+                for (int b = c + 1; b < N; ++b) rs = t_max(rs, t_abs(B[c][b]));
+                okp = okp && (t_abs(pv) > T(1e-14) * rs) && (rs > T(0));
+                neg += pv < T(0) ? 1 : 0;
+                const T ip = t_rcp(pv);
+                okp = okp && t_finite(ip);
+#pragma unroll
+                for (int r = c + 1; r < N; ++r) {
+                    const T m = B[r][c] * ip;
+#pragma unroll
+                    for (int b = c + 1; b < N; ++b) B[r][b] -= m * B[c][b];
+                }
+            }
+            if (!okp) return 0;
+            if (neg != NF) return -1;
+        }
+        T ipiv[N];
+        bool ok = true;
+#pragma unroll
+        for (int c = 0; c < N; ++c) {
+#pragma unroll
+            for (int r = c + 1; r < N; ++r) {
+                const bool sw = t_abs(A[r][c]) > t_abs(A[c][c]);
+#pragma unroll
+                for (int b = 0; b < N + 1; ++b) { const T x = A[c][b], y = A[r][b]; A[c][b] = sw ? y : x; A[r][b] = sw ? x : y; }
+            }
+            const T best = t_abs(A[c][c]);
+            ok = ok && (best > T(0)) && t_finite(best);
+            const T ip = t_rcp(A[c][c]);
+            ipiv[c] = ip;
+#pragma unroll
+            for (int r = c + 1; r < N; ++r) {
+                const T m = A[r][c] * ip;
+#pragma unroll
+                for (int b = c; b < N + 1; ++b) A[r][b] -= m * A[c][b];
+            }
+        }
+        if (!ok) return 0;
+        T sol[N];
+#pragma unroll
+        for (int c = N - 1; c >= 0; --c) {
+            T a = A[c][N];
+#pragma unroll
+            for (int b = c + 1; b < N; ++b) a -= A[c][b] * sol[b];
+            sol[c] = a * ipiv[c];
+        }
+        T out4[4] = {T(0), T(0), T(0), T(0)};      // (an unknown that does not exist: riccati_root's identity row solves to 0)
+        bool fin = true;
+#pragma unroll
+        for (int c = 0; c < N; ++c) { fin = fin && t_finite(sol[c]); out4[idx[c]] = sol[c]; }
+        dd_out = out4[0];
+        nu_out[0] = out4[1]; nu_out[1] = out4[2]; nu_out[2] = out4[3];
+        return fin ? 1 : 0;
+    }
 }
 
 // Excess of negative eigenvalues of the pivot block of a combine step of the partitioned sweep (mpc_wave.hpp::backward_pit): n-(W) + n-(P+ - W^-1) - 5 for symmetric 5 x 5

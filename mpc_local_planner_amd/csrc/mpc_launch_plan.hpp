@@ -15,6 +15,7 @@
 namespace mpc {
 
 constexpr size_t kLdsPerCu = 160u * 1024u;      // LDS of a CU
+constexpr int kFixedLayoutNS = 50;              // the grid size whose record layout is compiled into a kernel of its own (FixedLayout; select_kernel)
 
 // dynamic LDS of one workgroup: the record of T-sized words, then (16-byte aligned, 16 bytes further) the problem record (mpc_solve_kernel.hpp)
 inline size_t lds_bytes(const WaveLayout& L, size_t tsize, size_t psize) { return ((((size_t)L.total * tsize) + 15) & ~(size_t)15) + 16 + ((psize + 15) & ~(size_t)15); }
@@ -25,6 +26,7 @@ struct KernelChoice {
     bool w2;            // the two-waves-per-SIMD kernel (fp64, level 0, no clearance rows, LDS form)
     WaveLayout L;       // the record; L.GSF = 1: the global form
     size_t lds;         // dynamic LDS of one workgroup
+    int shape;          // != 0: the fixed-layout kernel that has this shape word compiled in (mpc_core.hpp::kHeadlineShape); 0: the kernel reads the word at run time
 };
 
 struct LaunchPlan {
@@ -36,14 +38,16 @@ struct LaunchPlan {
     int w2_min_batch;
     size_t lds64, lds32, lds_w2;      // dynamic LDS of the fp64 / fp32 one-wave kernel and of the two-wave kernel (0 for a kernel the handle never launches)
     size_t block_bytes;         // one block of the per-XCD pools (global form, or the clearance rows' elastic arrays); 0: the handle has no pool
+    int flags;                  // the handle's shape word (mpc_core.hpp::shape_flags of its problem record: what solve() computes in the kernel)
+    bool shape_ok;              // the one-wave fp64 launches run the fixed-layout kernel compiled for kHeadlineShape
     size_t lds() const { return precision == MPC_FP32 ? lds32 : lds64; }      // the larger of the two phases under MPC_MIXED (mpc_lds_bytes)
 };
 
 // what a launch of B instances in fp32 (f32) or fp64 runs; B = 0 asks for the one-wave kernel (the one that claims the pool's blocks)
 inline KernelChoice plan_launch(const LaunchPlan& p, bool f32, int B) {
-    if (!f32 && p.w2_ok && B >= p.w2_min_batch) return {p.level, true, p.WL, p.lds_w2};
+    if (!f32 && p.w2_ok && B >= p.w2_min_batch) return {p.level, true, p.WL, p.lds_w2, 0};
     const bool gs = f32 ? p.gs32 : p.gs64;
-    return {p.level, false, gs ? p.WLg : p.WL, f32 ? p.lds32 : p.lds64};
+    return {p.level, false, gs ? p.WLg : p.WL, f32 ? p.lds32 : p.lds64, (!f32 && p.shape_ok) ? kHeadlineShape : 0};
 }
 
 inline LaunchPlan make_launch_plan(const mpc_config& c) {
@@ -98,6 +102,15 @@ inline LaunchPlan make_launch_plan(const mpc_config& c) {
     const size_t blk64 = c.precision != MPC_FP32 ? (size_t)(p.gs64 ? p.WLg.GSW : p.WL.GSW) * 8 : 0;
     const size_t blk32 = c.precision != MPC_FP64 ? (size_t)(p.gs32 ? p.WLg.GSW : p.WL.GSW) * 4 : 0;
     p.block_bytes = blk64 > blk32 ? blk64 : blk32;
+    // The shape-known kernel: the handle's word is the headline's, bit for bit, and every condition of the fixed layout holds (fp64, the headline level without clearance
+    // rows, the LDS form, the record of the model's FixedLayout).  Any other word on that layout keeps the run-time-flags fixed-layout kernel (select_kernel).  The word is
+    // taken from the fp64 record; the fp32 record of a mixed handle is filled from the same mpc_config and has the same int fields.  Kernel and plan evaluate ONE expression
+    // (MPC_SHAPE_FLAGS) over int fields that every parameter set shares with its handle, so the kernel's run-time word cannot differ from the one compared here; a shape
+    // that select_kernel has no instantiation for fails the launch (hipErrorInvalidConfiguration) instead of running another kernel.
+    p.flags = shape_flags(P);
+    const bool trig4 = c.model == MPC_MODEL_KINEMATIC_BICYCLE || c.model == MPC_MODEL_SIMPLE_CAR_FRONT;      // (IpmWave::NTRB)
+    const bool fixed = trig4 ? FixedLayout<kFixedLayoutNS, 4, NSTG_BASE>::matches(p.WL) : FixedLayout<kFixedLayoutNS, 3, NSTG_BASE>::matches(p.WL);
+    p.shape_ok = c.precision != MPC_FP32 && p.flags == kHeadlineShape && p.level == 0 && p.WL.M == 0 && !p.gs64 && fixed;
     return p;
 }
 

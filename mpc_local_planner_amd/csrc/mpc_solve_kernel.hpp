@@ -40,7 +40,8 @@ constexpr int kWinIdle = 0x7f7f7f7f;
 // Grid: n_cand * B workgroups, candidate-major, so that the hardware dispatches every instance's candidate 0 before any hedge.
 // W2: the variant for TWO waves per SIMD (throughput regime: more instances than SIMDs): at most 256 registers, every phase of an iteration on a lane index of its own
 // (IpmWave::local_lane: no per-lane address arithmetic survives from one phase into the next), line-search trials on the generic path.  Same arithmetic, same results bit for bit.
-template <typename T, int MODEL, int EXT, bool OBST, int NSC = 0, bool GS = false, bool W2 = false>
+// SHAPE != 0: the problem's shape word as a compile-time constant (IpmWave's SHAPE; the launch plan has held the handle's word to it).
+template <typename T, int MODEL, int EXT, bool OBST, int NSC = 0, bool GS = false, bool W2 = false, int SHAPE = 0>
 __global__ __launch_bounds__(mpc::kWave)
 __attribute__((amdgpu_waves_per_eu(W2 ? 2 : 1)))
 void mpc_ipm_wave_kernel(
@@ -92,7 +93,7 @@ void mpc_ipm_wave_kernel(
             *Ps = P; Ps->n = n;
         }
         __syncthreads();
-        mpc::IpmWave<T, MODEL, EXT, OBST, NSC, GS, W2> S(*Ps, Lv, sm, lane);
+        mpc::IpmWave<T, MODEL, EXT, OBST, NSC, GS, W2, SHAPE> S(*Ps, Lv, sm, lane);
         int gslot = -1;
         if (GS || (OBST && L.GSW > 0)) {
             // this workgroup's block of factorisation data (GlobalStage): one of the n_gslots blocks OF ITS XCD, claimed for the lifetime of the workgroup.  Per XCD because
@@ -241,10 +242,9 @@ struct SolveLaunch {
     int n_gslots;
 };
 
-constexpr int kFixedLayoutNS = 50;
-
 // the kernel instantiation that serves a kernel choice (nullptr for a combination that does not exist): four per (arithmetic type, model) in either form -- the
-// headline level without / with clearance rows and the two extended levels (always with) --, and in fp64 the fixed-layout kernel and the two-wave kernel
+// headline level without / with clearance rows and the two extended levels (always with) --, and in fp64 the fixed-layout kernel with run-time and with the headline shape
+// and the two-wave kernel
 template <typename T, int MODEL>
 auto select_kernel(const KernelChoice& k) -> decltype(&mpc_ipm_wave_kernel<T, MODEL, 0, true>) {
     const bool no_rows = k.level == 0 && k.L.M == 0;      // the headline level without clearance rows (OBST = false)
@@ -256,7 +256,12 @@ auto select_kernel(const KernelChoice& k) -> decltype(&mpc_ipm_wave_kernel<T, MO
     if constexpr (sizeof(T) == 8) {
         // fp64 headline kernel on a grid of kFixedLayoutNS points per record (the grid size of BASELINE configs[1] / [3]): the instantiation whose LDS layout is a
         // compile-time constant (mpc_layout.hpp::FixedLayout) -- same code, same results bit for bit, ~3 % fewer instructions; every other size runs the generic one
-        if (no_rows && !k.L.GSF && IpmWave<T, MODEL, 0, false, kFixedLayoutNS>::LayoutT::matches(k.L)) kern = mpc_ipm_wave_kernel<T, MODEL, 0, false, kFixedLayoutNS>;
+        if (no_rows && !k.L.GSF && IpmWave<T, MODEL, 0, false, kFixedLayoutNS>::LayoutT::matches(k.L)) {
+            kern = mpc_ipm_wave_kernel<T, MODEL, 0, false, kFixedLayoutNS>;
+            // ... and, for a handle of the headline shape (the plan's word, k.shape), the one that has the shape compiled in as well: same arithmetic, same results bit for bit
+            if (k.shape == kHeadlineShape) kern = mpc_ipm_wave_kernel<T, MODEL, 0, false, kFixedLayoutNS, false, false, kHeadlineShape>;
+            else if (k.shape != 0) kern = nullptr;      // (no such instantiation: plan_launch never asks)
+        } else if (k.shape != 0) kern = nullptr;
         if (k.w2) kern = no_rows && !k.L.GSF ? mpc_ipm_wave_kernel<T, MODEL, 0, false, 0, false, true> : nullptr;
     } else if (k.w2) {
         kern = nullptr;

@@ -49,7 +49,9 @@ namespace mpc {
 // words of the obstacle arrays leave the scalar registers (the headline kernel spilled ~430 of them)
 // NSC > 0: the layout is a compile-time constant for the stride NS = NSC (FixedLayout; needs EXT == 0, OBST == false, no Crank-Nicolson trig words)
 // GS: the factorisation data (STG, GAIN) in global memory instead of LDS (GlobalStage): same arithmetic, same results bit for bit, a third of the LDS record
-template <typename T, int MODEL, int EXT = 1, bool OBST = true, int NSC = 0, bool GS = false, bool W2 = false>
+// SHAPE != 0: the problem's shape word (mpc_core.hpp::shape_flags) is this compile-time constant: fx / dtf / quad / hasqf / mintime / ron fold, and the root system is solved in
+//      its shape-known form (riccati_root_shape).  Exists for the fixed layout and kHeadlineShape; the launch plan hands it only to handles whose word equals SHAPE
+template <typename T, int MODEL, int EXT = 1, bool OBST = true, int NSC = 0, bool GS = false, bool W2 = false, int SHAPE = 0>
 struct IpmWave {
     static constexpr int NSTG = EXT ? NSTG_EXT : NSTG_BASE;        // words per stage record
     // trig-cache words per stage: sin, cos, steering term(s); Crank-Nicolson appends sin/cos of its second evaluation angle
@@ -57,6 +59,7 @@ struct IpmWave {
     static_assert(NSC == 0 || (EXT == 0 && !OBST), "the fixed layout exists for the headline instantiation only");
     static_assert(!GS || NSC == 0, "the fixed layout keeps its factorisation data in LDS");
     static_assert(!W2 || (!GS && EXT == 0 && !OBST), "the two-wave kernel exists for the headline instantiation in the LDS form only");
+    static_assert(SHAPE == 0 || NSC != 0, "a compile-time shape exists for the fixed layout only");
     using LayoutT = typename LayoutOf<NSC, NTRB, NSTG>::type;
     const Problem<T>& P;     // lives in LDS (copied once per workgroup): wave-uniform constants are fetched with
     const LayoutT L;         // broadcast ds_reads instead of being pinned in (and spilled from) scalar registers; the layout
@@ -126,13 +129,17 @@ struct IpmWave {
     __device__ __forceinline__ unsigned short* oi_base() const { return reinterpret_cast<unsigned short*>(sm + L.OI); }
     __device__ __forceinline__ int oi(int m, int k) const { const unsigned v = oi_base()[m * L.NS + k]; return v == 0xffffu ? -1 : (int)v; }
     __device__ __forceinline__ void set_oi(int m, int k, int j) const { oi_base()[m * L.NS + k] = (unsigned short)(j < 0 ? 0xffff : j); }
-    __device__ __forceinline__ bool fx(int i) const { return (flags >> i) & 1; }
-    __device__ __forceinline__ bool dtf() const { return (flags >> 3) & 1; }
-    __device__ __forceinline__ bool quad() const { return (flags >> 4) & 1; }
-    __device__ __forceinline__ bool hasqf() const { return (flags >> 5) & 1; }
+    // (the shape's switches: bits of the compile-time word where there is one, else of the run-time word solve() computed)
+    __device__ __forceinline__ bool fx(int i) const { if constexpr (SHAPE != 0) return (SHAPE >> i) & 1; else return (flags >> i) & 1; }
+    __device__ __forceinline__ bool dtf() const { if constexpr (SHAPE != 0) return (SHAPE >> 3) & 1; else return (flags >> 3) & 1; }
+    // dtf() for the two places where its answer selects a PRODUCT that is then added (d + (dtf ? alpha dd : 0): solve()'s trial dt, accept()): the run-time word in every
+    // instantiation.  With the answer known the compiler contracts product and sum into one fma, and dt rounds differently from every other kernel (profiles/r18_shape_kernel.md)
+    __device__ __forceinline__ bool dtf_sum() const { return (flags >> 3) & 1; }
+    __device__ __forceinline__ bool quad() const { if constexpr (SHAPE != 0) return (SHAPE >> 4) & 1; else return (flags >> 4) & 1; }
+    __device__ __forceinline__ bool hasqf() const { if constexpr (SHAPE != 0) return (SHAPE >> 5) & 1; else return (flags >> 5) & 1; }
     // cost variants: minimum-time term in the objective (minimum-time objectives and the hybrid quadratic form); off-diagonal weights /
     // trapezoidal rule (EXT instantiation only: everything below `costx()` is delta code on top of the diagonal left-sum arithmetic)
-    __device__ __forceinline__ bool mintime() const { return (flags >> 16) & 1; }
+    __device__ __forceinline__ bool mintime() const { if constexpr (SHAPE != 0) return (SHAPE >> 16) & 1; else return (flags >> 16) & 1; }
     __device__ __forceinline__ bool costx() const { return EXT >= 2; }      // that instantiation is only launched for such problems (mpc_launch_plan.hpp, the level)
     // off-diagonal part of W x and of x' W x for the symmetric matrix with off-diagonal terms o = (01, 02, 12)
     __device__ __forceinline__ void offmul(const T o[3], const T x[3], T y[3]) const {
@@ -153,7 +160,7 @@ struct IpmWave {
         if (P.trapz) f += T(0.5) * d * fullquad(P.Q, P.Qo, xd);
         return f;
     }
-    __device__ __forceinline__ bool ron(int q) const { return (flags >> (6 + q)) & 1; }
+    __device__ __forceinline__ bool ron(int q) const { if constexpr (SHAPE != 0) return (SHAPE >> (6 + q)) & 1; else return (flags >> (6 + q)) & 1; }
     __device__ __forceinline__ bool ball() const { return EXT && ((flags >> 10) & 1); }
     __device__ __forceinline__ bool via() const { return EXT && ((flags >> 11) & 1); }
     __device__ __forceinline__ bool fpline() const { return EXT && ((flags >> 12) & 1); }

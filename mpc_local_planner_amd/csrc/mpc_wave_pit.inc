@@ -463,7 +463,9 @@
             Vr.W[0][2] = Vr.W[2][0] = T(0.5) * (w02 + w20);
             Vr.W[1][2] = Vr.W[2][1] = T(0.5) * (w12 + w21);
         }
-        const int okr = riccati_root(Vr, P, dd_out, nu_out);       // 1 good, -1 wrong inertia (no point in repeating the sweep), 0 breakdown
+        int okr;
+        if constexpr (SHAPE != 0) okr = riccati_root_shape<((SHAPE >> 3) & 1) != 0, SHAPE & 7>(Vr, dd_out, nu_out);
+        else okr = riccati_root(Vr, P, dd_out, nu_out);       // 1 good, -1 wrong inertia (no point in repeating the sweep), 0 breakdown
         MPC_DBG_ROOT("pit   ", okr, rd_lane(wpiv, 0))
         return okr;
     }

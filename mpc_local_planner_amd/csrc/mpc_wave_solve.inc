@@ -31,8 +31,7 @@
 
     __device__ __forceinline__ SolveStats<T> solve() {
         SolveStats<T> out;
-        flags = (P.xf_fixed[0] ? 1 : 0) | (P.xf_fixed[1] ? 2 : 0) | (P.xf_fixed[2] ? 4 : 0) | (P.dt_free ? 8 : 0) | (P.objective == OBJ_QUADRATIC ? 16 : 0) |
-                (P.has_Qf ? 32 : 0) | (P.rate_on[0] ? 64 : 0) | (P.rate_on[1] ? 128 : 0) | (P.rate_on[2] ? 256 : 0) | (P.rate_on[3] ? 512 : 0) | (P.ball ? 1024 : 0) | (P.via ? 2048 : 0) | ((P.n_obst > 0 && (P.footprint_kind == 2 || P.footprint_kind == 3 || P.footprint_kind == 4)) ? 4096 : 0) | (P.integral_form ? 8192 : 0) | (P.dyn_obst ? 16384 : 0) | (P.hess_mode ? 32768 : 0) | ((P.objective != OBJ_QUADRATIC || P.hybrid) ? 65536 : 0) | (P.costx ? 131072 : 0);
+        flags = MPC_SHAPE_FLAGS(P);      // (mpc_core.hpp; SHAPE != 0: the launch plan has held this word to SHAPE, and the accessors of the shape's bits read the constant)
         flags = __builtin_amdgcn_readfirstlane(flags);
         nfix = (int)fx(0) + (int)fx(1) + (int)fx(2);
         row0_on = dtprev != T(0);
@@ -242,7 +241,7 @@
                 if (ls > 0) { alpha *= T(0.5); U(alpha); }
                 const bool below = filter && ls > 0 && alpha < a_min;      // below the shortest step worth trying: this trial point is the one taken with an emptied filter
                 T phit, tht;
-                T d_t = SCL(SC_D) + (dtf() ? alpha * SCL(SC_DD) : T(0)); U(d_t);
+                T d_t = SCL(SC_D) + (dtf_sum() ? alpha * SCL(SC_DD) : T(0)); U(d_t);
                 MPC_GAP_END(GLUE_LS_SETUP);
                 MPC_MARK("TRIAL_BEGIN");
                 if (fast_trials) {

@@ -177,7 +177,7 @@
         MPC_PHASE_LANE
         const int n = L.n;
         const T kS = T(1e10);
-        const T d_old = SCL(SC_D), dd = SCL(SC_DD), d_new = d_old + (dtf() ? alpha * dd : T(0));
+        const T d_old = SCL(SC_D), dd = SCL(SC_DD), d_new = d_old + (dtf_sum() ? alpha * dd : T(0));
         // phase 1: everything that reads the OLD point
         T sn[4], yn[4];
         // Chunks of 64 grid points are visited from the END of the horizon: a rate row k reads the OLD u_{k-1}, which belongs to the

@@ -66,8 +66,14 @@
             }
             if (ball()) { T a[3]; th += t_abs(ball_eval(al, a) + ball_slack(alpha, trial)); }
         }
+        if constexpr (kBatchedReductions) {
+            T r2[2] = {th, fo};
+            wave_reduce_n<OpSum, OpSum>(r2);
+            theta_c = r2[0]; fobj = r2[1];
+        } else {
         theta_c = wave_sum(th);
         fobj = wave_sum(fo);
+        }
     }
 
     // sum of barrier logs at the current (alpha = 0) or trial point; wave-reduced
@@ -158,6 +164,9 @@
             if (r.on[q]) { const T s = F(L.SR, q, k); r.s[q] = s; r.ds[q] = -(row_val(L.U, d, k, q) + s) - row_jdz(k, q, dd); }
         }
     }
+    // kBatchedReductions: the kernels whose passes carry their wave reductions through the DPP steps together (wave_reduce_n) -- the fixed layout's, shape known or not;
+    // every other kernel keeps one chain per value, and with it its registers and its text
+    static constexpr bool kBatchedReductions = NSC != 0;
     // returns wave-reduced sum|c| (th), objective (fo) and the sum of the barrier logs at z + alpha dz, dt = d
     __device__ __forceinline__ void trial_eval(const TrialRegs& r, T alpha, T d, T& th_out, T& fo_out, T& logs_out) const {
         MPC_PHASE_LANE
@@ -198,7 +207,13 @@
             if (r.dtf) { acc.mul(d - r.dt_lb); acc.mul(r.dt_ub - d); }
             if (ball()) { T a[3]; const T st = ball_slack(alpha, true); th += t_abs(ball_eval(alpha, a) + st); acc.mul(st); }
         }
+        if constexpr (kBatchedReductions) {
+            T r3[3] = {th, fo, acc.value()};
+            wave_reduce_n<OpSum, OpSum, OpSum>(r3);
+            th_out = r3[0]; fo_out = r3[1]; logs_out = r3[2];
+        } else {
         th_out = wave_sum(th); fo_out = wave_sum(fo); logs_out = wave_sum(acc.value());
+        }
     }
 
     // ---------------------------------------------------------------- KKT error + stage records
@@ -389,6 +404,14 @@
             }
         }
         Err e;
+        if constexpr (kBatchedReductions) {      // the nine reductions in two batches (the registers of a batch's moves stay few), two compare-and-select chains in each:
+            T ra[5] = {rdd, rd, rp, cs, sb}, rb[4] = {cmin, cmax, smult, th};      // the sums of a batch stand between a compare and the select that reads its mask
+            wave_reduce_n<OpSum, OpMax, OpMax, OpSum, OpSum>(ra);
+            wave_reduce_n<OpMin, OpMax, OpSum, OpSum>(rb);
+            rdd = ra[0]; e.rd = ra[1]; e.rp = ra[2]; e.csum = ra[3]; e.sum_bmult = ra[4];
+            if (dtf()) e.rd = t_max(e.rd, t_abs(rdd));
+            e.cmin = rb[0]; e.cmax = rb[1]; e.sum_mult = rb[2] + e.sum_bmult; e.theta = rb[3];
+        } else {
         rdd = wave_sum(rdd);
         e.rd = wave_max(rd);
         if (dtf()) e.rd = t_max(e.rd, t_abs(rdd));
@@ -399,6 +422,7 @@
         e.sum_bmult = wave_sum(sb);
         e.sum_mult = wave_sum(smult) + e.sum_bmult;
         e.theta = wave_sum(th);
+        }
         if (nM() == 0 && cnt_bmult >= 0) { e.n_bmult = cnt_bmult; e.n_mult = cnt_mult; }      // without clearance rows the counts never change
         else {
             e.n_bmult = (int)wave_sum((T)nb);

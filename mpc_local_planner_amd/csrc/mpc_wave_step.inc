@@ -164,8 +164,16 @@
             }
         }
         Fwd o;
+        if constexpr (kBatchedReductions) {
+            T ra[4] = {hdz, clam, r_p, r_d}, rb[3] = {dz2, dphi, dzmax};      // (sums and maxima mixed in each batch, as in kkt_pass)
+            wave_reduce_n<OpSum, OpSum, OpMax, OpMax>(ra);
+            wave_reduce_n<OpSum, OpSum, OpMax>(rb);
+            o.hdz = ra[0]; o.clam = ra[1]; o.dz2 = rb[0]; o.dphi = rb[1];
+            o.a_p = ftb_alpha(ra[2], tau); o.a_d = ftb_alpha(ra[3], tau); o.dzmax = rb[2];
+        } else {
         o.hdz = wave_sum(hdz); o.clam = wave_sum(clam); o.dz2 = wave_sum(dz2); o.dphi = wave_sum(dphi);
         o.a_p = ftb_alpha(wave_max(r_p), tau); o.a_d = ftb_alpha(wave_max(r_d), tau); o.dzmax = wave_max(dzmax);
+        }
         o.nunu = T(0);
         for (int i = 0; i < 3; ++i) if (fx(i)) o.nunu += nu[i] * nu[i];
         o.finite = t_finite(o.hdz) && t_finite(o.dz2) && t_finite(o.clam);

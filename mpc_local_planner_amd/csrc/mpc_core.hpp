@@ -214,27 +214,49 @@ MPC_HD double t_rcp_approx(double x) {
 #endif
 }
 MPC_HD float t_rcp_approx(float x) { return 1.0f / x; }
+// ---- fp64 literals of the wrap, trig and log kernels below, "here" (LL) or as plain constants.  gfx950's VOP3 takes no 64-bit literal: an fp64 constant is a scalar pair
+//      built from two 32-bit moves.  The compiler shares halves between constants (pi, -pi, 2 pi have one low word) and hoists them out of the interior-point loop; the
+//      fixed-layout kernels have no scalar pair to spare across that loop, so the halves are parked in lanes of a spill register and every use reloads one half, copies
+//      the other and writes the pair back (profiles/r20_literal_diet.md).  With LL a constant's halves come out of two `s_mov_b32` in asm statements at the use: nothing
+//      to hoist, share or spill; identical statements still merge inside a block.  Same bits either way -- MPC_LIT(c) IS c --, so results do not depend on LL.
+//      Only mpc_wave.hpp's IpmWave::kLocalLiterals kernels ask for it; on the host LL means nothing.
+template <unsigned long long BITS>
+MPC_HD double lit64_here() {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+    unsigned lo, hi;
+    asm("s_mov_b32 %0, %1" : "=s"(lo) : "i"((int)(unsigned)BITS));
+    asm("s_mov_b32 %0, %1" : "=s"(hi) : "i"((int)(unsigned)(BITS >> 32)));
+    const u32x2 w = {lo, hi};
+    return __builtin_bit_cast(double, w);
+#else
+    return __builtin_bit_cast(double, BITS);
+#endif
+}
+// (inside a function with a template parameter `bool LL`; without LL the expression is the literal itself, so such code compiles to what it was)
+#define MPC_LIT(c) (LL ? ::mpc::lit64_here<__builtin_bit_cast(unsigned long long, double(c))>() : (c))
 // ---- fp64 sine / cosine / tangent for the arguments this solver produces (angles wrapped to [-pi, pi), steering angles
 //      inside their box): Cody-Waite reduction by pi/2 (two FMAs, exact for the quadrant counts that occur) and the classic
 //      degree-13/14 minimax kernels on [-pi/4, pi/4] (Sun fdlibm coefficients).  ~40 instructions instead of the several hundred
 //      of the general libm routine, whose extended-precision reduction dominated the line-search trials; <= 1 ulp on the
 //      reduced range (tests/host_harness checks it against libm).  Arguments beyond 1e5 or non-finite take the libm path.
+template <bool LL = false>
 MPC_HD void sincos_reduced(double x, double* sp, double* cp) {
-    const double k = __builtin_rint(x * 6.36619772367581382433e-01);
-    double r = __builtin_fma(-k, 1.57079632673412561417e+00, x);
-    r = __builtin_fma(-k, 6.07710050650619224932e-11, r);
+    const double k = __builtin_rint(x * MPC_LIT(6.36619772367581382433e-01));
+    double r = __builtin_fma(-k, MPC_LIT(1.57079632673412561417e+00), x);
+    r = __builtin_fma(-k, MPC_LIT(6.07710050650619224932e-11), r);
     const double z = r * r;
-    double ps = __builtin_fma(z, 1.58969099521155010221e-10, -2.50507602534068634195e-08);
-    ps = __builtin_fma(z, ps, 2.75573137070700676789e-06);
-    ps = __builtin_fma(z, ps, -1.98412698298579493134e-04);
-    ps = __builtin_fma(z, ps, 8.33333333332248946124e-03);
-    ps = __builtin_fma(z, ps, -1.66666666666666324348e-01);
+    double ps = __builtin_fma(z, MPC_LIT(1.58969099521155010221e-10), MPC_LIT(-2.50507602534068634195e-08));
+    ps = __builtin_fma(z, ps, MPC_LIT(2.75573137070700676789e-06));
+    ps = __builtin_fma(z, ps, MPC_LIT(-1.98412698298579493134e-04));
+    ps = __builtin_fma(z, ps, MPC_LIT(8.33333333332248946124e-03));
+    ps = __builtin_fma(z, ps, MPC_LIT(-1.66666666666666324348e-01));
     const double s = __builtin_fma(z * r, ps, r);
-    double pc = __builtin_fma(z, -1.13596475577881948265e-11, 2.08757232129817482790e-09);
-    pc = __builtin_fma(z, pc, -2.75573143513906633035e-07);
-    pc = __builtin_fma(z, pc, 2.48015872894767294178e-05);
-    pc = __builtin_fma(z, pc, -1.38888888888741095749e-03);
-    pc = __builtin_fma(z, pc, 4.16666666666666019037e-02);
+    double pc = __builtin_fma(z, MPC_LIT(-1.13596475577881948265e-11), MPC_LIT(2.08757232129817482790e-09));
+    pc = __builtin_fma(z, pc, MPC_LIT(-2.75573143513906633035e-07));
+    pc = __builtin_fma(z, pc, MPC_LIT(2.48015872894767294178e-05));
+    pc = __builtin_fma(z, pc, MPC_LIT(-1.38888888888741095749e-03));
+    pc = __builtin_fma(z, pc, MPC_LIT(4.16666666666666019037e-02));
     const double hz = 0.5 * z, wv = 1.0 - hz;
     const double c = wv + (((1.0 - wv) - hz) + z * z * pc);
     const int q = (int)k & 3;
@@ -242,31 +264,46 @@ MPC_HD void sincos_reduced(double x, double* sp, double* cp) {
     *sp = (q & 2) ? -s1 : s1;
     *cp = ((q + 1) & 2) ? -c1 : c1;
 }
+template <bool LL = false>
 MPC_HD void t_sincos(double a, double* s, double* c) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    sincos_reduced(a, s, c);        // device callers pass wrapped angles / boxed steering angles only (no large-argument path, no branch)
+    sincos_reduced<LL>(a, s, c);        // device callers pass wrapped angles / boxed steering angles only (no large-argument path, no branch)
 #else
     if (a > -1e5 && a < 1e5) sincos_reduced(a, s, c);
     else ::sincos(a, s, c);
 #endif
 }
+template <bool LL = false>
 MPC_HD void t_sincos(float a, float* s, float* c) { ::sincosf(a, s, c); }
+template <bool LL = false>
 MPC_HD double t_tan(double a) {
 #if !defined(__HIP_DEVICE_COMPILE__)
     if (!(a > -1e5 && a < 1e5)) return ::tan(a);
 #endif
     double s, c;
-    sincos_reduced(a, &s, &c);
+    sincos_reduced<LL>(a, &s, &c);
     return s * t_rcp(c);
 }
+template <bool LL = false>
 MPC_HD float t_tan(float a) { return ::tanf(a); }
 // false for NaN and +-inf.  (Not `(a - a) == 0`: with FMA contraction `a` = x*y turns that into fma(x, y, -(x*y)), the rounding
 // error of the product, which is not zero.)
 template <typename T> MPC_HD bool t_finite(T a) { return __builtin_isfinite(a); }
 
 // include/mpc_local_planner/utils/math_utils.h:81-91
-template <typename T>
+template <bool LL = false, typename T>
 MPC_HD T normalize_theta(T th) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (LL && sizeof(T) == 8) {      // the same operations on constants made at their use (MPC_LIT): x - 2 pi as x + (-(2 pi)), -pi as a source modifier
+        const T pi = MPC_LIT(3.14159265358979323846), two_pi = MPC_LIT(2 * 3.14159265358979323846);
+        if (th >= -pi && th < pi) return th;
+        T m = t_floor(th * MPC_LIT(0.15915494309189533577));
+        th = th - m * T(2) * pi;
+        if (th >= pi) th -= two_pi;
+        if (th < -pi) th += two_pi;
+        return th;
+    }
+#endif
     const T pi = T(3.14159265358979323846);
     if (th >= -pi && th < pi) return th;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -299,20 +336,22 @@ MPC_HD void t_frexp(float a, float* m, int* e) {
 // log(m) for a frexp mantissa m in [0.5, 1) (or any m in ~[0.35, 1.42]): the kernel of the classic fdlibm log --
 // f = m' - 1 with m' in [sqrt(1/2), sqrt(2)), s = f / (2 + f), log(1 + f) = f - hfsq + s (hfsq + R(s^2)) -- one reciprocal and
 // 14 FMAs instead of the general routine (exponent handling, sub-normals, special values).  Non-positive m yields NaN.
+template <bool LL = false>
 MPC_HD double log_mantissa(double m) {
-    const bool lo = m < 0.70710678118654752440;
+    const bool lo = m < MPC_LIT(0.70710678118654752440);
     const double f = (lo ? m + m : m) - 1.0;
     const double s = f * t_rcp(2.0 + f), z = s * s, w = z * z;
-    const double t1 = w * (3.999999999940941908e-01 + w * (2.222219843214978396e-01 + w * 1.531383769920937332e-01));
-    const double t2 = z * (6.666666666666735130e-01 + w * (2.857142874366239149e-01 + w * (1.818357216161805012e-01 + w * 1.479819860511658591e-01)));
+    const double t1 = w * (MPC_LIT(3.999999999940941908e-01) + w * (MPC_LIT(2.222219843214978396e-01) + w * MPC_LIT(1.531383769920937332e-01)));
+    const double t2 = z * (MPC_LIT(6.666666666666735130e-01) + w * (MPC_LIT(2.857142874366239149e-01) + w * (MPC_LIT(1.818357216161805012e-01) + w * MPC_LIT(1.479819860511658591e-01))));
     const double hfsq = 0.5 * f * f;
     const double r = f - (hfsq - s * (hfsq + (t1 + t2)));
-    const double out = lo ? r - 0.69314718055994530942 : r;
+    const double out = lo ? r - MPC_LIT(0.69314718055994530942) : r;
     return m > 0.0 ? out : (m - m) / (m - m) + __builtin_nan("");
 }
+template <bool LL = false>
 MPC_HD float log_mantissa(float m) { return t_log(m); }
 
-template <typename T>
+template <typename T, bool LL = false>
 struct LogAcc {
     T m;
     int e;
@@ -322,7 +361,7 @@ struct LogAcc {
         t_frexp(m * a, &mm, &ee);
         m = mm; e += ee;
     }
-    MPC_HD T value() const { return log_mantissa(m) + T(e) * T(0.69314718055994530942); }
+    MPC_HD T value() const { return log_mantissa<LL>(m) + T(e) * T(MPC_LIT(0.69314718055994530942)); }
 };
 
 // Model functions: f, G = df/d(theta,v,w), and the lambda-contracted second derivative.
@@ -333,19 +372,19 @@ struct ModelEval {
 };
 
 // trig cache per stage: t0 = sin, t1 = cos (of theta, or theta+beta), t2 = tan(w)|sin(w)|sin(beta), t3 = model extra
-template <typename T, int MODEL>
+template <typename T, int MODEL, bool LL = false>
 MPC_HD void model_trig(const Problem<T>& P, T th, T w, T tr[4]) {
     if (MODEL == MODEL_KINEMATIC_BICYCLE) {
         const T kap = P.p0 / (P.p1 + P.p0);
-        T t = t_tan(w);
+        T t = t_tan<LL>(w);
         T beta = t_atan(kap * t);
-        t_sincos(th + beta, &tr[0], &tr[1]);
+        t_sincos<LL>(th + beta, &tr[0], &tr[1]);
         tr[2] = t;
         tr[3] = beta;
     } else {
-        t_sincos(th, &tr[0], &tr[1]);
-        if (MODEL == MODEL_SIMPLE_CAR) { tr[2] = t_tan(w); tr[3] = T(0); }
-        else if (MODEL == MODEL_SIMPLE_CAR_FRONT) { t_sincos(w, &tr[2], &tr[3]); }
+        t_sincos<LL>(th, &tr[0], &tr[1]);
+        if (MODEL == MODEL_SIMPLE_CAR) { tr[2] = t_tan<LL>(w); tr[3] = T(0); }
+        else if (MODEL == MODEL_SIMPLE_CAR_FRONT) { t_sincos<LL>(w, &tr[2], &tr[3]); }
         else { tr[2] = T(0); tr[3] = T(0); }
     }
 }
@@ -436,37 +475,42 @@ MPC_HD int colloc_points(int method, T wt[2], T ce[2]) {
     if (method == COLLOC_CN) { wt[0] = T(0.5); wt[1] = T(1.5); ce[1] = T(2); return 2; }
     return 1;
 }
-template <typename T, int MODEL>
+template <typename T, int MODEL, bool LL = false>
 MPC_HD T model_heading_rate(const Problem<T>& P, T v, T w) {
     if (MODEL == MODEL_UNICYCLE) return w;
-    if (MODEL == MODEL_SIMPLE_CAR) return v * t_tan(w) / P.p0;
-    if (MODEL == MODEL_SIMPLE_CAR_FRONT) { T sw, cw; t_sincos(w, &sw, &cw); return v * sw / P.p0; }
-    T sb, cb; t_sincos(t_atan(P.p0 / (P.p1 + P.p0) * t_tan(w)), &sb, &cb); return v * sb / P.p0;
+    if (MODEL == MODEL_SIMPLE_CAR) return v * t_tan<LL>(w) / P.p0;
+    if (MODEL == MODEL_SIMPLE_CAR_FRONT) { T sw, cw; t_sincos<LL>(w, &sw, &cw); return v * sw / P.p0; }
+    T sb, cb; t_sincos<LL>(t_atan(P.p0 / (P.p1 + P.p0) * t_tan<LL>(w)), &sb, &cb); return v * sb / P.p0;
 }
-template <typename T, int MODEL>
-MPC_HD void model_trig_colloc(const Problem<T>& P, T th, T v, T w, T d, T tr[4], T tr2[2]) {
+// (method: P.collocation, or the copy of it a caller holds -- the solve kernel's record lives in LDS, where every P.x is a read and a wait)
+template <typename T, int MODEL, bool LL = false>
+MPC_HD void model_trig_colloc(const Problem<T>& P, int method, T th, T v, T w, T d, T tr[4], T tr2[2]) {
     tr2[0] = T(0); tr2[1] = T(0);
-    if (P.collocation == COLLOC_FWD) { model_trig<T, MODEL>(P, th, w, tr); return; }
+    if (method == COLLOC_FWD) { model_trig<T, MODEL, LL>(P, th, w, tr); return; }
     T wt[2], ce[2];
-    const int np_ = colloc_points<T>(P.collocation, wt, ce);
-    const T f2 = model_heading_rate<T, MODEL>(P, v, w);
-    model_trig<T, MODEL>(P, th + ce[0] * d * f2, w, tr);
+    const int np_ = colloc_points<T>(method, wt, ce);
+    const T f2 = model_heading_rate<T, MODEL, LL>(P, v, w);
+    model_trig<T, MODEL, LL>(P, th + ce[0] * d * f2, w, tr);
     if (np_ > 1) {
         T thb = th + ce[1] * d * f2;
         if (MODEL == MODEL_KINEMATIC_BICYCLE) thb += tr[3];      // heading + slip angle beta
-        t_sincos(thb, &tr2[0], &tr2[1]);
+        t_sincos<LL>(thb, &tr2[0], &tr2[1]);
     }
 }
 template <typename T, int MODEL>
-MPC_HD void colloc_f(const Problem<T>& P, const T tr[4], const T tr2[2], T v, T w, T f[3]) {
+MPC_HD void model_trig_colloc(const Problem<T>& P, T th, T v, T w, T d, T tr[4], T tr2[2]) { model_trig_colloc<T, MODEL>(P, P.collocation, th, v, w, d, tr, tr2); }
+template <typename T, int MODEL>
+MPC_HD void colloc_f(const Problem<T>& P, int method, const T tr[4], const T tr2[2], T v, T w, T f[3]) {
     model_f<T, MODEL>(P, tr, v, w, f);
-    if (P.collocation == COLLOC_CN) {
+    if (method == COLLOC_CN) {
         const T trb[4] = {tr2[0], tr2[1], tr[2], tr[3]};
         T fb[3];
         model_f<T, MODEL>(P, trb, v, w, fb);
         for (int a = 0; a < 3; ++a) f[a] = T(0.5) * f[a] + T(1.5) * fb[a];
     }
 }
+template <typename T, int MODEL>
+MPC_HD void colloc_f(const Problem<T>& P, const T tr[4], const T tr2[2], T v, T w, T f[3]) { colloc_f<T, MODEL>(P, P.collocation, tr, tr2, v, w, f); }
 template <typename T>
 struct StageMap {
     T f[3];          // sum_e wt_e f_e  (D = dt * f)
@@ -507,10 +551,10 @@ MPC_HD void psd_project4(StageMap<T>& sm, bool drop_theta) {
 }
 
 template <typename T, int MODEL>
-MPC_HD void stage_map(const Problem<T>& P, const T tr[4], const T tr2[2], T v, T w, T d, const T lam[3], StageMap<T>& o) {
+MPC_HD void stage_map(const Problem<T>& P, int method, const T tr[4], const T tr2[2], T v, T w, T d, const T lam[3], StageMap<T>& o) {
     T G[3][3], Hq[3][3];
     model_derivs<T, MODEL>(P, tr, v, w, lam, o.f, G, Hq);
-    if (P.collocation == COLLOC_FWD) {
+    if (method == COLLOC_FWD) {
         T gq[3];
         for (int j = 0; j < 3; ++j) gq[j] = lam[0] * G[0][j] + lam[1] * G[1][j] + lam[2] * G[2][j];
         for (int a = 0; a < 3; ++a) { o.Jdt[a] = o.f[a]; for (int j = 0; j < 3; ++j) o.Jq[a][j] = d * G[a][j]; }
@@ -519,7 +563,7 @@ MPC_HD void stage_map(const Problem<T>& P, const T tr[4], const T tr2[2], T v, T
         return;
     }
     T wt[2], ce[2];
-    const int np_ = colloc_points<T>(P.collocation, wt, ce);
+    const int np_ = colloc_points<T>(method, wt, ce);
     // second derivatives of the heading rate f_2 wrt (v, w): the lam = e_2 slice of the model Hessian (independent of the angle)
     const T e2[3] = {T(0), T(0), T(1)};
     T f_[3], G_[3][3], H2[3][3];
@@ -570,6 +614,8 @@ MPC_HD void stage_map(const Problem<T>& P, const T tr[4], const T tr2[2], T v, T
     for (int j = 0; j < 3; ++j) { o.Hqd[j] = L[j][3]; for (int l = 0; l < 3; ++l) o.Hqq[j][l] = L[j][l]; }
     o.Hdd = L[3][3];
 }
+template <typename T, int MODEL>
+MPC_HD void stage_map(const Problem<T>& P, const T tr[4], const T tr2[2], T v, T w, T d, const T lam[3], StageMap<T>& o) { stage_map<T, MODEL>(P, P.collocation, tr, tr2, v, w, d, lam, o); }
 
 // ---------------------------------------------------------------------------------------------
 // Structured backward (Riccati) stage step, shared by both kernels.

@@ -201,6 +201,17 @@ struct IpmWave {
     __device__ __forceinline__ T sw_ld_at(SwCRef p, int step) const { if constexpr (GS) return *(const GlbT*)((const GlbC*)gmb + (size_t)(p + (unsigned)step)); else return p[step]; }
     __device__ __forceinline__ void sw_st(SwRef p, int i, T v) const { if constexpr (GS) *(GlbT*)((GlbC*)gmb + (size_t)p + (size_t)(i * (int)sizeof(T))) = v; else p[i] = v; }
 
+    // kLocalLiterals: the fixed-layout fp64 kernels, shape known or not.  Their scalar registers are taken by the solve loop's uniform values, and every fp64 constant the
+    // compiler keeps across that loop is spill traffic at its uses (mpc_core.hpp, MPC_LIT).  In these kernels the wrap, the trig and the log kernels make their constants at
+    // the use, pow() is a call at all its (rarely executed) call sites -- inlined, its three dozen constants stood in registers across the loop --, and the collocation
+    // method is read from the record once per solve (colloc_).  The same arithmetic; every other kernel keeps its text.
+    static constexpr bool kLocalLiterals = NSC != 0 && sizeof(T) == 8;
+    static constexpr bool LL = kLocalLiterals;      // (what MPC_LIT reads inside this struct)
+    int colloc_ = 0;      // kLocalLiterals: P.collocation, wave-uniform, read by solve() in front of everything that evaluates a collocation row
+    __device__ __forceinline__ int colloc() const { if constexpr (kLocalLiterals) return colloc_; else return P.collocation; }
+    __device__ __forceinline__ T normalize_theta(T th) const { return mpc::normalize_theta<kLocalLiterals>(th); }      // (what every pass of this struct calls)
+    using LogAccT = LogAcc<T, kLocalLiterals>;
+
     // trial point z + alpha*dz, evaluated on the fly (no trial copy in LDS)
     // (alpha == 0 must not touch the step arrays: they are unwritten before the first factorisation, and 0 * garbage can be NaN)
     __device__ __forceinline__ T xt(int i, int k, T alpha) const {
@@ -259,7 +270,7 @@ struct IpmWave {
     // pow() of the device library is some 300 instructions and three dozen fp64 literals; inlined at its two (rarely executed) call sites of the solve loop the compiler
     // materialises those literals ONCE in front of the loop and -- in the 256-register kernels -- spills them to scratch for the whole solve.  There it is a call.
     __device__ __attribute__((noinline)) static T pow_cold(T a, T b) { return t_pow(a, b); }
-    __device__ __forceinline__ static T pow_(T a, T b) { if constexpr (W2) return pow_cold(a, b); else return t_pow(a, b); }
+    __device__ __forceinline__ static T pow_(T a, T b) { if constexpr (W2 || kLocalLiterals) return pow_cold(a, b); else return t_pow(a, b); }
     __device__ __forceinline__ static void U(T& v) { if constexpr (kUniformScalars) v = uni_(v); }
     template <typename... Ts> __device__ __forceinline__ static void U(T& v, Ts&... rest) { U(v); U(rest...); }
 

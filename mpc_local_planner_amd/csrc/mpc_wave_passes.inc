@@ -34,13 +34,13 @@
             T xn[3] = {xt(0, k + 1, al), xt(1, k + 1, al), xt(2, k + 1, al)};
             T v = ut(0, k, al), w = ut(1, k, al);
             T tr[4], tr2[2], f[3];
-            model_trig_colloc<T, MODEL>(P, xk[2], v, w, d, tr, tr2);
-            colloc_f<T, MODEL>(P, tr, tr2, v, w, f);
+            model_trig_colloc<T, MODEL, kLocalLiterals>(P, colloc(), xk[2], v, w, d, tr, tr2);
+            colloc_f<T, MODEL>(P, colloc(), tr, tr2, v, w, f);
             T c0 = d * f[0] - (xn[0] - xk[0]);
             T c1 = d * f[1] - (xn[1] - xk[1]);
             T c2 = d * f[2] - normalize_theta(xn[2] - xk[2]);
             for (int i = 0; i < NTRB; ++i) F(L.TRIG, i, k) = tr[i];
-            if (P.collocation == COLLOC_CN) { F(L.TRIG, NTRB, k) = tr2[0]; F(L.TRIG, NTRB + 1, k) = tr2[1]; }
+            if (colloc() == COLLOC_CN) { F(L.TRIG, NTRB, k) = tr2[0]; F(L.TRIG, NTRB + 1, k) = tr2[1]; }
             C_(0, k) = c0; C_(1, k) = c1; C_(2, k) = c2;
             th += t_abs(c0) + t_abs(c1) + t_abs(c2);
             if (quad()) {
@@ -80,7 +80,7 @@
     __device__ __forceinline__ T barrier_logs(T d, T alpha, bool trial, T dd) const {
         MPC_PHASE_LANE
         const int n = L.n;
-        LogAcc<T> acc;
+        LogAccT acc;
         for (int k = lane; k < n; k += kWave) {
             if (k < n - 1) {
                 for (int j = 0; j < 2; ++j) { T u = ut(j, k, trial ? alpha : T(0)); acc.mul(u - P.u_lb[j]); acc.mul(P.u_ub[j] - u); }
@@ -171,7 +171,7 @@
     __device__ __forceinline__ void trial_eval(const TrialRegs& r, T alpha, T d, T& th_out, T& fo_out, T& logs_out) const {
         MPC_PHASE_LANE
         T th = T(0), fo = T(0);
-        LogAcc<T> acc;
+        LogAccT acc;
         if (r.stage) {
             const T x0_ = r.xk[0] + alpha * r.dxk[0], x1_ = r.xk[1] + alpha * r.dxk[1];
             const T x2_ = r.k > 0 ? normalize_theta(r.xk[2] + alpha * r.dxk[2]) : r.xk[2];
@@ -179,11 +179,11 @@
             const T n2 = r.dxn[2] != T(0) ? normalize_theta(r.xn[2] + alpha * r.dxn[2]) : r.xn[2];
             const T v = r.u[0] + alpha * r.du[0], w = r.u[1] + alpha * r.du[1];
             T tr[4], tr2[2], f[3];
-            model_trig_colloc<T, MODEL>(P, x2_, v, w, d, tr, tr2);
-            colloc_f<T, MODEL>(P, tr, tr2, v, w, f);
+            model_trig_colloc<T, MODEL, kLocalLiterals>(P, colloc(), x2_, v, w, d, tr, tr2);
+            colloc_f<T, MODEL>(P, colloc(), tr, tr2, v, w, f);
             const T c0 = d * f[0] - (n0 - x0_), c1 = d * f[1] - (n1 - x1_), c2 = d * f[2] - normalize_theta(n2 - x2_);
             for (int i = 0; i < NTRB; ++i) F(L.TRIG, i, r.k) = tr[i];
-            if (P.collocation == COLLOC_CN) { F(L.TRIG, NTRB, r.k) = tr2[0]; F(L.TRIG, NTRB + 1, r.k) = tr2[1]; }
+            if (colloc() == COLLOC_CN) { F(L.TRIG, NTRB, r.k) = tr2[0]; F(L.TRIG, NTRB + 1, r.k) = tr2[1]; }
             C_(0, r.k) = c0; C_(1, r.k) = c1; C_(2, r.k) = c2;
             th = t_abs(c0) + t_abs(c1) + t_abs(c2);
             if (r.quad) {
@@ -251,12 +251,12 @@
                 T lam[3] = {F(L.LAM, 0, k), F(L.LAM, 1, k), F(L.LAM, 2, k)};
                 T tr[4] = {F(L.TRIG, 0, k), F(L.TRIG, 1, k), F(L.TRIG, 2, k), NTRB > 3 ? F(L.TRIG, 3, k) : T(0)};
                 T tr2[2] = {T(0), T(0)};
-                if (P.collocation == COLLOC_CN) { tr2[0] = F(L.TRIG, NTRB, k); tr2[1] = F(L.TRIG, NTRB + 1, k); }
+                if (colloc() == COLLOC_CN) { tr2[0] = F(L.TRIG, NTRB, k); tr2[1] = F(L.TRIG, NTRB + 1, k); }
                 T v = F(L.U, 0, k), w = F(L.U, 1, k);
                 // derivatives of the collocation increment D(theta, u, dt) (forward or midpoint differences, mpc_core.hpp::stage_map);
                 // gJ[j] = lam' dD/dq_j is what the dual residuals need, Jdt = dD/d dt the dt column of the row
                 StageMap<T> sm_;
-                stage_map<T, MODEL>(P, tr, tr2, v, w, d, lam, sm_);
+                stage_map<T, MODEL>(P, colloc(), tr, tr2, v, w, d, lam, sm_);
                 T gJ[3];
                 for (int j = 0; j < 3; ++j) gJ[j] = lam[0] * sm_.Jq[0][j] + lam[1] * sm_.Jq[1][j] + lam[2] * sm_.Jq[2][j];
                 // stage record, mu-independent part: kept in registers and stored at the END of the loop body -- every LDS store

@@ -35,6 +35,7 @@
         flags = __builtin_amdgcn_readfirstlane(flags);
         nfix = (int)fx(0) + (int)fx(1) + (int)fx(2);
         row0_on = dtprev != T(0);
+        if constexpr (kLocalLiterals) colloc_ = uni_(P.collocation);
         if (iter_cap <= 0) iter_cap = P.max_iter;
         if (lane < 8) sm[L.ZC + lane] = lane == 4 ? T(1) : T(0);      // constant coefficient triples of the sweeps
         if constexpr (GS) {      // ... and their copies where the sweeps' pointers live: the single words, and 0 0 0 1 0 0 in every stage's tile slot (guard tile and spare tiles included)

@@ -184,7 +184,7 @@
     __device__ __forceinline__ void accept(T alpha, T a_d) const {
         MPC_PHASE_LANE
         const int n = L.n;
-        const T kS = T(1e10);
+        const T kS = T(MPC_LIT(1e10)), ikS = LL ? T(MPC_LIT(1.0 / 1e10)) : T(1) / kS;      // (LL is fp64 only: the quotient as the compiler folds it)
         const T d_old = SCL(SC_D), dd = SCL(SC_DD), d_new = d_old + (dtf_sum() ? alpha * dd : T(0));
         // phase 1: everything that reads the OLD point
         T sn[4], yn[4];
@@ -205,7 +205,7 @@
                 sn[q] = s + alpha * ds;
                 T yv = y + a_d * dy;
                 const T musn = mu * t_rcp(sn[q]);
-                yn[q] = t_min(t_max(yv, musn * (T(1) / kS)), kS * musn);
+                yn[q] = t_min(t_max(yv, musn * ikS), kS * musn);
             }
             if (nM() > 0 && k >= 1 && k < n - 1) {
                 for (int m0 = 0; m0 < nM(); m0 += kRowGroup) {
@@ -228,15 +228,15 @@
                         const T so = s + alpha * ds, eo = ee + alpha * de;
                         T yo = y + a_d * dy;
                         const T muso = mu * t_rcp(so), mueo = mu * t_rcp(eo);
-                        yo = t_min(t_max(yo, muso * (T(1) / kS)), kS * muso);
-                        yo = t_min(t_max(yo, erho - kS * mueo), erho - mueo * (T(1) / kS));
+                        yo = t_min(t_max(yo, muso * ikS), kS * muso);
+                        yo = t_min(t_max(yo, erho - kS * mueo), erho - mueo * ikS);
                         F(L.OS, m, k) = so; F(L.OY, m, k) = yo; OE_(0, m, k) = eo;
                         continue;
                     }
                     const T so = s + alpha * (-res - jdz);
                     T yo = y + a_d * (mu * is + sig * res + sig * jdz - y);
                     const T muso = mu * t_rcp(so);
-                    yo = t_min(t_max(yo, muso * (T(1) / kS)), kS * muso);
+                    yo = t_min(t_max(yo, muso * ikS), kS * muso);
                     F(L.OS, m, k) = so; F(L.OY, m, k) = yo;
                 }
                 }
@@ -255,8 +255,8 @@
                     T pun = pu + a_d * (mu * idu - pu + (pu * idu) * du_);
                     T un = ut(j, k, alpha);
                     const T mdl = mu * t_rcp(un - P.u_lb[j]), mdu = mu * t_rcp(P.u_ub[j] - un);
-                    F(L.PL, j, k) = t_min(t_max(pln, mdl * (T(1) / kS)), kS * mdl);
-                    F(L.PU, j, k) = t_min(t_max(pun, mdu * (T(1) / kS)), kS * mdu);
+                    F(L.PL, j, k) = t_min(t_max(pln, mdl * ikS), kS * mdl);
+                    F(L.PU, j, k) = t_min(t_max(pun, mdu * ikS), kS * mdu);
                     F(L.U, j, k) = un;
                 }
                 for (int i = 0; i < 3; ++i) {
@@ -275,8 +275,8 @@
                 T pln = pl + a_d * (mu * idl - pl - (pl * idl) * dd);
                 T pun = pu + a_d * (mu * idu - pu + (pu * idu) * dd);
                 const T mdl = mu * t_rcp(d_new - P.dt_lb), mdu = mu * t_rcp(P.dt_ub - d_new);
-                SCL(SC_PDL) = t_min(t_max(pln, mdl * (T(1) / kS)), kS * mdl);
-                SCL(SC_PDU) = t_min(t_max(pun, mdu * (T(1) / kS)), kS * mdu);
+                SCL(SC_PDL) = t_min(t_max(pln, mdl * ikS), kS * mdl);
+                SCL(SC_PDU) = t_min(t_max(pun, mdu * ikS), kS * mdu);
             }
             SCL(SC_D) = d_new;
             if (ball()) {        // from the caches of the OLD point (value, gradient) and the step
@@ -284,7 +284,7 @@
                 const T so = s + alpha * (-res - jdz);
                 T yo = y + a_d * (mu * is + sig * res + sig * jdz - y);
                 const T muso = mu * t_rcp(so);
-                yo = t_min(t_max(yo, muso * (T(1) / kS)), kS * muso);
+                yo = t_min(t_max(yo, muso * ikS), kS * muso);
                 SCL(SC_TS) = so; SCL(SC_TY) = yo;
             }
         }

@@ -236,6 +236,40 @@ PROTOTYPES = {
 }
 
 
+class MpcPool(C.Structure):
+    """struct mpc_pool (include/mpc_fleet.h): P obstacles laid out like one instance of mpc_obstacles; raw addresses (host or device)."""
+    _fields_ = [
+        ("P", C.c_int32),
+        ("n_vertices", C.c_void_p),
+        ("vertices", C.c_void_p),
+        ("radius", C.c_void_p),
+        ("velocity", C.c_void_p),
+    ]
+
+
+class MpcPoolParams(C.Structure):
+    """struct mpc_pool_params (include/mpc_fleet.h); field-for-field."""
+    _fields_ = [
+        ("reach", C.c_double),
+        ("min_speed", C.c_double),
+        ("append", C.c_int32),
+    ]
+
+
+# ---- the functions of include/mpc_fleet.h, in the same form.  They are exported by the same library and bound by _lib.load(), but are no part of PROTOTYPES / _lib.EXPORTS:
+# those mirror include/mpc_hip.h alone.  tests/test_fleet_abi.py holds every row to its declaration.
+# s, B, pool, robot_pose, self_index, params, n_obstacles, n_vertices, vertices, radius, velocity, dropped, n_taken
+_FROM_POOL = (_rc, [_p, _i, C.POINTER(MpcPool), _p, _p, C.POINTER(MpcPoolParams)] + [_p] * 7)
+# s, B, robot_pose, x, dt, status, robot_radius, robot_radius per robot, pool_offset, pool_n_vertices, pool_vertices, pool_radius, pool_velocity
+_FLEET_POOL = (_rc, [_p, _i, _p, _p, _p, _p, _d, _p, _i, _p, _p, _p, _p])
+
+FLEET_PROTOTYPES = {
+    "mpc_pool_params_defaults": (None, [_p, C.POINTER(MpcPoolParams)]),                         # s, p
+    "mpc_obstacles_from_pool": _FROM_POOL, "mpc_obstacles_from_pool_device": _FROM_POOL,
+    "mpc_fleet_pool": _FLEET_POOL, "mpc_fleet_pool_device": _FLEET_POOL,
+}
+
+
 def _diag_offdiag(w, dim):
     """a weight given as its diagonal or as a full dim x dim matrix -> (diagonal, off-diagonal terms (0,1)[, (0,2), (1,2)] of the symmetric part)"""
     rows = [list(r) if hasattr(r, "__len__") else None for r in w]

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/mpc_hip.h"
+#include "../../include/mpc_fleet.h"
 #include "mpc_core.hpp"
 #include "mpc_problem.hpp"
 #include "mpc_launch_plan.hpp"
@@ -23,6 +24,7 @@
 #include "mpc_controller_cycle.hpp"
 #include "mpc_evaluate.hpp"
 #include "mpc_plan_inputs.hpp"
+#include "mpc_fleet_obstacles.hpp"
 
 namespace {
 
@@ -1207,6 +1209,117 @@ int mpc_commands_batch(mpc_solver* s, int32_t B, const double* u_out, const int3
     return staged_call(s, "mpc_commands_batch", false, false, pc, 9, [&](void** d) {
         return commands_device(s, B, (const double*)d[0], 1, (const int32_t*)d[1], (const int32_t*)d[2], (const int32_t*)d[3], (double*)d[4], (int32_t*)d[5],
                                (int32_t*)d[6], (double*)d[7], (int32_t*)d[8]);
+    });
+}
+
+}  // extern "C"
+
+// ---- obstacles from a pool, and a pool from the fleet (mpc_fleet_obstacles.hpp; declared in include/mpc_fleet.h)
+
+// the argument checks both variants of mpc_obstacles_from_pool share: NULL when the call is fine
+static const char* from_pool_error(const mpc_solver* s, const mpc_pool* pool, const void* robot_pose, const mpc_pool_params* p, const void* n_obstacles, const void* n_vertices,
+                                   const void* vertices, const void* radius, const void* velocity) {
+    if (!s || !pool || !robot_pose || !p || !n_obstacles || !n_vertices || !vertices) return "mpc_obstacles_from_pool: null argument (pool, robot_pose, params, n_obstacles, n_vertices, vertices)";
+    if (s->cfg.max_obstacles <= 0) return "mpc_obstacles_from_pool: the solver was created with max_obstacles = 0";
+    if (pool->P < 0) return "mpc_obstacles_from_pool: P is negative";
+    if (pool->P > 0 && (!pool->n_vertices || !pool->vertices)) return "mpc_obstacles_from_pool: null pool array (n_vertices, vertices)";
+    if (!(p->reach >= 0.0) || p->reach - p->reach != 0.0) return "mpc_obstacles_from_pool: reach has to be finite and not negative";
+    if ((pool->radius && !radius) || (pool->velocity && !velocity)) return "mpc_obstacles_from_pool: the pool carries a radius / velocity and the container has no array for it";
+    return nullptr;
+}
+static const char* fleet_pool_error(const mpc_solver* s, const void* robot_pose, const void* x, const void* dt, int32_t pool_offset, const void* pool_n_vertices, const void* pool_vertices) {
+    if (!s || !robot_pose || !pool_n_vertices || !pool_vertices) return "mpc_fleet_pool: null argument (robot_pose, pool_n_vertices, pool_vertices)";
+    if (x && !dt) return "mpc_fleet_pool: x without dt";
+    if (pool_offset < 0) return "mpc_fleet_pool: pool_offset is negative";
+    return nullptr;
+}
+
+// x_stride: rows between two robots' first states (cfg.n for x_out itself; 2 for the host variant's compact copy of the first two rows)
+static int fleet_pool_device(mpc_solver* s, int32_t B, const double* d_robot_pose, const double* d_x, int32_t x_stride, const double* d_dt, const int32_t* d_status, double robot_radius,
+                             const double* d_robot_radius, int32_t pool_offset, int32_t* d_pool_n_vertices, double* d_pool_vertices, double* d_pool_radius, double* d_pool_velocity) {
+    g_err[0] = 0;
+    if (const char* e = fleet_pool_error(s, d_robot_pose, d_x, d_dt, pool_offset, d_pool_n_vertices, d_pool_vertices)) { set_err(e); return MPC_EINVAL; }
+    if (B <= 0) return MPC_OK;
+    if (const int rc = refused(s, B, REF_MAX_BATCH, "mpc_fleet_pool")) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    mpc::FleetPoolArgs a;
+    a.B = B; a.n_stride = x_stride; a.V = s->cfg.max_vertices > 0 ? s->cfg.max_vertices : 1; a.pool_offset = pool_offset;
+    a.pose = d_robot_pose; a.x = d_x; a.dt = d_dt; a.status = d_status; a.robot_radius = robot_radius; a.radius = d_robot_radius;
+    a.pool_n_vertices = d_pool_n_vertices; a.pool_vertices = d_pool_vertices; a.pool_radius = d_pool_radius; a.pool_velocity = d_pool_velocity;
+    hipLaunchKernelGGL(mpc::fleet_pool_kernel, dim3((B + 63) / 64), dim3(64), 0, s->stream, a);
+    HIP_TRY(hipGetLastError());
+    return MPC_OK;
+}
+
+extern "C" {
+
+void mpc_pool_params_defaults(const mpc_solver* s, mpc_pool_params* p) {
+    if (!p) return;
+    p->reach = s ? s->cfg.cutoff_dist : 0.0;
+    p->min_speed = 0.001;      // believed: teb_local_planner's Obstacle::setCentroidVelocity (mpc_fleet_obstacles.hpp)
+    p->append = 1;
+}
+
+int mpc_obstacles_from_pool_device(mpc_solver* s, int32_t B, const mpc_pool* pool, const double* d_robot_pose, const int32_t* d_self_index, const mpc_pool_params* params,
+                                   int32_t* d_n_obstacles, int32_t* d_n_vertices, double* d_vertices, double* d_radius, double* d_velocity, int32_t* d_dropped, int32_t* d_n_taken) {
+    g_err[0] = 0;
+    if (const char* e = from_pool_error(s, pool, d_robot_pose, params, d_n_obstacles, d_n_vertices, d_vertices, d_radius, d_velocity)) { set_err(e); return MPC_EINVAL; }
+    if (B <= 0) return MPC_OK;
+    if (const int rc = refused(s, B, REF_MAX_BATCH, "mpc_obstacles_from_pool")) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    mpc::FleetSelectArgs a;
+    a.pool = {pool->P, pool->n_vertices, pool->vertices, pool->radius, pool->velocity};
+    a.prm = {params->reach, params->min_speed, params->append};
+    a.pose = d_robot_pose; a.self_index = d_self_index;
+    a.O = s->cfg.max_obstacles; a.V = s->cfg.max_vertices > 0 ? s->cfg.max_vertices : 1;
+    a.n_obstacles = d_n_obstacles; a.n_vertices = d_n_vertices; a.vertices = d_vertices; a.radius = d_radius; a.velocity = d_velocity;
+    a.dropped = d_dropped; a.n_taken = d_n_taken;
+    hipLaunchKernelGGL(mpc::fleet_select_kernel, dim3(B), dim3(mpc::kFleetThreads), 0, s->stream, a);
+    HIP_TRY(hipGetLastError());
+    return MPC_OK;
+}
+
+int mpc_obstacles_from_pool(mpc_solver* s, int32_t B, const mpc_pool* pool, const double* robot_pose, const int32_t* self_index, const mpc_pool_params* params,
+                            int32_t* n_obstacles, int32_t* n_vertices, double* vertices, double* radius, double* velocity, int32_t* dropped, int32_t* n_taken) {
+    g_err[0] = 0;
+    if (const char* e = from_pool_error(s, pool, robot_pose, params, n_obstacles, n_vertices, vertices, radius, velocity)) { set_err(e); return MPC_EINVAL; }
+    if (B <= 0) return MPC_OK;
+    if (const int rc = refused(s, B, REF_MAX_BATCH, "mpc_obstacles_from_pool")) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t nb = (size_t)B, O = s->cfg.max_obstacles, V = s->cfg.max_vertices > 0 ? s->cfg.max_vertices : 1, np = (size_t)pool->P;
+    // in / out: the container, whose slots below the old and at or above the new n_obstacles[b] the kernel leaves alone
+    const mpc::StagePiece pc[13] = {stage_in(pool->n_vertices, np * 4), stage_in(pool->vertices, np * V * 16), stage_in(pool->radius, np * 8), stage_in(pool->velocity, np * 16),
+                                    stage_in(robot_pose, nb * 24), stage_in(self_index, nb * 4), stage_inout(n_obstacles, nb * 4), stage_inout(n_vertices, nb * O * 4),
+                                    stage_inout(vertices, nb * O * V * 16), stage_inout(radius, nb * O * 8), stage_inout(velocity, nb * O * 16), stage_out(dropped, nb * 4), stage_out(n_taken, nb * 4)};
+    return staged_call(s, "mpc_obstacles_from_pool", false, false, pc, 13, [&](void** d) {
+        const mpc_pool dp = {pool->P, (const int32_t*)d[0], (const double*)d[1], (const double*)d[2], (const double*)d[3]};
+        return mpc_obstacles_from_pool_device(s, B, &dp, (const double*)d[4], (const int32_t*)d[5], params, (int32_t*)d[6], (int32_t*)d[7], (double*)d[8], (double*)d[9], (double*)d[10],
+                                              (int32_t*)d[11], (int32_t*)d[12]);
+    });
+}
+
+int mpc_fleet_pool_device(mpc_solver* s, int32_t B, const double* d_robot_pose, const double* d_x, const double* d_dt, const int32_t* d_status, double robot_radius,
+                          const double* d_robot_radius, int32_t pool_offset, int32_t* d_pool_n_vertices, double* d_pool_vertices, double* d_pool_radius, double* d_pool_velocity) {
+    return fleet_pool_device(s, B, d_robot_pose, d_x, s ? s->cfg.n : 0, d_dt, d_status, robot_radius, d_robot_radius, pool_offset, d_pool_n_vertices, d_pool_vertices, d_pool_radius, d_pool_velocity);
+}
+
+int mpc_fleet_pool(mpc_solver* s, int32_t B, const double* robot_pose, const double* x, const double* dt, const int32_t* status, double robot_radius,
+                   const double* robot_radius_per_robot, int32_t pool_offset, int32_t* pool_n_vertices, double* pool_vertices, double* pool_radius, double* pool_velocity) {
+    g_err[0] = 0;
+    if (const char* e = fleet_pool_error(s, robot_pose, x, dt, pool_offset, pool_n_vertices, pool_vertices)) { set_err(e); return MPC_EINVAL; }
+    if (B <= 0) return MPC_OK;
+    if (const int rc = refused(s, B, REF_MAX_BATCH, "mpc_fleet_pool")) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t nb = (size_t)B, n = (size_t)s->cfg.n, V = s->cfg.max_vertices > 0 ? s->cfg.max_vertices : 1, off = (size_t)pool_offset;
+    std::vector<double> x01;      // only the first two states of every robot travel
+    if (x) { x01.resize(6 * nb); for (size_t b = 0; b < nb; ++b) memcpy(&x01[6 * b], x + b * n * 3, 48); }
+    // the B entries behind pool_offset alone; in / out: the vertices behind the first of an entry stay
+    const mpc::StagePiece pc[9] = {stage_in(robot_pose, nb * 24), stage_in(x ? x01.data() : nullptr, nb * 48), stage_in(dt, nb * 8), stage_in(status, nb * 4), stage_in(robot_radius_per_robot, nb * 8),
+                                   stage_out(pool_n_vertices + off, nb * 4), stage_inout(pool_vertices + off * V * 2, nb * V * 16), stage_out(pool_radius ? pool_radius + off : nullptr, nb * 8),
+                                   stage_out(pool_velocity ? pool_velocity + 2 * off : nullptr, nb * 16)};
+    return staged_call(s, "mpc_fleet_pool", false, false, pc, 9, [&](void** d) {
+        return fleet_pool_device(s, B, (const double*)d[0], (const double*)d[1], 2, (const double*)d[2], (const int32_t*)d[3], robot_radius, (const double*)d[4], 0, (int32_t*)d[5], (double*)d[6],
+                                 (double*)d[7], (double*)d[8]);
     });
 }
 

@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._abi import MpcConfig, MpcCycleParams, MpcEvalOut, MpcObstacles, MpcPlanParams, MPC_OK
+from ._abi import MpcConfig, MpcCycleParams, MpcEvalOut, MpcObstacles, MpcPlanParams, MpcPool, MpcPoolParams, MPC_OK
 
 
 class MpcError(RuntimeError):
@@ -319,6 +319,78 @@ class BatchSolver:
         """mpc_commands_batch_device: the same with device addresses (ints), asynchronous on the solver's stream; reset_next / u_prev_next are the reset / u_prev of the
         next controller_step_device"""
         self._check(self._lib.mpc_commands_batch_device(self._h, int(B), *map(_dev, (u, status, feasible, plan_flags, cmd, result, reset_next, u_prev_next, infeasible_count))))
+
+    def pool_params(self, **fields) -> MpcPoolParams:
+        """mpc_pool_params with the library's defaults (mpc_pool_params_defaults: reach = cfg.cutoff_dist, min_speed = 0.001, append = 1), then the given fields"""
+        p = MpcPoolParams()
+        self._lib.mpc_pool_params_defaults(self._h, C.byref(p))
+        for k, v in fields.items():
+            if k not in dict(MpcPoolParams._fields_):
+                raise ValueError(f"mpc_pool_params has no field {k}")
+            setattr(p, k, v)
+        return p
+
+    def obstacles_from_pool(self, pool, robot_pose, self_index=None, params=None, obstacles=None):
+        """Obstacles that are not in the costmap, for B robots (mpc_obstacles_from_pool, include/mpc_fleet.h): the entries of a shared pool within params.reach of each
+        robot, the nearest ones when they do not all fit, behind what the robot's container holds.  pool = (n_vertices (P,), vertices (P, V, 2)[, radius (P,)[, velocity
+        (P, 2)]]) in the planning frame; robot_pose (B, 3); self_index (B,): the pool entry that is the robot itself (-1 / None: none); obstacles: an existing container
+        (n_obstacles, n_vertices, vertices[, radius[, velocity]]) to append to -- it is copied, not written -- or None for an empty one.
+        Returns (n_obstacles (B,), n_vertices (B, O), vertices (B, O, V, 2), radius (B, O), velocity (B, O, 2), dropped (B,), n_taken (B,)): the first five are `obstacles`
+        of solve() / step() / controller_step()."""
+        rp = np.ascontiguousarray(robot_pose, dtype=np.float64)
+        B, O, V = int(rp.shape[0]), int(self.cfg.max_obstacles), max(1, int(self.cfg.max_vertices))
+        rp = _as_f64(rp, (B, 3))
+        pnv = np.ascontiguousarray(pool[0], dtype=np.int32).reshape(-1)
+        P = int(pnv.shape[0])
+        pv = _as_f64(pool[1], (P, V, 2))
+        pr = _as_f64(pool[2], (P,)) if len(pool) > 2 and pool[2] is not None else None
+        pvel = _as_f64(pool[3], (P, 2)) if len(pool) > 3 and pool[3] is not None else None
+        si = _as_i32(self_index, B, "self_index")
+        params = self.pool_params() if params is None else params
+        given = tuple(obstacles) + (None,) * 5 if obstacles is not None else (None,) * 5
+        held = lambda a, shape, dtype: np.zeros(shape, dtype) if a is None else np.array(a, dtype=dtype).reshape(shape)
+        no, nv, vt = held(given[0], (B,), np.int32), held(given[1], (B, O), np.int32), held(given[2], (B, O, V, 2), np.float64)
+        rd, vl = held(given[3], (B, O), np.float64), held(given[4], (B, O, 2), np.float64)
+        dr, tk = np.zeros(B, np.int32), np.zeros(B, np.int32)
+        cp = MpcPool(P, *(a.ctypes.data if a is not None and P > 0 else None for a in (pnv, pv, pr, pvel)))
+        self._check(self._lib.mpc_obstacles_from_pool(self._h, B, C.byref(cp), _addr(rp), _addr(si), C.byref(params), *map(_addr, (no, nv, vt, rd, vl, dr, tk))))
+        return no, nv, vt, rd, vl, dr, tk
+
+    def obstacles_from_pool_device(self, B: int, pool, robot_pose: int, self_index: Optional[int], params: MpcPoolParams, n_obstacles: int, n_vertices: int, vertices: int,
+                                   radius: Optional[int] = None, velocity: Optional[int] = None, dropped: Optional[int] = None, n_taken: Optional[int] = None) -> None:
+        """mpc_obstacles_from_pool_device: the same with device addresses (ints), asynchronous on the solver's stream; pool = (P, n_vertices, vertices[, radius[, velocity]])
+        with device addresses; n_obstacles is read and written, e.g. right behind mpc_costmap_to_obstacles_device on the same arrays"""
+        cp = MpcPool(int(pool[0]), *((tuple(a or None for a in pool[1:]) + (None,) * 4)[:4]))
+        self._check(self._lib.mpc_obstacles_from_pool_device(self._h, int(B), C.byref(cp), _dev(robot_pose), _dev(self_index), C.byref(params),
+                                                             *map(_dev, (n_obstacles, n_vertices, vertices, radius, velocity, dropped, n_taken))))
+
+    def fleet_pool(self, robot_pose, x=None, dt=None, status=None, radius=0.0, pool=None, pool_offset: int = 0):
+        """A pool made of the fleet itself (mpc_fleet_pool, include/mpc_fleet.h): robot b becomes entry pool_offset + b -- a circle of its radius at its pose, with the
+        velocity of the first interval of its own plan.  robot_pose (B, 3); x (B, n, 3), dt (B,), status (B,): BatchResult.x / .dt / .status of the robots' solves (None:
+        velocity 0); radius: one number or (B,).  pool: existing arrays (n_vertices, vertices, radius, velocity) to write into -- copied -- or None for one of
+        pool_offset + B entries.  Returns (n_vertices (P,), vertices (P, V, 2), radius (P,), velocity (P, 2)): `pool` of obstacles_from_pool, with self_index =
+        pool_offset + arange(B)."""
+        rp = np.ascontiguousarray(robot_pose, dtype=np.float64)
+        B, V, off = int(rp.shape[0]), max(1, int(self.cfg.max_vertices)), int(pool_offset)
+        rp = _as_f64(rp, (B, 3))
+        xs, dts, st = _as_f64(x, (B, self.n, 3)), _as_f64(dt, (B,)), _as_i32(status, B, "status")
+        per_robot = None if np.ndim(radius) == 0 else _as_f64(radius, (B,))
+        P = max(off, 0) + B if pool is None else int(np.shape(pool[0])[0])
+        if off < 0 or off + B > P:
+            raise ValueError("the pool has no room for pool_offset + B entries")
+        held = lambda a, shape, dtype: np.zeros(shape, dtype) if a is None else np.array(a, dtype=dtype).reshape(shape)
+        given = (None,) * 4 if pool is None else tuple(pool)
+        nv, vt, rd, vl = held(given[0], (P,), np.int32), held(given[1], (P, V, 2), np.float64), held(given[2], (P,), np.float64), held(given[3], (P, 2), np.float64)
+        self._check(self._lib.mpc_fleet_pool(self._h, B, _addr(rp), _addr(xs), _addr(dts), _addr(st), 0.0 if per_robot is not None else float(radius), _addr(per_robot), off,
+                                             *map(_addr, (nv, vt, rd, vl))))
+        return nv, vt, rd, vl
+
+    def fleet_pool_device(self, B: int, robot_pose: int, x: Optional[int], dt: Optional[int], status: Optional[int], radius: float, pool_n_vertices: int, pool_vertices: int,
+                          pool_radius: Optional[int] = None, pool_velocity: Optional[int] = None, pool_offset: int = 0, radius_per_robot: Optional[int] = None) -> None:
+        """mpc_fleet_pool_device: the same with device addresses (ints), asynchronous on the solver's stream -- e.g. right behind solve_device on its outputs; the pool
+        arrays feed obstacles_from_pool_device"""
+        self._check(self._lib.mpc_fleet_pool_device(self._h, int(B), _dev(robot_pose), _dev(x), _dev(dt), _dev(status), float(radius), _dev(radius_per_robot), int(pool_offset),
+                                                    *map(_dev, (pool_n_vertices, pool_vertices, pool_radius, pool_velocity))))
 
     def set_grid_sizes(self, n_grid=None):
         """Per-instance grid sizes n_i <= cfg.n for the following solves (grid adaptation); None = uniform cfg.n."""

@@ -270,6 +270,26 @@ FLEET_PROTOTYPES = {
 }
 
 
+class MpcClusterParams(C.Structure):
+    """struct mpc_cluster_params (include/mpc_costmap_clusters.h); field-for-field."""
+    _fields_ = [
+        ("behind_robot_dist", C.c_double),
+        ("link_dist_sq", C.c_int32),
+    ]
+
+
+# ---- the functions of include/mpc_costmap_clusters.h, in the same form: exported by the same library, bound by _lib.load(), no part of PROTOTYPES / _lib.EXPORTS.
+# tests/test_costmap_clusters_abi.py holds every row to its declaration.
+# s, B, cost, size_x, size_y, resolution, origin, robot_pose, params, n_obstacles, n_vertices, vertices, radius, velocity, dropped, info
+_TO_POLYGONS = (_rc, [_p, _i, _p, _i, _i, _d, _p, _p, C.POINTER(MpcClusterParams)] + [_p] * 7)
+
+CLUSTER_PROTOTYPES = {
+    "mpc_cluster_params_defaults": (None, [C.POINTER(MpcClusterParams), _d, _d]),               # p, resolution, cluster_max_distance
+    "mpc_costmap_to_polygons": _TO_POLYGONS, "mpc_costmap_to_polygons_device": _TO_POLYGONS,
+    "mpc_last_costmap_ms": (_rc, [_p, C.POINTER(C.c_float)]),                                   # s, ms
+}
+
+
 def _diag_offdiag(w, dim):
     """a weight given as its diagonal or as a full dim x dim matrix -> (diagonal, off-diagonal terms (0,1)[, (0,2), (1,2)] of the symmetric part)"""
     rows = [list(r) if hasattr(r, "__len__") else None for r in w]

@@ -13,9 +13,18 @@
 // rejected with one SWAR test -- a workgroup scan over (column outer, band inner) turns the counts into output positions, pass 2
 // (served from L2) walks the same pieces again and writes the obstacles: stable in the reference's order without any sorting.
 // HBM-bound byte work: algorithmic traffic = size_x * size_y bytes read + 20 bytes written per obstacle.
+//
+// The helpers in front of the kernel (cm_world, cm_keep, cm_load, cm_lethal_mask, ...) are host / device functions: a g++ build of mpc_costmap_clusters.hpp, which
+// scans with them, compiles them for the tests.  The kernel itself exists under hipcc only.
 #pragma once
-#include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define MPC_CM_HD __host__ __device__ __forceinline__
+#else
+#define MPC_CM_HD inline
+#endif
 
 namespace mpc {
 
@@ -37,13 +46,13 @@ struct CostmapArgs {
 
 // products and sums are kept un-fused (hipcc contracts a + b * c into an fma by default, and the __d*_rn intrinsics are plain operators
 // that get contracted as well) so that the cell centres are bit-identical to the reference's double arithmetic
-__device__ __forceinline__ double cm_world(double origin, int m, double res) {
+MPC_CM_HD double cm_world(double origin, int m, double res) {
 #pragma clang fp contract(off)
     const double c = ((double)m + 0.5) * res;
     return origin + c;
 }
 
-__device__ __forceinline__ bool cm_keep(double wx, double wy, double px, double py, double ox, double oy, double behind) {
+MPC_CM_HD bool cm_keep(double wx, double wy, double px, double py, double ox, double oy, double behind) {
 #pragma clang fp contract(off)
     const double dx = wx - px, dy = wy - py;
     const double a = dx * ox, b = dy * oy;
@@ -58,7 +67,7 @@ constexpr int kCmPiece = 16;                      // bytes per load = columns pe
 constexpr int kCmRows = 4;                        // rows loaded back to back per thread (memory-level parallelism)
 constexpr int kCmSlabCols = kCmPiece * kCostmapThreads;   // widest slab handled in one sweep (4096 columns)
 
-__device__ __forceinline__ bool cm_has_lethal(uint32_t v) {          // any byte == 254 ?
+MPC_CM_HD bool cm_has_lethal(uint32_t v) {          // any byte == 254 ?
     const uint32_t x = v ^ 0xFEFEFEFEu;
     return ((x - 0x01010101u) & ~x & 0x80808080u) != 0u;
 }
@@ -66,7 +75,7 @@ __device__ __forceinline__ bool cm_has_lethal(uint32_t v) {          // any byte
 struct CmPiece { uint32_t w[4]; };
 // 16 bytes (unaligned), bytes >= valid read as 0.  All indices are compile-time constants after unrolling: a dynamically indexed
 // piece would live in scratch memory.
-__device__ __forceinline__ CmPiece cm_load(const uint8_t* p, int valid) {
+MPC_CM_HD CmPiece cm_load(const uint8_t* p, int valid) {
     CmPiece q;
     if (valid >= kCmPiece) __builtin_memcpy(&q, p, kCmPiece);
     else {
@@ -76,16 +85,18 @@ __device__ __forceinline__ CmPiece cm_load(const uint8_t* p, int valid) {
     }
     return q;
 }
-__device__ __forceinline__ bool cm_any_lethal(const CmPiece& q) {
+MPC_CM_HD bool cm_any_lethal(const CmPiece& q) {
     return cm_has_lethal(q.w[0]) | cm_has_lethal(q.w[1]) | cm_has_lethal(q.w[2]) | cm_has_lethal(q.w[3]);
 }
 // bit e set <=> byte e of the piece is LETHAL (branch-free SWAR per dword; exact, no cross-byte carries: x ^ 0xFE is 0 only there)
-__device__ __forceinline__ uint32_t cm_lethal_mask(const CmPiece& q) {
+MPC_CM_HD uint32_t cm_lethal_mask(const CmPiece& q) {
     uint32_t m = 0u;
 #pragma unroll
     for (int e = 0; e < kCmPiece; ++e) m |= (((q.w[e >> 2] >> (8 * (e & 3))) & 0xFFu) == kLethal ? 1u : 0u) << e;
     return m;
 }
+
+#if defined(__HIPCC__)
 
 __global__ __launch_bounds__(kCostmapThreads) void costmap_to_obstacles_kernel(CostmapArgs a) {
     __shared__ int cnt[kCmSlabCols];                  // (column in slab) * R + band  ->  count, then output position
@@ -183,5 +194,7 @@ __global__ __launch_bounds__(kCostmapThreads) void costmap_to_obstacles_kernel(C
         if (a.dropped) a.dropped[b] = total > a.O ? total - a.O : 0;
     }
 }
+
+#endif  // __HIPCC__
 
 }  // namespace mpc

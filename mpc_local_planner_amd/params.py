@@ -400,6 +400,44 @@ def plan_params_from_options(plugin_options: dict, costmap_shape, resolution: fl
     return c
 
 
+CLUSTER_PLUGIN = "costmap_converter::CostmapToPolygonsDBSMCCH"
+
+
+def cluster_params_from_options(plugin_options: dict, converter_params: dict | None, resolution: float):
+    """struct mpc_cluster_params (mpc_costmap_to_polygons*, BatchSolver.costmap_to_polygons_device) from what plugin_options_from_params returns and the plugin namespace's
+    parameter tree, which holds the converter's block: `costmap_converter/CostmapToPolygonsDBSMCCH` (as ONE key, the way the shipped yaml writes it, or nested), or the
+    block of the plugin that costmap_converter_plugin names.  Read: cluster_max_distance (0.4) and cluster_min_pts (2), the in-code defaults of the shipped
+    costmap_converter_params.yaml's values; link_dist_sq = clamp(floor((cluster_max_distance / resolution)^2 + 1e-9), 1, 64), as mpc_cluster_params_defaults has it.
+    Returns (params, notes).  A note, not an error, says where the library does something else than the configured plugin would: clusters and convex hulls are what this
+    library builds -- so for cluster_min_pts > 2 (small clusters are not discarded as noise) and for the line / RANSAC / concave-hull plugins."""
+    tree = converter_params or {}
+    plugin = str(plugin_options.get("costmap_converter_plugin", "") or "")
+    notes: list[str] = []
+
+    def block(name):
+        key = name.replace("::", "/")
+        if isinstance(tree.get(key), dict):
+            return tree[key]
+        node = tree
+        for part in key.split("/"):
+            node = node.get(part) if isinstance(node, dict) else None
+        return node if isinstance(node, dict) else None
+
+    b = (block(plugin) if plugin else None) or block(CLUSTER_PLUGIN) or {}
+    r = _Reader(b)
+    d, min_pts = r.get("cluster_max_distance", 0.4), r.get("cluster_min_pts", 2)
+    if plugin and plugin != CLUSTER_PLUGIN:
+        notes.append(f"costmap_converter_plugin {plugin}: clusters and convex hulls are what this library builds ({CLUSTER_PLUGIN} at cluster_min_pts <= 2)")
+    if min_pts > 2:
+        notes.append(f"cluster_min_pts {min_pts}: clusters and convex hulls are what this library builds; clusters of fewer cells are kept (every cell with a neighbour is a core point)")
+    c = A.MpcClusterParams()
+    c.behind_robot_dist = float(plugin_options.get("costmap_obstacles_behind_robot_dist", 1.5))
+    q = d / float(resolution) if resolution else float("nan")
+    sq = math.floor(q * q + 1e-9) if math.isfinite(q) else 1
+    c.link_dist_sq = int(min(max(sq, 1), 64))
+    return c, notes
+
+
 def _is_number(v) -> bool:
     return isinstance(v, (int, float)) and not isinstance(v, bool)
 

@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._abi import MpcConfig, MpcCycleParams, MpcEvalOut, MpcObstacles, MpcPlanParams, MpcPool, MpcPoolParams, MPC_OK
+from ._abi import MpcClusterParams, MpcConfig, MpcCycleParams, MpcEvalOut, MpcObstacles, MpcPlanParams, MpcPool, MpcPoolParams, MPC_OK
 
 
 class MpcError(RuntimeError):
@@ -432,6 +432,46 @@ class BatchSolver:
         self._check(self._lib.mpc_costmap_to_obstacles(self._h, B, _addr(cost), sx, sy, float(resolution), _addr(org), _addr(pose), float(behind_robot_dist),
                                                        _addr(no), _addr(nv), _addr(vt), _addr(dr)))
         return no, nv, vt, dr
+
+    def cluster_params(self, resolution, cluster_max_distance=0.4, behind_robot_dist=1.5) -> MpcClusterParams:
+        """mpc_cluster_params with the library's rule (mpc_cluster_params_defaults): link_dist_sq = clamp(floor((cluster_max_distance / resolution)^2 + 1e-9), 1, 64)"""
+        p = MpcClusterParams()
+        self._lib.mpc_cluster_params_defaults(C.byref(p), float(resolution), float(cluster_max_distance))
+        p.behind_robot_dist = float(behind_robot_dist)
+        return p
+
+    def costmap_to_polygons(self, cost, resolution, origin, robot_pose, cluster_max_distance=0.4, behind_robot_dist=1.5):
+        """Lethal costmap cells -> one point, line or convex polygon per cluster of cells (mpc_costmap_to_polygons, include/mpc_costmap_clusters.h): the kept cells of
+        costmap_to_obstacles, clustered within cluster_max_distance, each cluster as its convex hull (its bounding box when the hull has more than cfg.max_vertices
+        vertices, its cells when the shape contains the robot).  Convex hulls overreach concave clusters: an L-shaped wall becomes a triangle.
+        cost: uint8 [B][size_y][size_x]; origin [B][2]; robot_pose [B][3].  Returns (n_obstacles (B,), n_vertices (B, O), vertices (B, O, V, 2), radius (B, O),
+        velocity (B, O, 2), dropped (B,), info (B, 4) = kept cells, clusters, hulls replaced by their box, clusters emitted as cells): the first five are `obstacles` of
+        solve() / step() / controller_step()."""
+        cost = np.ascontiguousarray(cost, dtype=np.uint8)
+        B, sy, sx = cost.shape
+        org = np.ascontiguousarray(origin, dtype=np.float64).reshape(B, 2)
+        pose = np.ascontiguousarray(robot_pose, dtype=np.float64).reshape(B, 3)
+        O, V = int(self.cfg.max_obstacles), max(1, int(self.cfg.max_vertices))
+        no, nv, vt = np.zeros(B, np.int32), np.zeros((B, O), np.int32), np.zeros((B, O, V, 2))
+        rd, vl, dr, info = np.zeros((B, O)), np.zeros((B, O, 2)), np.zeros(B, np.int32), np.zeros((B, 4), np.int32)
+        p = self.cluster_params(resolution, cluster_max_distance, behind_robot_dist)
+        self._check(self._lib.mpc_costmap_to_polygons(self._h, B, _addr(cost), sx, sy, float(resolution), _addr(org), _addr(pose), C.byref(p),
+                                                      *map(_addr, (no, nv, vt, rd, vl, dr, info))))
+        return no, nv, vt, rd, vl, dr, info
+
+    def costmap_to_polygons_device(self, B: int, cost: int, size_x: int, size_y: int, resolution: float, origin: int, robot_pose: int, params: MpcClusterParams,
+                                   n_obstacles: int, n_vertices: int, vertices: int, radius: Optional[int] = None, velocity: Optional[int] = None,
+                                   dropped: Optional[int] = None, info: Optional[int] = None) -> None:
+        """mpc_costmap_to_polygons_device: the same with device addresses (ints), asynchronous on the solver's stream, in the slot of the fleet cycle where
+        mpc_costmap_to_obstacles_device stands; slots at or above the new n_obstacles keep their bytes"""
+        self._check(self._lib.mpc_costmap_to_polygons_device(self._h, int(B), _dev(cost), int(size_x), int(size_y), float(resolution), _dev(origin), _dev(robot_pose),
+                                                             C.byref(params), *map(_dev, (n_obstacles, n_vertices, vertices, radius, velocity, dropped, info))))
+
+    def last_costmap_ms(self) -> float:
+        """device milliseconds of the most recent costmap step (mpc_last_costmap_ms), 0 when there has been none"""
+        ms = C.c_float(0.0)
+        self._check(self._lib.mpc_last_costmap_ms(self._h, C.byref(ms)))
+        return float(ms.value)
 
     def last_candidates(self, B: int):
         """(winner[B], iters_total[B]) of the most recent solve (mpc_last_candidates): index of the candidate initial trajectory that

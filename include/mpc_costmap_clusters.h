@@ -63,7 +63,7 @@ int mpc_costmap_to_polygons(mpc_solver* s, int32_t B, const uint8_t* cost, int32
                             const double* robot_pose, const mpc_cluster_params* params, int32_t* n_obstacles, int32_t* n_vertices, double* vertices,
                             double* radius, double* velocity, int32_t* dropped, int32_t* info);
 
-/* Milliseconds the device spent in the most recent costmap step of this handle (mpc_costmap_to_obstacles* or mpc_costmap_to_polygons*), between the two events that
+/* Milliseconds the device spent in the most recent costmap step of this handle (mpc_costmap_to_obstacles*, mpc_costmap_to_polygons* or mpc_costmap_to_lines* of include/mpc_costmap_lines.h), between the two events that
  * bracket its launch on the solver's stream; waits for that launch.  0 when there has been none.  (mpc_last_kernel_ms reports the solve launch alone.) */
 int mpc_last_costmap_ms(mpc_solver* s, float* ms);
 

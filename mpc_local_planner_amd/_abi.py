@@ -290,6 +290,28 @@ CLUSTER_PROTOTYPES = {
 }
 
 
+class MpcLineParams(C.Structure):
+    """struct mpc_line_params (include/mpc_costmap_lines.h); field-for-field."""
+    _fields_ = [
+        ("behind_robot_dist", C.c_double),
+        ("link_dist_sq", C.c_int32),
+        ("inlier_dist_sq", C.c_int32),
+        ("min_inliers", C.c_int32),
+        ("n_hypotheses", C.c_int32),
+        ("remaining_outliers", C.c_int32),
+    ]
+
+
+# ---- the functions of include/mpc_costmap_lines.h, in the same form.  tests/test_costmap_lines_abi.py holds every row to its declaration.
+# s, B, cost, size_x, size_y, resolution, origin, robot_pose, params, n_obstacles, n_vertices, vertices, radius, velocity, dropped, info
+_TO_LINES = (_rc, [_p, _i, _p, _i, _i, _d, _p, _p, C.POINTER(MpcLineParams)] + [_p] * 7)
+
+LINE_PROTOTYPES = {
+    "mpc_line_params_defaults": (None, [C.POINTER(MpcLineParams), _d, _d, _d]),                 # p, resolution, cluster_max_distance, ransac_inlier_distance
+    "mpc_costmap_to_lines": _TO_LINES, "mpc_costmap_to_lines_device": _TO_LINES,
+}
+
+
 def _diag_offdiag(w, dim):
     """a weight given as its diagonal or as a full dim x dim matrix -> (diagonal, off-diagonal terms (0,1)[, (0,2), (1,2)] of the symmetric part)"""
     rows = [list(r) if hasattr(r, "__len__") else None for r in w]

@@ -14,6 +14,7 @@
 #include "../../include/mpc_hip.h"
 #include "../../include/mpc_fleet.h"
 #include "../../include/mpc_costmap_clusters.h"
+#include "../../include/mpc_costmap_lines.h"
 #include "mpc_core.hpp"
 #include "mpc_problem.hpp"
 #include "mpc_launch_plan.hpp"
@@ -27,6 +28,7 @@
 #include "mpc_plan_inputs.hpp"
 #include "mpc_fleet_obstacles.hpp"
 #include "mpc_costmap_clusters.hpp"
+#include "mpc_costmap_lines.hpp"
 
 namespace {
 
@@ -99,7 +101,7 @@ struct mpc_solver {
     int ngrid_B, nvia_B;        // batch sizes the per-instance grid sizes / own via-point copies were set for (solves must not exceed them)
     hipEvent_t cev0, cev1;      // costmap kernel timing (kept apart from the solve kernel's events)
     bool ctimed;                // a costmap step has recorded them (mpc_last_costmap_ms)
-    int32_t* d_cluster_lab;     // scratch of mpc_costmap_to_polygons*: one label per cell and instance, allocated by the first such call, grows on demand
+    int32_t* d_cluster_lab;     // scratch of mpc_costmap_to_polygons* / mpc_costmap_to_lines*: one label (and for the lines one list word) per cell and instance, allocated by the first such call, grows on demand
     // candidate initial trajectories (n_candidates > 1): bookkeeping words, candidate records, per-instance winner / total iterations
     int *d_cwin, *d_cexited, *d_citsum;
     double* d_crec;
@@ -225,7 +227,7 @@ static void declare_buffers(mpc_solver* s) {
     s->bufs[BUF_CYC] = {(void**)&s->d_cyc, 0, 0, false, false};
     s->bufs[BUF_H_STAGE] = {(void**)&s->h_stage, 0, FILL_NONE, false, true};                    // the shared pair of staged_call: allocated by the first call that stages, grows on demand
     s->bufs[BUF_D_STAGE] = {(void**)&s->d_stage, 0, FILL_NONE, false, false};
-    s->bufs[BUF_CLUSTER_LAB] = {(void**)&s->d_cluster_lab, 0, FILL_NONE, false, false};         // allocated by the first mpc_costmap_to_polygons*, grows on demand
+    s->bufs[BUF_CLUSTER_LAB] = {(void**)&s->d_cluster_lab, 0, FILL_NONE, false, false};         // allocated by the first mpc_costmap_to_polygons* / mpc_costmap_to_lines*, grows on demand
     add(&s->h_out, cap.out_bytes, FILL_NONE, false, true);
     add(&s->d_in, cap.in_bytes);
     add(&s->d_out, cap.out_bytes);
@@ -1411,6 +1413,93 @@ int mpc_last_costmap_ms(mpc_solver* s, float* ms) {
     HIP_TRY(hipEventSynchronize(s->cev1));
     HIP_TRY(hipEventElapsedTime(ms, s->cev0, s->cev1));
     return MPC_OK;
+}
+
+}  // extern "C"
+
+// ---- costmap -> line segments (mpc_costmap_lines.hpp; declared in include/mpc_costmap_lines.h)
+
+// the argument checks both variants of mpc_costmap_to_lines share: NULL when the call is fine
+static const char* to_lines_error(const mpc_solver* s, const void* cost, int32_t size_x, int32_t size_y, double resolution, const void* origin, const void* robot_pose,
+                                  const mpc_line_params* p, const void* n_obstacles, const void* n_vertices, const void* vertices) {
+    if (!s || !cost || !origin || !robot_pose || !p || !n_obstacles || !n_vertices || !vertices)
+        return "mpc_costmap_to_lines: null argument (cost, origin, robot_pose, params, n_obstacles, n_vertices, vertices)";
+    if (s->cfg.max_obstacles <= 0) return "mpc_costmap_to_lines: the solver was created with max_obstacles = 0";
+    if (s->cfg.max_vertices < 4) return "mpc_costmap_to_lines: the solver was created with max_vertices < 4 (a bounding box has four)";
+    if (size_x < 1 || size_y < 1 || size_x > mpc::kClMaxSize || size_y > mpc::kClMaxSize || (long long)size_x * size_y > mpc::kCcMaxCells || !(resolution > 0))
+        return "mpc_costmap_to_lines: bad costmap geometry (size_x, size_y <= 4096, size_x * size_y <= 2^20)";
+    if (p->link_dist_sq < 1 || p->link_dist_sq > mpc::kCcMaxLink) return "mpc_costmap_to_lines: link_dist_sq has to be in [1, 64]";
+    if (p->inlier_dist_sq < 0 || p->inlier_dist_sq > mpc::kClMaxInlier) return "mpc_costmap_to_lines: inlier_dist_sq has to be in [0, 64]";
+    if (p->min_inliers < 2) return "mpc_costmap_to_lines: min_inliers has to be at least 2";
+    if (p->n_hypotheses < 1 || p->n_hypotheses > mpc::kClMaxHypotheses) return "mpc_costmap_to_lines: n_hypotheses has to be in [1, 65536]";
+    if (p->remaining_outliers < 0) return "mpc_costmap_to_lines: remaining_outliers has to be at least 0";
+    return nullptr;
+}
+
+extern "C" {
+
+void mpc_line_params_defaults(mpc_line_params* p, double resolution, double cluster_max_distance, double ransac_inlier_distance) {
+    if (!p) return;
+    mpc_cluster_params cp;
+    mpc_cluster_params_defaults(&cp, resolution, cluster_max_distance);
+    p->behind_robot_dist = cp.behind_robot_dist;
+    p->link_dist_sq = cp.link_dist_sq;
+    const double q = ransac_inlier_distance / resolution, sq = floor(q * q + 1e-9);
+    p->inlier_dist_sq = sq >= 64.0 ? 64 : sq >= 0.0 ? (int32_t)sq : 0;      // (not a number: 0)
+    p->min_inliers = 10;
+    p->n_hypotheses = 1500;
+    p->remaining_outliers = 3;
+}
+
+int mpc_costmap_to_lines_device(mpc_solver* s, int32_t B, const uint8_t* d_cost, int32_t size_x, int32_t size_y, double resolution, const double* d_origin,
+                                const double* d_robot_pose, const mpc_line_params* params, int32_t* d_n_obstacles, int32_t* d_n_vertices, double* d_vertices,
+                                double* d_radius, double* d_velocity, int32_t* d_dropped, int32_t* d_info) {
+    g_err[0] = 0;
+    if (const char* e = to_lines_error(s, d_cost, size_x, size_y, resolution, d_origin, d_robot_pose, params, d_n_obstacles, d_n_vertices, d_vertices)) { set_err(e); return MPC_EINVAL; }
+    if (B <= 0) return MPC_OK;
+    if (const int rc = refused(s, B, REF_MAX_BATCH, "mpc_costmap_to_lines")) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t words = (size_t)B * size_x * size_y, need = words * 8;      // the labels, then the list of a cluster that does not fit the kernel's LDS list
+    Buf& lab = s->bufs[BUF_CLUSTER_LAB];
+    if (need > lab.bytes) {      // a launch that still reads the old block may be in flight
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        const hipError_t e = buf_alloc(lab, need);
+        if (e != hipSuccess) { set_err("mpc_costmap_to_lines: scratch", e); return e == hipErrorOutOfMemory ? MPC_ENOMEM : MPC_EHIP; }
+    }
+    mpc::LineArgs a;
+    a.cost = d_cost; a.origin = d_origin; a.pose = d_robot_pose;
+    a.size_x = size_x; a.size_y = size_y; a.resolution = resolution;
+    a.prm = {params->behind_robot_dist, params->link_dist_sq, params->inlier_dist_sq, params->min_inliers, params->n_hypotheses, params->remaining_outliers};
+    a.O = s->cfg.max_obstacles; a.V = s->cfg.max_vertices;
+    a.lab = s->d_cluster_lab; a.list = reinterpret_cast<uint32_t*>(s->d_cluster_lab + words);
+    a.n_obstacles = d_n_obstacles; a.n_vertices = d_n_vertices; a.vertices = d_vertices; a.radius = d_radius; a.velocity = d_velocity;
+    a.dropped = d_dropped; a.info = d_info;
+    HIP_TRY(hipEventRecord(s->cev0, s->stream));
+    hipLaunchKernelGGL(mpc::costmap_lines_kernel, dim3(B), dim3(mpc::kCcThreads), 0, s->stream, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(s->cev1, s->stream));
+    s->ctimed = true;
+    return MPC_OK;
+}
+
+int mpc_costmap_to_lines(mpc_solver* s, int32_t B, const uint8_t* cost, int32_t size_x, int32_t size_y, double resolution, const double* origin,
+                         const double* robot_pose, const mpc_line_params* params, int32_t* n_obstacles, int32_t* n_vertices, double* vertices,
+                         double* radius, double* velocity, int32_t* dropped, int32_t* info) {
+    g_err[0] = 0;
+    if (const char* e = to_lines_error(s, cost, size_x, size_y, resolution, origin, robot_pose, params, n_obstacles, n_vertices, vertices)) { set_err(e); return MPC_EINVAL; }
+    if (B <= 0) return MPC_OK;
+    if (const int rc = refused(s, B, REF_MAX_BATCH, "mpc_costmap_to_lines")) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t nb = (size_t)B, O = s->cfg.max_obstacles, V = s->cfg.max_vertices;
+    const mpc::StagePiece pc[10] = {stage_in(cost, nb * size_x * size_y), stage_in(origin, nb * 16), stage_in(robot_pose, nb * 24), stage_out(n_obstacles, nb * 4),
+                                    stage_out(n_vertices, nb * O * 4), stage_out(vertices, nb * O * V * 16), stage_out(radius, nb * O * 8), stage_out(velocity, nb * O * 16),
+                                    stage_out(dropped, nb * 4), stage_out(info, nb * 16)};
+    return staged_call(s, "mpc_costmap_to_lines", true, true, pc, 10, [&](void** d) -> int {
+        // the kernel writes the slots it fills: the rest is cleared on the device, behind the copy of the inputs
+        for (int i = 4; i <= 7; ++i) if (d[i]) HIP_TRY(hipMemsetAsync(d[i], 0, pc[i].bytes, s->stream));
+        return mpc_costmap_to_lines_device(s, B, (const uint8_t*)d[0], size_x, size_y, resolution, (const double*)d[1], (const double*)d[2], params, (int32_t*)d[3],
+                                           (int32_t*)d[4], (double*)d[5], (double*)d[6], (double*)d[7], (int32_t*)d[8], (int32_t*)d[9]);
+    });
 }
 
 }  // extern "C"

@@ -113,7 +113,8 @@ MPC_CM_HD void cc_put_box(const CcMap& m, const CcContainer& c, int V, int O, in
 // ---- the statement (host).  lab: size_x * size_y words of scratch; info: 4 words or NULL; dropped: nullable.
 inline int cc_root(int32_t* lab, int x) { while (lab[x] != x) x = lab[x]; return x; }
 
-inline void cc_instance(const CcMap& m, const ClusterParams& prm, int V, int O, int32_t* lab, int32_t* n_obstacles, const CcContainer& c, int32_t* dropped, int32_t* info) {
+// rules 1 and 2: lab[p] becomes the key of the cluster of the kept cell at scan position p, -1 everywhere else; returns the number of kept cells
+inline int cc_label(const CcMap& m, const ClusterParams& prm, int32_t* lab) {
     const int H = m.H, ncol = m.W - 1, nrow = m.H - 1, L = prm.link_dist_sq, r = cc_isqrt(L);
     const size_t N = (size_t)m.W * m.H;
     for (size_t p = 0; p < N; ++p) lab[p] = -1;
@@ -134,64 +135,79 @@ inline void cc_instance(const CcMap& m, const ClusterParams& prm, int V, int O, 
                 }
         }
     for (int p = 0; p < ncol * H; ++p) if (lab[p] >= 0) lab[p] = cc_root(lab, p);
+    return kept;
+}
+
+// the cells of the cluster `key` in scan order
+inline void cc_cells_of(const CcMap& m, const int32_t* lab, int key, std::vector<int>& cells) {
+    cells.clear();
+    for (int p = key; p < (m.W - 1) * m.H; ++p) if (lab[p] == key) cells.push_back(p);
+}
+
+// rules 3 to 5 for one cluster: its cells (scan positions, in scan order) as one shape or, when that contains the robot (u, v), one point per cell, from slot `total`
+// on; total, boxes and as_cells are counted up
+inline void cc_emit_cluster(const CcMap& m, int V, int O, const std::vector<int>& cells, double u, double v, const CcContainer& c, long long& total, int& boxes, int& as_cells) {
+    const int H = m.H;
+    int imax = 0, jmin = m.H, jmax = 0;
+    for (size_t k = 0; k < cells.size(); ++k) {
+        const int i = cells[k] / H, j = cells[k] % H;
+        imax = i > imax ? i : imax; jmin = j < jmin ? j : jmin; jmax = j > jmax ? j : jmax;
+    }
+    const int first = cells.front(), last = cells.back(), imin = first / H;
+    bool box = false, inside = false;
+    std::vector<int> lower, upper, hull;      // scan positions
+    if (cells.size() == 1) hull.push_back(first);
+    else if (imax - imin + 1 > kCcMaxSpan) {
+        if (jmin == jmax) { hull.push_back(first); hull.push_back(last); }
+        else box = true;
+    } else {
+        // rule 3: Andrew's monotone chain; the cells are sorted as they come
+        auto chain = [&](std::vector<int>& st, int p) {
+            while (st.size() >= 2 && cc_cross(st[st.size() - 2] / H, st[st.size() - 2] % H, st.back() / H, st.back() % H, p / H, p % H) <= 0) st.pop_back();
+            st.push_back(p);
+        };
+        for (size_t k = 0; k < cells.size(); ++k) chain(lower, cells[k]);
+        for (size_t k = cells.size(); k-- > 0;) chain(upper, cells[k]);
+        hull.assign(lower.begin(), lower.end() - 1);
+        hull.insert(hull.end(), upper.begin(), upper.end() - 1);
+        if ((int)hull.size() > V) box = true;
+    }
+    if (box) { ++boxes; inside = cc_in_box(imin, imax, jmin, jmax, u, v); }
+    else if (hull.size() >= 3) {
+        inside = true;
+        for (size_t k = 0; k < hull.size(); ++k) {
+            const int o = hull[k], a = hull[(k + 1) % hull.size()];
+            inside = inside && cc_left_of(o / H, o % H, a / H, a % H, u, v);
+        }
+    }
+    if (inside) {      // rule 4
+        ++as_cells;
+        for (size_t k = 0; k < cells.size(); ++k, ++total)
+            if (total < O) cc_put_point(m, c, V, O, (int)total, cells[k] / H, cells[k] % H);
+        return;
+    }
+    if (total < O) {
+        const int slot = (int)total;
+        if (box) cc_put_box(m, c, V, O, slot, imin, imax, jmin, jmax);
+        else {
+            for (size_t k = 0; k < hull.size(); ++k) cc_put_vertex(m, c, V, slot, (int)k, hull[k] / H, hull[k] % H);
+            cc_close_slot(c, slot, (int)hull.size());
+        }
+    }
+    ++total;
+}
+
+inline void cc_instance(const CcMap& m, const ClusterParams& prm, int V, int O, int32_t* lab, int32_t* n_obstacles, const CcContainer& c, int32_t* dropped, int32_t* info) {
+    const int kept = cc_label(m, prm, lab);
     const double u = cc_index_of(m.px, m.ox0, m.res), v = cc_index_of(m.py, m.oy0, m.res);
     long long total = 0;
     int clusters = 0, boxes = 0, as_cells = 0;
-    std::vector<int> cells, lower, upper, hull;      // scan positions
-    for (int key = 0; key < ncol * H; ++key) {
+    std::vector<int> cells;
+    for (int key = 0; key < (m.W - 1) * m.H; ++key) {
         if (lab[key] != key) continue;
         ++clusters;
-        cells.clear();
-        int imax = 0, jmin = nrow, jmax = 0;
-        for (int p = key; p < ncol * H; ++p)
-            if (lab[p] == key) {
-                cells.push_back(p);
-                const int i = p / H, j = p % H;
-                imax = i > imax ? i : imax; jmin = j < jmin ? j : jmin; jmax = j > jmax ? j : jmax;
-            }
-        const int imin = key / H, first = cells.front(), last = cells.back();
-        bool box = false, inside = false;
-        hull.clear();
-        if (cells.size() == 1) hull.push_back(first);
-        else if (imax - imin + 1 > kCcMaxSpan) {
-            if (jmin == jmax) { hull.push_back(first); hull.push_back(last); }
-            else box = true;
-        } else {
-            // rule 3: Andrew's monotone chain; the cells are sorted as they come
-            auto chain = [&](std::vector<int>& st, int p) {
-                while (st.size() >= 2 && cc_cross(st[st.size() - 2] / H, st[st.size() - 2] % H, st.back() / H, st.back() % H, p / H, p % H) <= 0) st.pop_back();
-                st.push_back(p);
-            };
-            lower.clear(); upper.clear();
-            for (size_t k = 0; k < cells.size(); ++k) chain(lower, cells[k]);
-            for (size_t k = cells.size(); k-- > 0;) chain(upper, cells[k]);
-            hull.assign(lower.begin(), lower.end() - 1);
-            hull.insert(hull.end(), upper.begin(), upper.end() - 1);
-            if ((int)hull.size() > V) box = true;
-        }
-        if (box) { ++boxes; inside = cc_in_box(imin, imax, jmin, jmax, u, v); }
-        else if (hull.size() >= 3) {
-            inside = true;
-            for (size_t k = 0; k < hull.size(); ++k) {
-                const int o = hull[k], a = hull[(k + 1) % hull.size()];
-                inside = inside && cc_left_of(o / H, o % H, a / H, a % H, u, v);
-            }
-        }
-        if (inside) {      // rule 4
-            ++as_cells;
-            for (size_t k = 0; k < cells.size(); ++k, ++total)
-                if (total < O) cc_put_point(m, c, V, O, (int)total, cells[k] / H, cells[k] % H);
-            continue;
-        }
-        if (total < O) {
-            const int slot = (int)total;
-            if (box) cc_put_box(m, c, V, O, slot, imin, imax, jmin, jmax);
-            else {
-                for (size_t k = 0; k < hull.size(); ++k) cc_put_vertex(m, c, V, slot, (int)k, hull[k] / H, hull[k] % H);
-                cc_close_slot(c, slot, (int)hull.size());
-            }
-        }
-        ++total;
+        cc_cells_of(m, lab, key, cells);
+        cc_emit_cluster(m, V, O, cells, u, v, c, total, boxes, as_cells);
     }
     *n_obstacles = total < O ? (int)total : O;
     if (dropped) *dropped = (int)(total - *n_obstacles);
@@ -300,45 +316,21 @@ constexpr int kCcBitmapCells = 2 * kCcMaxSpan * 32;
 
 constexpr int kCcKindPoint = 0, kCcKindHull = 1, kCcKindBox = 2, kCcKindCells = 3, kCcKindLine = 4;
 
-// One workgroup (256 threads) per instance.  The labels live at their scan position, lab[i * size_y + j], so that a sweep in thread order is a sweep in scan order.
+// The first three steps of a workgroup (256 threads) on its instance, shared by costmap_clusters_kernel and costmap_lines_kernel (mpc_costmap_lines.hpp).  The labels
+// live at their scan position, lab[i * size_y + j], so that a sweep in thread order is a sweep in scan order.
 //   keep   : 16-byte pieces of the costmap rows (cm_load, cm_lethal_mask, cm_keep), the lanes along j: a kept cell gets its own scan position, every other word is -1
 //            (and, on maps of up to kCcBitmapCells cells, its bit in an LDS bitmap and an entry in an LDS list, which the next step reads);
 //   link   : every kept cell is united with the kept cells before it in scan order within link_dist_sq (in its own column the nearest one is enough) by cc_union,
 //            then every label is replaced by its root: the fixed point -- the component's smallest scan position -- is unique, and nothing counts passes;
-//   rank   : an ordered count of the roots gives every cluster its rank in key order; the labels become -2 - rank;
-//   shape  : the clusters in chunks of 256 in rank order, thread k on cluster r0 + k.  Count, first cell and bounding box by integer LDS atomics (order-independent);
-//            then runs of clusters whose column spans fit kCcMaxSpan words together: column extremes by LDS atomicMin / atomicMax, cc_wrap per thread once for the
-//            vertex count and the robot test, an ordered prefix of the obstacles every cluster emits gives the slots, cc_wrap again writes the vertices;
-//   cells  : a cluster that contains the robot is swept in scan order by the whole workgroup, its cells numbered by ballot.
-__global__ __launch_bounds__(kCcThreads) void costmap_clusters_kernel(ClusterArgs a) {
-    __shared__ int s_cnt[kCcThreads], s_first[kCcThreads], s_imax[kCcThreads], s_jmin[kCcThreads], s_jmax[kCcThreads];
-    __shared__ int s_inc[kCcThreads], s_kind[kCcThreads];
-    int* const s_slot = s_cnt;       // a chunk's counts are in registers once its runs begin (40 KB of LDS: four workgroups per compute unit)
-    int* const s_part = s_kind;      // the scans' workspace: a scan is over before the kinds of its run are written, and those are read before the next scan
-    __shared__ int s_ext[2 * kCcMaxSpan];
-    int* const s_lo = s_ext;
-    int* const s_hi = s_ext + kCcMaxSpan;
+//   rank   : an ordered count of the roots gives every cluster its rank in key order; the labels become -2 - rank.
+// s_ext: 2 * kCcMaxSpan words of LDS, free again on return; s_ws: 8 words; s_nlist: one word.  Every thread calls it; it ends behind a barrier.
+__device__ __forceinline__ void cc_label_device(const CcMap& m, double behind_dist, int L, int32_t* lab, int* s_ext, int* s_ws, int* s_nlist_p, int& kept, int& nclusters) {
     unsigned* const s_bits = reinterpret_cast<unsigned*>(s_ext);
-    __shared__ int s_ws[8];
-    __shared__ int s_tot[2];
-    __shared__ int s_nlist;
-    const int b = blockIdx.x, t = threadIdx.x;
-    const int W = a.size_x, H = a.size_y, ncol = W - 1, nrow = H - 1, O = a.O, V = a.V;
+    int& s_nlist = *s_nlist_p;
+    const int t = threadIdx.x;
+    const int W = m.W, H = m.H, ncol = W - 1, nrow = H - 1;
     const int ncell = W * H, nscan = ncol > 0 && nrow > 0 ? ncol * H : 0;      // the sweeps' range: the scan positions of the visited columns
-    int32_t* lab = a.lab + (size_t)b * ncell;
-    CcMap m;
-    m.cost = a.cost + (size_t)b * ncell; m.W = W; m.H = H; m.res = a.resolution;
-    m.ox0 = a.origin[2 * b]; m.oy0 = a.origin[2 * b + 1];
-    m.px = a.pose[3 * b]; m.py = a.pose[3 * b + 1];
-    const double th = a.pose[3 * b + 2];
-    m.hx = cos(th); m.hy = sin(th);
-    CcContainer c;
-    c.n_vertices = a.n_vertices + (size_t)b * O;
-    c.vertices = a.vertices + (size_t)b * O * V * 2;
-    c.radius = a.radius ? a.radius + (size_t)b * O : nullptr;
-    c.velocity = a.velocity ? a.velocity + (size_t)b * O * 2 : nullptr;
-    const double u = cc_index_of(m.px, m.ox0, m.res), v = cc_index_of(m.py, m.oy0, m.res);
-    const int L = a.prm.link_dist_sq, r = cc_isqrt(L);
+    const int r = cc_isqrt(L);
 
     // ---- keep
     const bool bitmap = ncell <= kCcBitmapCells;
@@ -347,7 +339,6 @@ __global__ __launch_bounds__(kCcThreads) void costmap_clusters_kernel(ClusterArg
     const int cap = bitmap ? 2 * kCcMaxSpan - nwords : 0;
     for (int p = t; p < ncell; p += kCcThreads) cc_st(lab + p, -1);
     for (int e = t; e < nwords; e += kCcThreads) s_bits[e] = 0u;
-    if (t < 2) s_tot[t] = 0;
     if (t == 0) s_nlist = 0;
     __syncthreads();
     if (nscan > 0) {
@@ -361,7 +352,7 @@ __global__ __launch_bounds__(kCcThreads) void costmap_clusters_kernel(ClusterArg
             const double wy = cm_world(m.oy0, j, m.res);
             for (uint32_t msk = cm_lethal_mask(pc); msk; msk &= msk - 1) {
                 const int i = i0 + __builtin_ctz(msk);
-                if (!cm_keep(cm_world(m.ox0, i, m.res), wy, m.px, m.py, m.hx, m.hy, a.prm.behind_dist)) continue;
+                if (!cm_keep(cm_world(m.ox0, i, m.res), wy, m.px, m.py, m.hx, m.hy, behind_dist)) continue;
                 const int p = i * H + j;
                 cc_st(lab + p, p);
                 if (bitmap) {
@@ -415,7 +406,7 @@ __global__ __launch_bounds__(kCcThreads) void costmap_clusters_kernel(ClusterArg
     else for (int p = t; p < nscan; p += kCcThreads) if (cc_ld(lab + p) >= 0) cc_st(lab + p, cc_find(lab, p));
     __syncthreads();
     // ---- rank
-    int kept = 0, nclusters = 0;
+    kept = 0; nclusters = 0;
     for (int p0 = 0; p0 < nscan; p0 += kCcThreads) {
         const int p = p0 + t;
         const int l = p < nscan ? cc_ld(lab + p) : -1;
@@ -429,6 +420,43 @@ __global__ __launch_bounds__(kCcThreads) void costmap_clusters_kernel(ClusterArg
     if (listed) for (int e = t; e < nlist; e += kCcThreads) { const int p = s_list[e], l = cc_ld(lab + p); if (l >= 0) cc_st(lab + p, cc_ld(lab + l)); }
     else for (int p = t; p < nscan; p += kCcThreads) { const int l = cc_ld(lab + p); if (l >= 0) cc_st(lab + p, cc_ld(lab + l)); }
     __syncthreads();
+}
+
+// One workgroup (256 threads) per instance: keep, link and rank by cc_label_device, then
+//   shape  : the clusters in chunks of 256 in rank order, thread k on cluster r0 + k.  Count, first cell and bounding box by integer LDS atomics (order-independent);
+//            then runs of clusters whose column spans fit kCcMaxSpan words together: column extremes by LDS atomicMin / atomicMax, cc_wrap per thread once for the
+//            vertex count and the robot test, an ordered prefix of the obstacles every cluster emits gives the slots, cc_wrap again writes the vertices;
+//   cells  : a cluster that contains the robot is swept in scan order by the whole workgroup, its cells numbered by ballot.
+__global__ __launch_bounds__(kCcThreads) void costmap_clusters_kernel(ClusterArgs a) {
+    __shared__ int s_cnt[kCcThreads], s_first[kCcThreads], s_imax[kCcThreads], s_jmin[kCcThreads], s_jmax[kCcThreads];
+    __shared__ int s_inc[kCcThreads], s_kind[kCcThreads];
+    int* const s_slot = s_cnt;       // a chunk's counts are in registers once its runs begin (40 KB of LDS: four workgroups per compute unit)
+    int* const s_part = s_kind;      // the scans' workspace: a scan is over before the kinds of its run are written, and those are read before the next scan
+    __shared__ int s_ext[2 * kCcMaxSpan];
+    int* const s_lo = s_ext;
+    int* const s_hi = s_ext + kCcMaxSpan;
+    __shared__ int s_ws[8];
+    __shared__ int s_tot[2];
+    __shared__ int s_nlist;
+    const int b = blockIdx.x, t = threadIdx.x;
+    const int W = a.size_x, H = a.size_y, ncol = W - 1, nrow = H - 1, O = a.O, V = a.V;
+    const int ncell = W * H, nscan = ncol > 0 && nrow > 0 ? ncol * H : 0;      // the sweeps' range: the scan positions of the visited columns
+    int32_t* lab = a.lab + (size_t)b * ncell;
+    CcMap m;
+    m.cost = a.cost + (size_t)b * ncell; m.W = W; m.H = H; m.res = a.resolution;
+    m.ox0 = a.origin[2 * b]; m.oy0 = a.origin[2 * b + 1];
+    m.px = a.pose[3 * b]; m.py = a.pose[3 * b + 1];
+    const double th = a.pose[3 * b + 2];
+    m.hx = cos(th); m.hy = sin(th);
+    CcContainer c;
+    c.n_vertices = a.n_vertices + (size_t)b * O;
+    c.vertices = a.vertices + (size_t)b * O * V * 2;
+    c.radius = a.radius ? a.radius + (size_t)b * O : nullptr;
+    c.velocity = a.velocity ? a.velocity + (size_t)b * O * 2 : nullptr;
+    const double u = cc_index_of(m.px, m.ox0, m.res), v = cc_index_of(m.py, m.oy0, m.res);
+    if (t < 2) s_tot[t] = 0;
+    int kept, nclusters;
+    cc_label_device(m, a.prm.behind_dist, a.prm.link_dist_sq, lab, s_ext, s_ws, &s_nlist, kept, nclusters);
     // ---- shape
     int total = 0;      // obstacles emitted so far (workgroup-uniform)
     for (int r0 = 0; r0 < nclusters; r0 += kCcThreads) {

@@ -438,6 +438,59 @@ def cluster_params_from_options(plugin_options: dict, converter_params: dict | N
     return c, notes
 
 
+LINE_PLUGIN = "costmap_converter::CostmapToLinesDBSRANSAC"
+
+
+def line_params_from_options(plugin_options: dict, converter_params: dict | None, resolution: float):
+    """struct mpc_line_params (mpc_costmap_to_lines*, BatchSolver.costmap_to_lines_device) from what plugin_options_from_params returns and the plugin namespace's
+    parameter tree, which holds the converter's block: `costmap_converter/CostmapToLinesDBSRANSAC` (as ONE key, the way the shipped yaml writes it, or nested), or the
+    block of the plugin that costmap_converter_plugin names.  Read: cluster_max_distance (0.4), cluster_min_pts (2), ransac_inlier_distance (0.15), ransac_min_inliers
+    (10), ransac_no_iterations (1500) and ransac_remainig_outliers (3; the reference's spelling), the shipped costmap_converter_params.yaml's values; link_dist_sq and
+    inlier_dist_sq as mpc_line_params_defaults has them.
+    Returns (params, notes).  A note, not an error, says where the library does something else than the configured plugin would: the line rule is the library's own
+    (include/mpc_costmap_lines.h), leftover cells are always emitted as points, none is filtered, hull vertices are never thinned, small clusters are kept."""
+    tree = converter_params or {}
+    plugin = str(plugin_options.get("costmap_converter_plugin", "") or "")
+    notes: list[str] = []
+
+    def block(name):
+        key = name.replace("::", "/")
+        if isinstance(tree.get(key), dict):
+            return tree[key]
+        node = tree
+        for part in key.split("/"):
+            node = node.get(part) if isinstance(node, dict) else None
+        return node if isinstance(node, dict) else None
+
+    b = (block(plugin) if plugin else None) or block(LINE_PLUGIN) or {}
+    r = _Reader(b)
+    d, min_pts, inlier = r.get("cluster_max_distance", 0.4), r.get("cluster_min_pts", 2), r.get("ransac_inlier_distance", 0.15)
+    if plugin and plugin != LINE_PLUGIN:
+        notes.append(f"costmap_converter_plugin {plugin}: mpc_costmap_to_lines is the library's own line rule, modelled on {LINE_PLUGIN}")
+    if min_pts > 2:
+        notes.append(f"cluster_min_pts {min_pts}: clusters of fewer cells are kept (every cell with a neighbour is a core point)")
+    if not r.get("ransac_convert_outlier_pts", True):
+        notes.append("ransac_convert_outlier_pts False: the cells that no line takes are always emitted as points, nothing that was kept is left unrepresented")
+    if r.get("ransac_filter_remaining_outlier_pts", False):
+        notes.append("ransac_filter_remaining_outlier_pts True: the leftover points are not filtered")
+    sep = r.get("convex_hull_min_pt_separation", 0.1)
+    if sep != 0.1:
+        notes.append(f"convex_hull_min_pt_separation {sep}: not read; the hull vertices of a small cluster are never thinned")
+    c = A.MpcLineParams()
+    c.behind_robot_dist = float(plugin_options.get("costmap_obstacles_behind_robot_dist", 1.5))
+
+    def cells_sq(dist, lo):
+        q = dist / float(resolution) if resolution else float("nan")
+        sq = math.floor(q * q + 1e-9) if math.isfinite(q) else lo
+        return int(min(max(sq, lo), 64))
+
+    c.link_dist_sq, c.inlier_dist_sq = cells_sq(d, 1), cells_sq(inlier, 0)
+    c.min_inliers = int(r.get("ransac_min_inliers", 10))
+    c.n_hypotheses = int(r.get("ransac_no_iterations", 1500))
+    c.remaining_outliers = int(r.get("ransac_remainig_outliers", 3))
+    return c, notes
+
+
 def _is_number(v) -> bool:
     return isinstance(v, (int, float)) and not isinstance(v, bool)
 

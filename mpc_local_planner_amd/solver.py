@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._abi import MpcClusterParams, MpcConfig, MpcCycleParams, MpcEvalOut, MpcObstacles, MpcPlanParams, MpcPool, MpcPoolParams, MPC_OK
+from ._abi import MpcClusterParams, MpcConfig, MpcLineParams, MpcCycleParams, MpcEvalOut, MpcObstacles, MpcPlanParams, MpcPool, MpcPoolParams, MPC_OK
 
 
 class MpcError(RuntimeError):
@@ -466,6 +466,43 @@ class BatchSolver:
         mpc_costmap_to_obstacles_device stands; slots at or above the new n_obstacles keep their bytes"""
         self._check(self._lib.mpc_costmap_to_polygons_device(self._h, int(B), _dev(cost), int(size_x), int(size_y), float(resolution), _dev(origin), _dev(robot_pose),
                                                              C.byref(params), *map(_dev, (n_obstacles, n_vertices, vertices, radius, velocity, dropped, info))))
+
+    def line_params(self, resolution, cluster_max_distance=0.4, ransac_inlier_distance=0.15, behind_robot_dist=1.5, min_inliers=10, n_hypotheses=1500,
+                    remaining_outliers=3) -> MpcLineParams:
+        """mpc_line_params with the library's rules (mpc_line_params_defaults): link_dist_sq as cluster_params has it, inlier_dist_sq =
+        clamp(floor((ransac_inlier_distance / resolution)^2 + 1e-9), 0, 64); the other fields as given (the shipped block's 10, 1500, 3)"""
+        p = MpcLineParams()
+        self._lib.mpc_line_params_defaults(C.byref(p), float(resolution), float(cluster_max_distance), float(ransac_inlier_distance))
+        p.behind_robot_dist = float(behind_robot_dist)
+        p.min_inliers, p.n_hypotheses, p.remaining_outliers = int(min_inliers), int(n_hypotheses), int(remaining_outliers)
+        return p
+
+    def costmap_to_lines(self, cost, resolution, origin, robot_pose, params: Optional[MpcLineParams] = None):
+        """Lethal costmap cells -> line segments along the walls (mpc_costmap_to_lines, include/mpc_costmap_lines.h): the clusters of costmap_to_polygons; a cluster of
+        at least min_inliers cells is cut into lines by a deterministic consensus rule in integers (an L-shaped wall becomes two segments and the free corner stays
+        free), what is left of it comes out as points; smaller clusters come out as costmap_to_polygons emits them.  params: line_params(resolution) by default.
+        cost: uint8 [B][size_y][size_x]; origin [B][2]; robot_pose [B][3].  Returns (n_obstacles (B,), n_vertices (B, O), vertices (B, O, V, 2), radius (B, O),
+        velocity (B, O, 2), dropped (B,), info (B, 4) = kept cells, clusters, lines, cells emitted as points by the line rule): the first five are `obstacles` of
+        solve() / step() / controller_step()."""
+        cost = np.ascontiguousarray(cost, dtype=np.uint8)
+        B, sy, sx = cost.shape
+        org = np.ascontiguousarray(origin, dtype=np.float64).reshape(B, 2)
+        pose = np.ascontiguousarray(robot_pose, dtype=np.float64).reshape(B, 3)
+        O, V = int(self.cfg.max_obstacles), max(1, int(self.cfg.max_vertices))
+        no, nv, vt = np.zeros(B, np.int32), np.zeros((B, O), np.int32), np.zeros((B, O, V, 2))
+        rd, vl, dr, info = np.zeros((B, O)), np.zeros((B, O, 2)), np.zeros(B, np.int32), np.zeros((B, 4), np.int32)
+        p = params if params is not None else self.line_params(resolution)
+        self._check(self._lib.mpc_costmap_to_lines(self._h, B, _addr(cost), sx, sy, float(resolution), _addr(org), _addr(pose), C.byref(p),
+                                                   *map(_addr, (no, nv, vt, rd, vl, dr, info))))
+        return no, nv, vt, rd, vl, dr, info
+
+    def costmap_to_lines_device(self, B: int, cost: int, size_x: int, size_y: int, resolution: float, origin: int, robot_pose: int, params: MpcLineParams,
+                                n_obstacles: int, n_vertices: int, vertices: int, radius: Optional[int] = None, velocity: Optional[int] = None,
+                                dropped: Optional[int] = None, info: Optional[int] = None) -> None:
+        """mpc_costmap_to_lines_device: the same with device addresses (ints), asynchronous on the solver's stream, in the slot of the fleet cycle where
+        mpc_costmap_to_obstacles_device and mpc_costmap_to_polygons_device stand; slots at or above the new n_obstacles keep their bytes"""
+        self._check(self._lib.mpc_costmap_to_lines_device(self._h, int(B), _dev(cost), int(size_x), int(size_y), float(resolution), _dev(origin), _dev(robot_pose),
+                                                          C.byref(params), *map(_dev, (n_obstacles, n_vertices, vertices, radius, velocity, dropped, info))))
 
     def last_costmap_ms(self) -> float:
         """device milliseconds of the most recent costmap step (mpc_last_costmap_ms), 0 when there has been none"""

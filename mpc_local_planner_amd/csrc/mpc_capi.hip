@@ -495,6 +495,17 @@ static mpc::StagePiece stage_in(const void* p, size_t bytes) { return {p, nullpt
 static mpc::StagePiece stage_out(void* p, size_t bytes) { return {nullptr, p, bytes, mpc::STAGE_OUT}; }
 static mpc::StagePiece stage_inout(void* p, size_t bytes) { return {p, p, bytes, mpc::STAGE_INOUT}; }
 
+// a costmap step's launch, one workgroup per instance, between the two events mpc_last_costmap_ms reads
+template <typename Kernel, typename Args>
+static int costmap_timed_launch(mpc_solver* s, Kernel kernel, int32_t B, int threads, const Args& a) {
+    HIP_TRY(hipEventRecord(s->cev0, s->stream));
+    hipLaunchKernelGGL(kernel, dim3(B), dim3(threads), 0, s->stream, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(s->cev1, s->stream));
+    s->ctimed = true;
+    return MPC_OK;
+}
+
 // mpc_solve_batch_device with the per-instance start mode of the controller cycle (d_init_mode: NULL everywhere else)
 static int solve_device(mpc_solver* s, int32_t B, const double* d_x0, const double* d_xf, const double* d_u_prev,
                         const double* d_dt_prev, const double* d_x_init, const double* d_u_init, const double* d_dt_init,
@@ -644,12 +655,7 @@ int mpc_costmap_to_obstacles_device(mpc_solver* s, int32_t B, const uint8_t* d_c
     a.size_x = size_x; a.size_y = size_y; a.resolution = resolution; a.behind_dist = behind_robot_dist;
     a.O = s->cfg.max_obstacles; a.V = s->cfg.max_vertices > 0 ? s->cfg.max_vertices : 1;
     a.n_obstacles = d_n_obstacles; a.n_vertices = d_n_vertices; a.vertices = d_vertices; a.dropped = d_dropped;
-    HIP_TRY(hipEventRecord(s->cev0, s->stream));
-    hipLaunchKernelGGL(mpc::costmap_to_obstacles_kernel, dim3(B), dim3(mpc::kCostmapThreads), 0, s->stream, a);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(s->cev1, s->stream));
-    s->ctimed = true;
-    return MPC_OK;
+    return costmap_timed_launch(s, mpc::costmap_to_obstacles_kernel, B, mpc::kCostmapThreads, a);
 }
 
 int mpc_costmap_to_obstacles(mpc_solver* s, int32_t B, const uint8_t* cost, int32_t size_x, int32_t size_y, double resolution,
@@ -1333,18 +1339,77 @@ int mpc_fleet_pool(mpc_solver* s, int32_t B, const double* robot_pose, const dou
 
 }  // extern "C"
 
-// ---- costmap -> clustered obstacles (mpc_costmap_clusters.hpp; declared in include/mpc_costmap_clusters.h)
+// ---- costmap -> clustered obstacles and costmap -> line segments (mpc_costmap_clusters.hpp, mpc_costmap_lines.hpp; declared in include/mpc_costmap_clusters.h and
+// include/mpc_costmap_lines.h): two steps with one entry path
 
-// the argument checks both variants of mpc_costmap_to_polygons share: NULL when the call is fine
-static const char* to_polygons_error(const mpc_solver* s, const void* cost, int32_t size_x, int32_t size_y, double resolution, const void* origin, const void* robot_pose,
-                                     const mpc_cluster_params* p, const void* n_obstacles, const void* n_vertices, const void* vertices) {
-    if (!s || !cost || !origin || !robot_pose || !p || !n_obstacles || !n_vertices || !vertices)
-        return "mpc_costmap_to_polygons: null argument (cost, origin, robot_pose, params, n_obstacles, n_vertices, vertices)";
-    if (s->cfg.max_obstacles <= 0) return "mpc_costmap_to_polygons: the solver was created with max_obstacles = 0";
-    if (s->cfg.max_vertices < 4) return "mpc_costmap_to_polygons: the solver was created with max_vertices < 4 (a bounding box has four)";
-    if (size_x < 1 || size_y < 1 || (long long)size_x * size_y > mpc::kCcMaxCells || !(resolution > 0)) return "mpc_costmap_to_polygons: bad costmap geometry (size_x * size_y <= 2^20)";
-    if (p->link_dist_sq < 1 || p->link_dist_sq > mpc::kCcMaxLink) return "mpc_costmap_to_polygons: link_dist_sq has to be in [1, 64]";
-    return nullptr;
+static bool costmap_no(const char* who, const char* why) {
+    if (why) snprintf(g_err, sizeof(g_err), "%s: %s", who, why);
+    return why != nullptr;
+}
+
+// the argument checks both steps and both variants of each share, in the order in which they win: true with mpc_last_error set when the call is refused.
+// max_side: the per-axis limit of the line step
+static bool costmap_shapes_error(const char* who, const mpc_solver* s, const void* cost, int32_t size_x, int32_t size_y, double resolution, const void* origin, const void* robot_pose,
+                                 const void* params, const void* n_obstacles, const void* n_vertices, const void* vertices, int32_t max_side, int32_t link_dist_sq) {
+    if (!s || !cost || !origin || !robot_pose || !params || !n_obstacles || !n_vertices || !vertices)
+        return costmap_no(who, "null argument (cost, origin, robot_pose, params, n_obstacles, n_vertices, vertices)");
+    if (s->cfg.max_obstacles <= 0) return costmap_no(who, "the solver was created with max_obstacles = 0");
+    if (s->cfg.max_vertices < 4) return costmap_no(who, "the solver was created with max_vertices < 4 (a bounding box has four)");
+    if (size_x < 1 || size_y < 1 || size_x > max_side || size_y > max_side || (long long)size_x * size_y > mpc::kCcMaxCells || !(resolution > 0))
+        return costmap_no(who, max_side < mpc::kCcMaxCells ? "bad costmap geometry (size_x, size_y <= 4096, size_x * size_y <= 2^20)" : "bad costmap geometry (size_x * size_y <= 2^20)");
+    return costmap_no(who, link_dist_sq < 1 || link_dist_sq > mpc::kCcMaxLink ? "link_dist_sq has to be in [1, 64]" : nullptr);
+}
+static bool to_polygons_error(const mpc_solver* s, const void* cost, int32_t size_x, int32_t size_y, double resolution, const void* origin, const void* robot_pose,
+                              const mpc_cluster_params* p, const void* n_obstacles, const void* n_vertices, const void* vertices) {
+    return costmap_shapes_error("mpc_costmap_to_polygons", s, cost, size_x, size_y, resolution, origin, robot_pose, p, n_obstacles, n_vertices, vertices, mpc::kCcMaxCells, p ? p->link_dist_sq : 0);
+}
+static bool to_lines_error(const mpc_solver* s, const void* cost, int32_t size_x, int32_t size_y, double resolution, const void* origin, const void* robot_pose,
+                           const mpc_line_params* p, const void* n_obstacles, const void* n_vertices, const void* vertices) {
+    const char* who = "mpc_costmap_to_lines";
+    if (costmap_shapes_error(who, s, cost, size_x, size_y, resolution, origin, robot_pose, p, n_obstacles, n_vertices, vertices, mpc::kClMaxSize, p ? p->link_dist_sq : 0)) return true;
+    if (p->inlier_dist_sq < 0 || p->inlier_dist_sq > mpc::kClMaxInlier) return costmap_no(who, "inlier_dist_sq has to be in [0, 64]");
+    if (p->min_inliers < 2) return costmap_no(who, "min_inliers has to be at least 2");
+    if (p->n_hypotheses < 1 || p->n_hypotheses > mpc::kClMaxHypotheses) return costmap_no(who, "n_hypotheses has to be in [1, 65536]");
+    return costmap_no(who, p->remaining_outliers < 0 ? "remaining_outliers has to be at least 0" : nullptr);
+}
+
+// What a checked device call of either step does before its launch: the batch refusal, the scratch (BUF_CLUSTER_LAB) grown to bytes_per_cell per cell of the batch
+// -- 4: the labels; 8: behind them the list of a cluster that does not fit the line kernel's LDS list --, and the launch's description of the batch.
+static int costmap_shapes_batch(mpc_solver* s, const char* who, int32_t B, size_t bytes_per_cell, const uint8_t* d_cost, int32_t size_x, int32_t size_y, double resolution,
+                                const double* d_origin, const double* d_robot_pose, int32_t* d_n_obstacles, int32_t* d_n_vertices, double* d_vertices, double* d_radius,
+                                double* d_velocity, int32_t* d_dropped, int32_t* d_info, mpc::CcBatch& a) {
+    if (const int rc = refused(s, B, REF_MAX_BATCH, who)) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t need = (size_t)B * size_x * size_y * bytes_per_cell;
+    Buf& lab = s->bufs[BUF_CLUSTER_LAB];
+    if (need > lab.bytes) {      // a launch that still reads the old block may be in flight
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        const hipError_t e = buf_alloc(lab, need);
+        if (e != hipSuccess) { snprintf(g_err, sizeof(g_err), "%s: scratch: %s", who, hipGetErrorString(e)); return e == hipErrorOutOfMemory ? MPC_ENOMEM : MPC_EHIP; }
+    }
+    a = {d_cost, d_origin, d_robot_pose, size_x, size_y, resolution, s->cfg.max_obstacles, s->cfg.max_vertices, s->d_cluster_lab,
+         d_n_obstacles, d_n_vertices, d_vertices, d_radius, d_velocity, d_dropped, d_info};
+    return MPC_OK;
+}
+
+// The host-pointer variant of either step: the pieces through the staging pair, the container's arrays cleared on the device, device_entry on the device addresses.
+template <typename Params, typename Entry>
+static int costmap_shapes_host(mpc_solver* s, const char* who, int32_t B, const uint8_t* cost, int32_t size_x, int32_t size_y, double resolution, const double* origin,
+                               const double* robot_pose, const Params* params, int32_t* n_obstacles, int32_t* n_vertices, double* vertices, double* radius, double* velocity,
+                               int32_t* dropped, int32_t* info, Entry device_entry) {
+    if (B <= 0) return MPC_OK;
+    if (const int rc = refused(s, B, REF_MAX_BATCH, who)) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t nb = (size_t)B, O = s->cfg.max_obstacles, V = s->cfg.max_vertices;
+    const mpc::StagePiece pc[10] = {stage_in(cost, nb * size_x * size_y), stage_in(origin, nb * 16), stage_in(robot_pose, nb * 24), stage_out(n_obstacles, nb * 4),
+                                    stage_out(n_vertices, nb * O * 4), stage_out(vertices, nb * O * V * 16), stage_out(radius, nb * O * 8), stage_out(velocity, nb * O * 16),
+                                    stage_out(dropped, nb * 4), stage_out(info, nb * 16)};
+    return staged_call(s, who, true, true, pc, 10, [&](void** d) -> int {
+        // the kernel writes the slots it fills: the rest is cleared on the device, behind the copy of the inputs
+        for (int i = 4; i <= 7; ++i) if (d[i]) HIP_TRY(hipMemsetAsync(d[i], 0, pc[i].bytes, s->stream));
+        return device_entry(s, B, (const uint8_t*)d[0], size_x, size_y, resolution, (const double*)d[1], (const double*)d[2], params, (int32_t*)d[3], (int32_t*)d[4], (double*)d[5],
+                            (double*)d[6], (double*)d[7], (int32_t*)d[8], (int32_t*)d[9]);
+    });
 }
 
 extern "C" {
@@ -1360,51 +1425,22 @@ int mpc_costmap_to_polygons_device(mpc_solver* s, int32_t B, const uint8_t* d_co
                                    const double* d_robot_pose, const mpc_cluster_params* params, int32_t* d_n_obstacles, int32_t* d_n_vertices, double* d_vertices,
                                    double* d_radius, double* d_velocity, int32_t* d_dropped, int32_t* d_info) {
     g_err[0] = 0;
-    if (const char* e = to_polygons_error(s, d_cost, size_x, size_y, resolution, d_origin, d_robot_pose, params, d_n_obstacles, d_n_vertices, d_vertices)) { set_err(e); return MPC_EINVAL; }
+    if (to_polygons_error(s, d_cost, size_x, size_y, resolution, d_origin, d_robot_pose, params, d_n_obstacles, d_n_vertices, d_vertices)) return MPC_EINVAL;
     if (B <= 0) return MPC_OK;
-    if (const int rc = refused(s, B, REF_MAX_BATCH, "mpc_costmap_to_polygons")) return rc;
-    HIP_TRY(hipSetDevice(s->device));
-    const size_t need = (size_t)B * size_x * size_y * 4;
-    Buf& lab = s->bufs[BUF_CLUSTER_LAB];
-    if (need > lab.bytes) {      // a launch that still reads the old block may be in flight
-        HIP_TRY(hipStreamSynchronize(s->stream));
-        const hipError_t e = buf_alloc(lab, need);
-        if (e != hipSuccess) { set_err("mpc_costmap_to_polygons: scratch", e); return e == hipErrorOutOfMemory ? MPC_ENOMEM : MPC_EHIP; }
-    }
     mpc::ClusterArgs a;
-    a.cost = d_cost; a.origin = d_origin; a.pose = d_robot_pose;
-    a.size_x = size_x; a.size_y = size_y; a.resolution = resolution;
+    if (const int rc = costmap_shapes_batch(s, "mpc_costmap_to_polygons", B, 4, d_cost, size_x, size_y, resolution, d_origin, d_robot_pose, d_n_obstacles, d_n_vertices, d_vertices,
+                                            d_radius, d_velocity, d_dropped, d_info, a)) return rc;
     a.prm = {params->behind_robot_dist, params->link_dist_sq};
-    a.O = s->cfg.max_obstacles; a.V = s->cfg.max_vertices;
-    a.lab = s->d_cluster_lab;
-    a.n_obstacles = d_n_obstacles; a.n_vertices = d_n_vertices; a.vertices = d_vertices; a.radius = d_radius; a.velocity = d_velocity;
-    a.dropped = d_dropped; a.info = d_info;
-    HIP_TRY(hipEventRecord(s->cev0, s->stream));
-    hipLaunchKernelGGL(mpc::costmap_clusters_kernel, dim3(B), dim3(mpc::kCcThreads), 0, s->stream, a);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(s->cev1, s->stream));
-    s->ctimed = true;
-    return MPC_OK;
+    return costmap_timed_launch(s, mpc::costmap_clusters_kernel, B, mpc::kCcThreads, a);
 }
 
 int mpc_costmap_to_polygons(mpc_solver* s, int32_t B, const uint8_t* cost, int32_t size_x, int32_t size_y, double resolution, const double* origin,
                             const double* robot_pose, const mpc_cluster_params* params, int32_t* n_obstacles, int32_t* n_vertices, double* vertices,
                             double* radius, double* velocity, int32_t* dropped, int32_t* info) {
     g_err[0] = 0;
-    if (const char* e = to_polygons_error(s, cost, size_x, size_y, resolution, origin, robot_pose, params, n_obstacles, n_vertices, vertices)) { set_err(e); return MPC_EINVAL; }
-    if (B <= 0) return MPC_OK;
-    if (const int rc = refused(s, B, REF_MAX_BATCH, "mpc_costmap_to_polygons")) return rc;
-    HIP_TRY(hipSetDevice(s->device));
-    const size_t nb = (size_t)B, O = s->cfg.max_obstacles, V = s->cfg.max_vertices;
-    const mpc::StagePiece pc[10] = {stage_in(cost, nb * size_x * size_y), stage_in(origin, nb * 16), stage_in(robot_pose, nb * 24), stage_out(n_obstacles, nb * 4),
-                                    stage_out(n_vertices, nb * O * 4), stage_out(vertices, nb * O * V * 16), stage_out(radius, nb * O * 8), stage_out(velocity, nb * O * 16),
-                                    stage_out(dropped, nb * 4), stage_out(info, nb * 16)};
-    return staged_call(s, "mpc_costmap_to_polygons", true, true, pc, 10, [&](void** d) -> int {
-        // the kernel writes the slots it fills: the rest is cleared on the device, behind the copy of the inputs
-        for (int i = 4; i <= 7; ++i) if (d[i]) HIP_TRY(hipMemsetAsync(d[i], 0, pc[i].bytes, s->stream));
-        return mpc_costmap_to_polygons_device(s, B, (const uint8_t*)d[0], size_x, size_y, resolution, (const double*)d[1], (const double*)d[2], params, (int32_t*)d[3],
-                                              (int32_t*)d[4], (double*)d[5], (double*)d[6], (double*)d[7], (int32_t*)d[8], (int32_t*)d[9]);
-    });
+    if (to_polygons_error(s, cost, size_x, size_y, resolution, origin, robot_pose, params, n_obstacles, n_vertices, vertices)) return MPC_EINVAL;
+    return costmap_shapes_host(s, "mpc_costmap_to_polygons", B, cost, size_x, size_y, resolution, origin, robot_pose, params, n_obstacles, n_vertices, vertices, radius, velocity,
+                               dropped, info, mpc_costmap_to_polygons_device);
 }
 
 int mpc_last_costmap_ms(mpc_solver* s, float* ms) {
@@ -1414,29 +1450,6 @@ int mpc_last_costmap_ms(mpc_solver* s, float* ms) {
     HIP_TRY(hipEventElapsedTime(ms, s->cev0, s->cev1));
     return MPC_OK;
 }
-
-}  // extern "C"
-
-// ---- costmap -> line segments (mpc_costmap_lines.hpp; declared in include/mpc_costmap_lines.h)
-
-// the argument checks both variants of mpc_costmap_to_lines share: NULL when the call is fine
-static const char* to_lines_error(const mpc_solver* s, const void* cost, int32_t size_x, int32_t size_y, double resolution, const void* origin, const void* robot_pose,
-                                  const mpc_line_params* p, const void* n_obstacles, const void* n_vertices, const void* vertices) {
-    if (!s || !cost || !origin || !robot_pose || !p || !n_obstacles || !n_vertices || !vertices)
-        return "mpc_costmap_to_lines: null argument (cost, origin, robot_pose, params, n_obstacles, n_vertices, vertices)";
-    if (s->cfg.max_obstacles <= 0) return "mpc_costmap_to_lines: the solver was created with max_obstacles = 0";
-    if (s->cfg.max_vertices < 4) return "mpc_costmap_to_lines: the solver was created with max_vertices < 4 (a bounding box has four)";
-    if (size_x < 1 || size_y < 1 || size_x > mpc::kClMaxSize || size_y > mpc::kClMaxSize || (long long)size_x * size_y > mpc::kCcMaxCells || !(resolution > 0))
-        return "mpc_costmap_to_lines: bad costmap geometry (size_x, size_y <= 4096, size_x * size_y <= 2^20)";
-    if (p->link_dist_sq < 1 || p->link_dist_sq > mpc::kCcMaxLink) return "mpc_costmap_to_lines: link_dist_sq has to be in [1, 64]";
-    if (p->inlier_dist_sq < 0 || p->inlier_dist_sq > mpc::kClMaxInlier) return "mpc_costmap_to_lines: inlier_dist_sq has to be in [0, 64]";
-    if (p->min_inliers < 2) return "mpc_costmap_to_lines: min_inliers has to be at least 2";
-    if (p->n_hypotheses < 1 || p->n_hypotheses > mpc::kClMaxHypotheses) return "mpc_costmap_to_lines: n_hypotheses has to be in [1, 65536]";
-    if (p->remaining_outliers < 0) return "mpc_costmap_to_lines: remaining_outliers has to be at least 0";
-    return nullptr;
-}
-
-extern "C" {
 
 void mpc_line_params_defaults(mpc_line_params* p, double resolution, double cluster_max_distance, double ransac_inlier_distance) {
     if (!p) return;
@@ -1455,51 +1468,23 @@ int mpc_costmap_to_lines_device(mpc_solver* s, int32_t B, const uint8_t* d_cost,
                                 const double* d_robot_pose, const mpc_line_params* params, int32_t* d_n_obstacles, int32_t* d_n_vertices, double* d_vertices,
                                 double* d_radius, double* d_velocity, int32_t* d_dropped, int32_t* d_info) {
     g_err[0] = 0;
-    if (const char* e = to_lines_error(s, d_cost, size_x, size_y, resolution, d_origin, d_robot_pose, params, d_n_obstacles, d_n_vertices, d_vertices)) { set_err(e); return MPC_EINVAL; }
+    if (to_lines_error(s, d_cost, size_x, size_y, resolution, d_origin, d_robot_pose, params, d_n_obstacles, d_n_vertices, d_vertices)) return MPC_EINVAL;
     if (B <= 0) return MPC_OK;
-    if (const int rc = refused(s, B, REF_MAX_BATCH, "mpc_costmap_to_lines")) return rc;
-    HIP_TRY(hipSetDevice(s->device));
-    const size_t words = (size_t)B * size_x * size_y, need = words * 8;      // the labels, then the list of a cluster that does not fit the kernel's LDS list
-    Buf& lab = s->bufs[BUF_CLUSTER_LAB];
-    if (need > lab.bytes) {      // a launch that still reads the old block may be in flight
-        HIP_TRY(hipStreamSynchronize(s->stream));
-        const hipError_t e = buf_alloc(lab, need);
-        if (e != hipSuccess) { set_err("mpc_costmap_to_lines: scratch", e); return e == hipErrorOutOfMemory ? MPC_ENOMEM : MPC_EHIP; }
-    }
     mpc::LineArgs a;
-    a.cost = d_cost; a.origin = d_origin; a.pose = d_robot_pose;
-    a.size_x = size_x; a.size_y = size_y; a.resolution = resolution;
+    if (const int rc = costmap_shapes_batch(s, "mpc_costmap_to_lines", B, 8, d_cost, size_x, size_y, resolution, d_origin, d_robot_pose, d_n_obstacles, d_n_vertices, d_vertices,
+                                            d_radius, d_velocity, d_dropped, d_info, a)) return rc;
     a.prm = {params->behind_robot_dist, params->link_dist_sq, params->inlier_dist_sq, params->min_inliers, params->n_hypotheses, params->remaining_outliers};
-    a.O = s->cfg.max_obstacles; a.V = s->cfg.max_vertices;
-    a.lab = s->d_cluster_lab; a.list = reinterpret_cast<uint32_t*>(s->d_cluster_lab + words);
-    a.n_obstacles = d_n_obstacles; a.n_vertices = d_n_vertices; a.vertices = d_vertices; a.radius = d_radius; a.velocity = d_velocity;
-    a.dropped = d_dropped; a.info = d_info;
-    HIP_TRY(hipEventRecord(s->cev0, s->stream));
-    hipLaunchKernelGGL(mpc::costmap_lines_kernel, dim3(B), dim3(mpc::kCcThreads), 0, s->stream, a);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(s->cev1, s->stream));
-    s->ctimed = true;
-    return MPC_OK;
+    a.list = reinterpret_cast<uint32_t*>(s->d_cluster_lab + (size_t)B * size_x * size_y);      // behind the labels
+    return costmap_timed_launch(s, mpc::costmap_lines_kernel, B, mpc::kCcThreads, a);
 }
 
 int mpc_costmap_to_lines(mpc_solver* s, int32_t B, const uint8_t* cost, int32_t size_x, int32_t size_y, double resolution, const double* origin,
                          const double* robot_pose, const mpc_line_params* params, int32_t* n_obstacles, int32_t* n_vertices, double* vertices,
                          double* radius, double* velocity, int32_t* dropped, int32_t* info) {
     g_err[0] = 0;
-    if (const char* e = to_lines_error(s, cost, size_x, size_y, resolution, origin, robot_pose, params, n_obstacles, n_vertices, vertices)) { set_err(e); return MPC_EINVAL; }
-    if (B <= 0) return MPC_OK;
-    if (const int rc = refused(s, B, REF_MAX_BATCH, "mpc_costmap_to_lines")) return rc;
-    HIP_TRY(hipSetDevice(s->device));
-    const size_t nb = (size_t)B, O = s->cfg.max_obstacles, V = s->cfg.max_vertices;
-    const mpc::StagePiece pc[10] = {stage_in(cost, nb * size_x * size_y), stage_in(origin, nb * 16), stage_in(robot_pose, nb * 24), stage_out(n_obstacles, nb * 4),
-                                    stage_out(n_vertices, nb * O * 4), stage_out(vertices, nb * O * V * 16), stage_out(radius, nb * O * 8), stage_out(velocity, nb * O * 16),
-                                    stage_out(dropped, nb * 4), stage_out(info, nb * 16)};
-    return staged_call(s, "mpc_costmap_to_lines", true, true, pc, 10, [&](void** d) -> int {
-        // the kernel writes the slots it fills: the rest is cleared on the device, behind the copy of the inputs
-        for (int i = 4; i <= 7; ++i) if (d[i]) HIP_TRY(hipMemsetAsync(d[i], 0, pc[i].bytes, s->stream));
-        return mpc_costmap_to_lines_device(s, B, (const uint8_t*)d[0], size_x, size_y, resolution, (const double*)d[1], (const double*)d[2], params, (int32_t*)d[3],
-                                           (int32_t*)d[4], (double*)d[5], (double*)d[6], (double*)d[7], (int32_t*)d[8], (int32_t*)d[9]);
-    });
+    if (to_lines_error(s, cost, size_x, size_y, resolution, origin, robot_pose, params, n_obstacles, n_vertices, vertices)) return MPC_EINVAL;
+    return costmap_shapes_host(s, "mpc_costmap_to_lines", B, cost, size_x, size_y, resolution, origin, robot_pose, params, n_obstacles, n_vertices, vertices, radius, velocity,
+                               dropped, info, mpc_costmap_to_lines_device);
 }
 
 }  // extern "C"

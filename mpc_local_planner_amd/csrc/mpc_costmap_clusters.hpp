@@ -37,6 +37,8 @@
 #include "mpc_costmap.hpp"
 #include "mpc_fleet_obstacles.hpp"      // fo_scan_flags (the kernel's ordered counts)
 
+#include <cmath>
+#include <type_traits>
 #include <vector>
 
 namespace mpc {
@@ -55,6 +57,51 @@ struct CcMap {
 };
 // one instance's container: slot o at n_vertices[o], vertices[o][V][2], radius[o] (nullable), velocity[o][2] (nullable)
 struct CcContainer { int32_t* n_vertices; double* vertices; double* radius; double* velocity; };
+
+// What a launch of costmap_clusters_kernel and of costmap_lines_kernel (mpc_costmap_lines.hpp) is told about its batch, and what the host builds of the tests are: the
+// arrays of include/mpc_costmap_clusters.h, instance b at b times the size of one.
+struct CcBatch {
+    const uint8_t* cost;      // [B][size_y][size_x]
+    const double* origin;     // [B][2]
+    const double* pose;       // [B][3]
+    int32_t size_x, size_y;
+    double resolution;
+    int32_t O, V;
+    int32_t* lab;             // [B][size_x * size_y]   the scratch: labels (the kernels; the host statement brings its own)
+    int32_t* n_obstacles;     // [B]
+    int32_t* n_vertices;      // [B][O]
+    double* vertices;         // [B][O][V][2]
+    double* radius;           // [B][O] or NULL
+    double* velocity;         // [B][O][2] or NULL
+    int32_t* dropped;         // [B] or NULL
+    int32_t* info;            // [B][4] or NULL
+};
+
+// map, robot and container of instance b
+MPC_CM_HD void cc_view(const CcBatch& a, int b, CcMap& m, CcContainer& c) {
+    const int W = a.size_x, H = a.size_y, O = a.O, V = a.V;
+    const int ncell = W * H;
+    m.cost = a.cost + (size_t)b * ncell; m.W = W; m.H = H; m.res = a.resolution;
+    m.ox0 = a.origin[2 * b]; m.oy0 = a.origin[2 * b + 1];
+    m.px = a.pose[3 * b]; m.py = a.pose[3 * b + 1];
+    const double th = a.pose[3 * b + 2];
+#if defined(__HIP_DEVICE_COMPILE__)
+    m.hx = cos(th); m.hy = sin(th);
+#else
+    m.hx = std::cos(th); m.hy = std::sin(th);
+#endif
+    c.n_vertices = a.n_vertices + (size_t)b * O;
+    c.vertices = a.vertices + (size_t)b * O * V * 2;
+    c.radius = a.radius ? a.radius + (size_t)b * O : nullptr;
+    c.velocity = a.velocity ? a.velocity + (size_t)b * O * 2 : nullptr;
+}
+
+// rule 5's counts of one instance (dropped, info: nullable)
+MPC_CM_HD void cc_finish(long long total, int O, int32_t* n_obstacles, int32_t* dropped, int32_t* info, int i0, int i1, int i2, int i3) {
+    *n_obstacles = total < O ? (int)total : O;
+    if (dropped) *dropped = total > O ? (int)(total - O) : 0;
+    if (info) { info[0] = i0; info[1] = i1; info[2] = i2; info[3] = i3; }
+}
 
 MPC_CM_HD bool cc_kept(const CcMap& m, int i, int j, double behind) {
     return m.cost[(size_t)j * m.W + i] == kLethal && cm_keep(cm_world(m.ox0, i, m.res), cm_world(m.oy0, j, m.res), m.px, m.py, m.hx, m.hy, behind);
@@ -209,32 +256,15 @@ inline void cc_instance(const CcMap& m, const ClusterParams& prm, int V, int O, 
         cc_cells_of(m, lab, key, cells);
         cc_emit_cluster(m, V, O, cells, u, v, c, total, boxes, as_cells);
     }
-    *n_obstacles = total < O ? (int)total : O;
-    if (dropped) *dropped = (int)(total - *n_obstacles);
-    if (info) { info[0] = kept; info[1] = clusters; info[2] = boxes; info[3] = as_cells; }
+    cc_finish(total, O, n_obstacles, dropped, info, kept, clusters, boxes, as_cells);
 }
 
 #if defined(__HIPCC__)
 
 constexpr int kCcThreads = 256;
 
-struct ClusterArgs {
-    const uint8_t* cost;      // [B][size_y][size_x]
-    const double* origin;     // [B][2]
-    const double* pose;       // [B][3]
-    int32_t size_x, size_y;
-    double resolution;
-    ClusterParams prm;
-    int32_t O, V;
-    int32_t* lab;             // [B][size_x * size_y]   the scratch
-    int32_t* n_obstacles;     // [B]
-    int32_t* n_vertices;      // [B][O]
-    double* vertices;         // [B][O][V][2]
-    double* radius;           // [B][O] or NULL
-    double* velocity;         // [B][O][2] or NULL
-    int32_t* dropped;         // [B] or NULL
-    int32_t* info;            // [B][4] or NULL
-};
+struct ClusterArgs : CcBatch { ClusterParams prm; };
+static_assert(std::is_trivially_copyable<ClusterArgs>::value, "a kernel argument");
 
 // The labels are read and written with relaxed device-scope atomics throughout: the unions below go through atomicMin, which works in L2, and a plain load
 // could be served from a line the CU's L1 still holds from before.
@@ -422,8 +452,62 @@ __device__ __forceinline__ void cc_label_device(const CcMap& m, double behind_di
     __syncthreads();
 }
 
+// The workgroup's steps on the ranked labels that costmap_clusters_kernel and costmap_lines_kernel share.  Every thread calls them.
+
+// Count, first cell and bounding box of the clusters of rank r0 .. r0 + nc - 1 (nc <= 256), cluster r0 + k at word k of the five arrays, by integer LDS atomics
+// (order-independent).  It ends behind a barrier.
+__device__ __forceinline__ void cc_chunk_stats(const int32_t* lab, int nscan, int H, int r0, int nc, int* s_cnt, int* s_first, int* s_imax, int* s_jmin, int* s_jmax) {
+    const int t = threadIdx.x;
+    s_cnt[t] = 0; s_first[t] = 0x7fffffff; s_imax[t] = -1; s_jmin[t] = 0x7fffffff; s_jmax[t] = -1;
+    __syncthreads();
+    for (int p = t; p < nscan; p += kCcThreads) {
+        const int k = -2 - cc_ld(lab + p) - r0;
+        if (k < 0 || k >= nc) continue;
+        const int i = p / H, j = p - i * H;
+        atomicAdd(&s_cnt[k], 1); atomicMin(&s_first[k], p); atomicMax(&s_imax[k], i); atomicMin(&s_jmin[k], j); atomicMax(&s_jmax[k], j);
+    }
+    __syncthreads();
+}
+
+constexpr int kCcNoStop = 0x7fffffff;
+
+// The cells of the cluster whose label is `want` among the scan positions [pbeg, pend), in scan order, numbered by ballot: f(p, place) for each, the places counted
+// on from `at`; returns the place behind the last one.  The sweep ends early once that place has reached `stop` (kCcNoStop: never).  s_ws: 8 words.
+template <typename F>
+__device__ __forceinline__ int cc_sweep_cluster(const int32_t* lab, int want, int pbeg, int pend, int at, int stop, int* s_ws, F f) {
+    const int t = threadIdx.x;
+    for (int p0 = pbeg; p0 < pend && at < stop; p0 += kCcThreads) {
+        const int p = p0 + t;
+        const bool is = p < pend && cc_ld(lab + p) == want;
+        int pre, pre1, tot, tot1;
+        fo_scan_flags(is, false, s_ws, pre, pre1, tot, tot1);
+        if (is) f(p, at + pre);
+        at += tot;
+    }
+    return at;
+}
+
+// One thread writes the shape chosen for a cluster (kind: kCcKind*) into slot `slot`: nothing for kCcKindCells, and nothing at or above O.  nv: the vertices of a
+// hull, which cc_wrap finds again in the w words of column extremes at lo, hi; j0: the row of the first cell.
+__device__ __forceinline__ void cc_put_shape(const CcMap& m, const CcContainer& c, int V, int O, int slot, int kind, int nv, int w, const int* lo, const int* hi, int imin, int imax,
+                                             int j0, int jmin, int jmax, double u, double v) {
+    if (slot < O) {
+        if (kind == kCcKindPoint) cc_put_point(m, c, V, O, slot, imin, j0);
+        else if (kind == kCcKindBox) cc_put_box(m, c, V, O, slot, imin, imax, jmin, jmax);
+        else if (kind == kCcKindLine) {      // one row, first and last cell
+            cc_put_vertex(m, c, V, slot, 0, imin, jmin);
+            cc_put_vertex(m, c, V, slot, 1, imax, jmin);
+            cc_close_slot(c, slot, 2);
+        } else if (kind == kCcKindHull) {
+            bool inside;
+            cc_wrap(lo, hi, w, imin, V, u, v, inside, &m, &c, slot);
+            cc_close_slot(c, slot, nv);
+        }
+    }
+}
+
 // One workgroup (256 threads) per instance: keep, link and rank by cc_label_device, then
-//   shape  : the clusters in chunks of 256 in rank order, thread k on cluster r0 + k.  Count, first cell and bounding box by integer LDS atomics (order-independent);
+//   shape  : the clusters in chunks of 256 in rank order, thread k on cluster r0 + k.  Count, first cell and bounding box by cc_chunk_stats;
 //            then runs of clusters whose column spans fit kCcMaxSpan words together: column extremes by LDS atomicMin / atomicMax, cc_wrap per thread once for the
 //            vertex count and the robot test, an ordered prefix of the obstacles every cluster emits gives the slots, cc_wrap again writes the vertices;
 //   cells  : a cluster that contains the robot is swept in scan order by the whole workgroup, its cells numbered by ballot.
@@ -443,16 +527,8 @@ __global__ __launch_bounds__(kCcThreads) void costmap_clusters_kernel(ClusterArg
     const int ncell = W * H, nscan = ncol > 0 && nrow > 0 ? ncol * H : 0;      // the sweeps' range: the scan positions of the visited columns
     int32_t* lab = a.lab + (size_t)b * ncell;
     CcMap m;
-    m.cost = a.cost + (size_t)b * ncell; m.W = W; m.H = H; m.res = a.resolution;
-    m.ox0 = a.origin[2 * b]; m.oy0 = a.origin[2 * b + 1];
-    m.px = a.pose[3 * b]; m.py = a.pose[3 * b + 1];
-    const double th = a.pose[3 * b + 2];
-    m.hx = cos(th); m.hy = sin(th);
     CcContainer c;
-    c.n_vertices = a.n_vertices + (size_t)b * O;
-    c.vertices = a.vertices + (size_t)b * O * V * 2;
-    c.radius = a.radius ? a.radius + (size_t)b * O : nullptr;
-    c.velocity = a.velocity ? a.velocity + (size_t)b * O * 2 : nullptr;
+    cc_view(a, b, m, c);
     const double u = cc_index_of(m.px, m.ox0, m.res), v = cc_index_of(m.py, m.oy0, m.res);
     if (t < 2) s_tot[t] = 0;
     int kept, nclusters;
@@ -461,15 +537,7 @@ __global__ __launch_bounds__(kCcThreads) void costmap_clusters_kernel(ClusterArg
     int total = 0;      // obstacles emitted so far (workgroup-uniform)
     for (int r0 = 0; r0 < nclusters; r0 += kCcThreads) {
         const int nc = nclusters - r0 < kCcThreads ? nclusters - r0 : kCcThreads;
-        s_cnt[t] = 0; s_first[t] = 0x7fffffff; s_imax[t] = -1; s_jmin[t] = 0x7fffffff; s_jmax[t] = -1;
-        __syncthreads();
-        for (int p = t; p < nscan; p += kCcThreads) {
-            const int k = -2 - cc_ld(lab + p) - r0;
-            if (k < 0 || k >= nc) continue;
-            const int i = p / H, j = p - i * H;
-            atomicAdd(&s_cnt[k], 1); atomicMin(&s_first[k], p); atomicMax(&s_imax[k], i); atomicMin(&s_jmin[k], j); atomicMax(&s_jmax[k], j);
-        }
-        __syncthreads();
+        cc_chunk_stats(lab, nscan, H, r0, nc, s_cnt, s_first, s_imax, s_jmin, s_jmax);
         const bool mine = t < nc;
         const int cnt = mine ? s_cnt[t] : 0, first = mine ? s_first[t] : 0, imax = mine ? s_imax[t] : 0, jmin = mine ? s_jmin[t] : 0, jmax = mine ? s_jmax[t] : 0;
         const int imin = first / H, span = imax - imin + 1;
@@ -520,44 +588,20 @@ __global__ __launch_bounds__(kCcThreads) void costmap_clusters_kernel(ClusterArg
             const int ninc = cc_block_scan(nout, s_part, ntot);
             const int slot = total + ninc - nout;
             s_kind[t] = run ? kind : kCcKindPoint; s_slot[t] = slot;
-            if (run && slot < O) {
-                if (kind == kCcKindPoint) cc_put_point(m, c, V, O, slot, imin, first - imin * H);
-                else if (kind == kCcKindBox) cc_put_box(m, c, V, O, slot, imin, imax, jmin, jmax);
-                else if (kind == kCcKindLine) {      // one row, first and last cell
-                    cc_put_vertex(m, c, V, slot, 0, imin, jmin);
-                    cc_put_vertex(m, c, V, slot, 1, imax, jmin);
-                    cc_close_slot(c, slot, 2);
-                } else if (kind == kCcKindHull) {
-                    bool inside;
-                    cc_wrap(lo, hi, w, imin, V, u, v, inside, &m, &c, slot);
-                    cc_close_slot(c, slot, nv);
-                }
-            }
+            if (run) cc_put_shape(m, c, V, O, slot, kind, nv, w, lo, hi, imin, imax, first - imin * H, jmin, jmax, u, v);
             __syncthreads();
             // ---- cells: the clusters of the run that contain the robot, one after the other
             for (int k = k0; k < k1; ++k) {
                 if (s_kind[k] != kCcKindCells) continue;      // workgroup-uniform
                 const int want = -2 - (r0 + k), pbeg = (s_first[k] / H) * H, pend = (s_imax[k] + 1) * H;
-                int at = s_slot[k];
-                for (int p0 = pbeg; p0 < pend && at < O; p0 += kCcThreads) {
-                    const int p = p0 + t;
-                    const bool is = p < pend && cc_ld(lab + p) == want;
-                    int pre, pre1b, tot, tot1b;
-                    fo_scan_flags(is, false, s_ws, pre, pre1b, tot, tot1b);
-                    if (is) cc_put_point(m, c, V, O, at + pre, p / H, p % H);
-                    at += tot;
-                }
+                cc_sweep_cluster(lab, want, pbeg, pend, s_slot[k], O, s_ws, [&](int p, int place) { cc_put_point(m, c, V, O, place, p / H, p % H); });
             }
             __syncthreads();
             total += ntot;
             k0 = k1;
         }
     }
-    if (t == 0) {
-        a.n_obstacles[b] = total < O ? total : O;
-        if (a.dropped) a.dropped[b] = total > O ? total - O : 0;
-        if (a.info) { int32_t* f = a.info + 4 * b; f[0] = kept; f[1] = nclusters; f[2] = s_tot[0]; f[3] = s_tot[1]; }
-    }
+    if (t == 0) cc_finish(total, O, a.n_obstacles + b, a.dropped ? a.dropped + b : nullptr, a.info ? a.info + 4 * b : nullptr, kept, nclusters, s_tot[0], s_tot[1]);
 }
 
 #endif  // __HIPCC__

@@ -174,31 +174,16 @@ inline void cl_instance(const CcMap& m, const LineParams& prm, int V, int O, int
         if ((long long)cells.size() < prm.min_inliers) cc_emit_cluster(m, V, O, cells, u, v, c, total, boxes, as_cells);      // rule 2
         else cl_extract(m, prm, V, O, cells, c, total, lines, points);
     }
-    *n_obstacles = total < O ? (int)total : O;
-    if (dropped) *dropped = (int)(total - *n_obstacles);
-    if (info) { info[0] = kept; info[1] = clusters; info[2] = lines; info[3] = points; }
+    cc_finish(total, O, n_obstacles, dropped, info, kept, clusters, lines, points);
 }
 
 #if defined(__HIPCC__)
 
-struct LineArgs {
-    const uint8_t* cost;      // [B][size_y][size_x]
-    const double* origin;     // [B][2]
-    const double* pose;       // [B][3]
-    int32_t size_x, size_y;
-    double resolution;
+struct LineArgs : CcBatch {
     LineParams prm;
-    int32_t O, V;
-    int32_t* lab;             // [B][size_x * size_y]   the scratch: labels
     uint32_t* list;           // [B][size_x * size_y]   the scratch: the cell list of a cluster that does not fit the LDS list
-    int32_t* n_obstacles;     // [B]
-    int32_t* n_vertices;      // [B][O]
-    double* vertices;         // [B][O][V][2]
-    double* radius;           // [B][O] or NULL
-    double* velocity;         // [B][O][2] or NULL
-    int32_t* dropped;         // [B] or NULL
-    int32_t* info;            // [B][4] or NULL
 };
+static_assert(std::is_trivially_copyable<LineArgs>::value, "a kernel argument");
 
 // The gap rule's bins along t.  A bin is wb = floor(sqrt(link_dist_sq * len2)) wide, so two inliers of one bin are never a break apart, and two inliers with an empty
 // bin between them always are (their distance is at least wb + 1): the breaks are the empty bins and those pairs of neighbouring bins whose nearest cells are too far
@@ -356,7 +341,7 @@ __device__ __forceinline__ void cl_extract_device(uint32_t* list, int r, const L
 }
 
 // One workgroup (256 threads) per instance: keep, link and rank by cc_label_device (mpc_costmap_clusters.hpp), then the clusters one after the other in rank order.
-// Count, first cell and bounding box of 256 clusters at a time by integer LDS atomics, as costmap_clusters_kernel has them.
+// Count, first cell and bounding box of 256 clusters at a time by cc_chunk_stats, as costmap_clusters_kernel has them.
 //   small  : fewer than min_inliers cells.  Column extremes by LDS atomicMin / atomicMax, cc_wrap by one thread for the vertex count and the robot test, again to write
 //            the vertices; a cluster that contains the robot is swept in scan order by the workgroup: the shapes and the bytes of costmap_clusters_kernel.
 //   lines  : the cells in scan order into the list by ordered ballots, then cl_extract_device.
@@ -380,46 +365,25 @@ __global__ __launch_bounds__(kCcThreads) __attribute__((amdgpu_waves_per_eu(4)))
     int32_t* lab = a.lab + (size_t)b * ncell;
     uint32_t* glist = a.list + (size_t)b * ncell;
     CcMap m;
-    m.cost = a.cost + (size_t)b * ncell; m.W = W; m.H = H; m.res = a.resolution;
-    m.ox0 = a.origin[2 * b]; m.oy0 = a.origin[2 * b + 1];
-    m.px = a.pose[3 * b]; m.py = a.pose[3 * b + 1];
-    const double th = a.pose[3 * b + 2];
-    m.hx = cos(th); m.hy = sin(th);
     CcContainer c;
-    c.n_vertices = a.n_vertices + (size_t)b * O;
-    c.vertices = a.vertices + (size_t)b * O * V * 2;
-    c.radius = a.radius ? a.radius + (size_t)b * O : nullptr;
-    c.velocity = a.velocity ? a.velocity + (size_t)b * O * 2 : nullptr;
+    cc_view(a, b, m, c);
     const double u = cc_index_of(m.px, m.ox0, m.res), v = cc_index_of(m.py, m.oy0, m.res);
     int kept, nclusters;
     cc_label_device(m, a.prm.behind_dist, a.prm.link_dist_sq, lab, s_ext, s_ws, &s_nlist, kept, nclusters);
     int total = 0, lines = 0, points = 0;      // workgroup-uniform
     for (int r0 = 0; r0 < nclusters; r0 += kCcThreads) {
         const int nc = nclusters - r0 < kCcThreads ? nclusters - r0 : kCcThreads;
-        s_cnt[t] = 0; s_first[t] = 0x7fffffff; s_imax[t] = -1; s_jmin[t] = 0x7fffffff; s_jmax[t] = -1;
-        __syncthreads();
-        for (int p = t; p < nscan; p += kCcThreads) {
-            const int k = -2 - cc_ld(lab + p) - r0;
-            if (k < 0 || k >= nc) continue;
-            const int i = p / H, j = p - i * H;
-            atomicAdd(&s_cnt[k], 1); atomicMin(&s_first[k], p); atomicMax(&s_imax[k], i); atomicMin(&s_jmin[k], j); atomicMax(&s_jmax[k], j);
-        }
-        __syncthreads();
+        cc_chunk_stats(lab, nscan, H, r0, nc, s_cnt, s_first, s_imax, s_jmin, s_jmax);
         for (int k = 0; k < nc; ++k) {
             const int cnt = s_cnt[k], first = s_first[k], imax = s_imax[k], jmin = s_jmin[k], jmax = s_jmax[k];
             const int imin = first / H, want = -2 - (r0 + k), pbeg = imin * H, pend = (imax + 1) * H;
             if (cnt >= a.prm.min_inliers) {
                 // ---- lines
                 uint32_t* const list = cnt <= kClListCap ? s_list : glist;
-                int at = 0;
-                for (int p0 = pbeg; p0 < pend; p0 += kCcThreads) {
-                    const int p = p0 + t;
-                    const bool is = p < pend && cc_ld(lab + p) == want;
-                    int pre, pre1, tot, tot1;
-                    fo_scan_flags(is, false, s_ws, pre, pre1, tot, tot1);
-                    if (is) { const int i = p / H, j = p - i * H; list[at + pre] = ((uint32_t)(i - imin) << 16) | (uint32_t)(j - jmin); }
-                    at += tot;
-                }
+                cc_sweep_cluster(lab, want, pbeg, pend, 0, kCcNoStop, s_ws, [&](int p, int place) {
+                    const int i = p / H, j = p - i * H;
+                    list[place] = ((uint32_t)(i - imin) << 16) | (uint32_t)(j - jmin);
+                });
                 __syncthreads();
                 if (cnt <= kClListCap) cl_extract_device(s_list, cnt, a.prm, m, c, V, O, imin, jmin, s_bin, s_joined, s_start, s_part, s_ws, s_red, total, lines, points);
                 else cl_extract_device(glist, cnt, a.prm, m, c, V, O, imin, jmin, s_bin, s_joined, s_start, s_part, s_ws, s_red, total, lines, points);
@@ -448,34 +412,19 @@ __global__ __launch_bounds__(kCcThreads) __attribute__((amdgpu_waves_per_eu(4)))
                 if (nv < 3) inside = false;
                 if (kind == kCcKindBox) inside = cc_in_box(imin, imax, jmin, jmax, u, v);
                 if (inside) kind = kCcKindCells;
-                if (total < O) {
-                    if (kind == kCcKindBox) cc_put_box(m, c, V, O, total, imin, imax, jmin, jmax);
-                    else if (kind == kCcKindHull) { cc_wrap(s_lo, s_hi, w, imin, V, u, v, inside, &m, &c, total); cc_close_slot(c, total, nv); }
-                }
+                cc_put_shape(m, c, V, O, total, kind, nv, w, s_lo, s_hi, imin, imax, first - imin * H, jmin, jmax, u, v);
                 s_shape[0] = kind;
             }
             __syncthreads();
             if (s_shape[0] == kCcKindCells) {      // workgroup-uniform
-                int at = total;
-                for (int p0 = pbeg; p0 < pend && at < O; p0 += kCcThreads) {
-                    const int p = p0 + t;
-                    const bool is = p < pend && cc_ld(lab + p) == want;
-                    int pre, pre1, tot, tot1;
-                    fo_scan_flags(is, false, s_ws, pre, pre1, tot, tot1);
-                    if (is) cc_put_point(m, c, V, O, at + pre, p / H, p % H);
-                    at += tot;
-                }
+                cc_sweep_cluster(lab, want, pbeg, pend, total, O, s_ws, [&](int p, int place) { cc_put_point(m, c, V, O, place, p / H, p % H); });
                 total += cnt;
             } else ++total;
             __syncthreads();
         }
         __syncthreads();
     }
-    if (t == 0) {
-        a.n_obstacles[b] = total < O ? total : O;
-        if (a.dropped) a.dropped[b] = total > O ? total - O : 0;
-        if (a.info) { int32_t* f = a.info + 4 * b; f[0] = kept; f[1] = nclusters; f[2] = lines; f[3] = points; }
-    }
+    if (t == 0) cc_finish(total, O, a.n_obstacles + b, a.dropped ? a.dropped + b : nullptr, a.info ? a.info + 4 * b : nullptr, kept, nclusters, lines, points);
 }
 
 #endif  // __HIPCC__

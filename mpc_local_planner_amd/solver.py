@@ -420,13 +420,22 @@ class BatchSolver:
         assert vp.shape == (nv.shape[0], self.cfg.max_via_points, 3), vp.shape
         self._check(self._lib.mpc_set_via_points(self._h, int(nv.shape[0]), _addr(nv), _addr(vp)))
 
+    @staticmethod
+    def _costmap_inputs(cost, origin, robot_pose):
+        """(cost uint8 (B, size_y, size_x), origin (B, 2), robot_pose (B, 3), B, size_x, size_y), contiguous, of a costmap step's inputs"""
+        cost = np.ascontiguousarray(cost, dtype=np.uint8)
+        B, sy, sx = cost.shape
+        return cost, np.ascontiguousarray(origin, dtype=np.float64).reshape(B, 2), np.ascontiguousarray(robot_pose, dtype=np.float64).reshape(B, 3), B, sx, sy
+
+    def _shape_outputs(self, B):
+        """the zeroed outputs of costmap_to_polygons / costmap_to_lines, in the order of their return tuple"""
+        O, V, z = int(self.cfg.max_obstacles), max(1, int(self.cfg.max_vertices)), np.zeros
+        return z(B, np.int32), z((B, O), np.int32), z((B, O, V, 2)), z((B, O)), z((B, O, 2)), z(B, np.int32), z((B, 4), np.int32)
+
     def costmap_to_obstacles(self, cost, resolution, origin, robot_pose, behind_robot_dist=1.5):
         """Lethal costmap cells -> point obstacles in this solver's obstacle layout (mpc_costmap_to_obstacles).
         cost: uint8 [B][size_y][size_x]; origin [B][2]; robot_pose [B][3].  Returns (n_obstacles[B], n_vertices[B][O], vertices[B][O][V][2], dropped[B])."""
-        cost = np.ascontiguousarray(cost, dtype=np.uint8)
-        B, sy, sx = cost.shape
-        org = np.ascontiguousarray(origin, dtype=np.float64).reshape(B, 2)
-        pose = np.ascontiguousarray(robot_pose, dtype=np.float64).reshape(B, 3)
+        cost, org, pose, B, sx, sy = self._costmap_inputs(cost, origin, robot_pose)
         O, V = self.cfg.max_obstacles, max(1, self.cfg.max_vertices)
         no = np.zeros(B, np.int32); nv = np.zeros((B, O), np.int32); vt = np.zeros((B, O, V, 2)); dr = np.zeros(B, np.int32)
         self._check(self._lib.mpc_costmap_to_obstacles(self._h, B, _addr(cost), sx, sy, float(resolution), _addr(org), _addr(pose), float(behind_robot_dist),
@@ -447,17 +456,12 @@ class BatchSolver:
         cost: uint8 [B][size_y][size_x]; origin [B][2]; robot_pose [B][3].  Returns (n_obstacles (B,), n_vertices (B, O), vertices (B, O, V, 2), radius (B, O),
         velocity (B, O, 2), dropped (B,), info (B, 4) = kept cells, clusters, hulls replaced by their box, clusters emitted as cells): the first five are `obstacles` of
         solve() / step() / controller_step()."""
-        cost = np.ascontiguousarray(cost, dtype=np.uint8)
-        B, sy, sx = cost.shape
-        org = np.ascontiguousarray(origin, dtype=np.float64).reshape(B, 2)
-        pose = np.ascontiguousarray(robot_pose, dtype=np.float64).reshape(B, 3)
-        O, V = int(self.cfg.max_obstacles), max(1, int(self.cfg.max_vertices))
-        no, nv, vt = np.zeros(B, np.int32), np.zeros((B, O), np.int32), np.zeros((B, O, V, 2))
-        rd, vl, dr, info = np.zeros((B, O)), np.zeros((B, O, 2)), np.zeros(B, np.int32), np.zeros((B, 4), np.int32)
+        cost, org, pose, B, sx, sy = self._costmap_inputs(cost, origin, robot_pose)
+        out = self._shape_outputs(B)
         p = self.cluster_params(resolution, cluster_max_distance, behind_robot_dist)
         self._check(self._lib.mpc_costmap_to_polygons(self._h, B, _addr(cost), sx, sy, float(resolution), _addr(org), _addr(pose), C.byref(p),
-                                                      *map(_addr, (no, nv, vt, rd, vl, dr, info))))
-        return no, nv, vt, rd, vl, dr, info
+                                                      *map(_addr, out)))
+        return out
 
     def costmap_to_polygons_device(self, B: int, cost: int, size_x: int, size_y: int, resolution: float, origin: int, robot_pose: int, params: MpcClusterParams,
                                    n_obstacles: int, n_vertices: int, vertices: int, radius: Optional[int] = None, velocity: Optional[int] = None,
@@ -484,17 +488,12 @@ class BatchSolver:
         cost: uint8 [B][size_y][size_x]; origin [B][2]; robot_pose [B][3].  Returns (n_obstacles (B,), n_vertices (B, O), vertices (B, O, V, 2), radius (B, O),
         velocity (B, O, 2), dropped (B,), info (B, 4) = kept cells, clusters, lines, cells emitted as points by the line rule): the first five are `obstacles` of
         solve() / step() / controller_step()."""
-        cost = np.ascontiguousarray(cost, dtype=np.uint8)
-        B, sy, sx = cost.shape
-        org = np.ascontiguousarray(origin, dtype=np.float64).reshape(B, 2)
-        pose = np.ascontiguousarray(robot_pose, dtype=np.float64).reshape(B, 3)
-        O, V = int(self.cfg.max_obstacles), max(1, int(self.cfg.max_vertices))
-        no, nv, vt = np.zeros(B, np.int32), np.zeros((B, O), np.int32), np.zeros((B, O, V, 2))
-        rd, vl, dr, info = np.zeros((B, O)), np.zeros((B, O, 2)), np.zeros(B, np.int32), np.zeros((B, 4), np.int32)
+        cost, org, pose, B, sx, sy = self._costmap_inputs(cost, origin, robot_pose)
+        out = self._shape_outputs(B)
         p = params if params is not None else self.line_params(resolution)
         self._check(self._lib.mpc_costmap_to_lines(self._h, B, _addr(cost), sx, sy, float(resolution), _addr(org), _addr(pose), C.byref(p),
-                                                   *map(_addr, (no, nv, vt, rd, vl, dr, info))))
-        return no, nv, vt, rd, vl, dr, info
+                                                   *map(_addr, out)))
+        return out
 
     def costmap_to_lines_device(self, B: int, cost: int, size_x: int, size_y: int, resolution: float, origin: int, robot_pose: int, params: MpcLineParams,
                                 n_obstacles: int, n_vertices: int, vertices: int, radius: Optional[int] = None, velocity: Optional[int] = None,

@@ -915,13 +915,27 @@ MPC_HD int riccati_root(const RicState<T>& V, const Problem<T>& P_, T& dd_out, T
     return (t_finite(sol[0]) && t_finite(sol[1]) && t_finite(sol[2]) && t_finite(sol[3])) ? 1 : 0;
 }
 
+// A decision every lane of the wave takes alike, as ONE scalar: on the device the compare's lane mask read as a scalar condition (a branch on it is a scalar branch, no
+// exec mask, no select per value), on the host the bool itself.  Only for operands that are the same in every active lane.  uni_if<false> is the bool as it stands.
+MPC_HD bool uni_true(bool b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_ballot_w64(b) != 0;
+#else
+    return b;
+#endif
+}
+template <bool UNI> MPC_HD bool uni_if(bool b) { if constexpr (UNI) return uni_true(b); else return b; }
+
 // riccati_root with the shape known at compile time (DTF: dt free; FXM: bits 0..2 = the fixed goal components): the system over the unknowns that exist alone, in
 // riccati_root's order -- dt first, then the fixed components' nu ascending; the inertia count over nu ascending, then dt.  An identity row of riccati_root is never the
 // row a column's exchange brings up before its own column (it holds one entry, on its diagonal), multiplies its neighbours by +-0 only and solves to 0: leaving it out
 // leaves every other operation with the same operands in the same order.  Same return codes, same dd / nu bit for bit (tests/test_shape_root_host.py) -- for a shape with
 // identity rows with one exception: what is left in dd / nu behind an answer of 0, where riccati_root drags a NaN through those rows (0 x NaN) and no caller reads the
 // values.  The headline shape has no identity rows and no exception.  The shape-known instantiation of the wave kernel calls it (mpc_wave.hpp, SHAPE).
-template <bool DTF, int FXM, typename T>
+// UNI (r25, riccati_root_uniform below): for a wave whose lanes all hold the same system in VECTOR registers -- a partial-pivot exchange is a wave-uniform branch around a swap
+// of the two rows instead of two selects per entry and compare, and the okp / inertia / ok / finite flags, gathered as without UNI, are read as scalars once each.  The fp
+// operations, their operands and their order are the same text either way.
+template <bool DTF, int FXM, bool UNI = false, typename T>
 MPC_HD int riccati_root_shape(const RicState<T>& V, T& dd_out, T nu_out[3]) {
     constexpr int NF = (FXM & 1) + ((FXM >> 1) & 1) + ((FXM >> 2) & 1);      // fixed components = rows of nu = what the inertia asks for
     constexpr int N = NF + (DTF ? 1 : 0);
@@ -971,8 +985,8 @@ MPC_HD int riccati_root_shape(const RicState<T>& V, T& dd_out, T nu_out[3]) {
                     for (int b = c + 1; b < N; ++b) B[r][b] -= m * B[c][b];
                 }
             }
-            if (!okp) return 0;
-            if (neg != NF) return -1;
+            if (!uni_if<UNI>(okp)) return 0;
+            if (uni_if<UNI>(neg != NF)) return -1;
         }
         T ipiv[N];
         bool ok = true;
@@ -981,8 +995,15 @@ MPC_HD int riccati_root_shape(const RicState<T>& V, T& dd_out, T nu_out[3]) {
 #pragma unroll
             for (int r = c + 1; r < N; ++r) {
                 const bool sw = t_abs(A[r][c]) > t_abs(A[c][c]);
+                if constexpr (UNI) {
+                    if (uni_true(sw)) {
+#pragma unroll
+                        for (int b = 0; b < N + 1; ++b) { const T x = A[c][b]; A[c][b] = A[r][b]; A[r][b] = x; }
+                    }
+                } else {
 #pragma unroll
                 for (int b = 0; b < N + 1; ++b) { const T x = A[c][b], y = A[r][b]; A[c][b] = sw ? y : x; A[r][b] = sw ? x : y; }
+                }
             }
             const T best = t_abs(A[c][c]);
             ok = ok && (best > T(0)) && t_finite(best);
@@ -995,7 +1016,7 @@ MPC_HD int riccati_root_shape(const RicState<T>& V, T& dd_out, T nu_out[3]) {
                 for (int b = c; b < N + 1; ++b) A[r][b] -= m * A[c][b];
             }
         }
-        if (!ok) return 0;
+        if (!uni_if<UNI>(ok)) return 0;
         T sol[N];
 #pragma unroll
         for (int c = N - 1; c >= 0; --c) {
@@ -1010,9 +1031,14 @@ MPC_HD int riccati_root_shape(const RicState<T>& V, T& dd_out, T nu_out[3]) {
         for (int c = 0; c < N; ++c) { fin = fin && t_finite(sol[c]); out4[idx[c]] = sol[c]; }
         dd_out = out4[0];
         nu_out[0] = out4[1]; nu_out[1] = out4[2]; nu_out[2] = out4[3];
-        return fin ? 1 : 0;
+        return uni_if<UNI>(fin) ? 1 : 0;
     }
 }
+
+// riccati_root_shape for the fixed-layout kernels' sweeps, which take the tableau with row broadcasts (mpc_wave_pit.inc) or v_readlane (the serial sweeps): UNI.  dd / nu
+// and the answer are riccati_root_shape's bit for bit (tests/test_root_uniform_host.py holds the host build of both against each other).
+template <bool DTF, int FXM, typename T>
+MPC_HD int riccati_root_uniform(const RicState<T>& V, T& dd_out, T nu_out[3]) { return riccati_root_shape<DTF, FXM, true>(V, dd_out, nu_out); }
 
 // Excess of negative eigenvalues of the pivot block of a combine step of the partitioned sweep (mpc_wave.hpp::backward_pit): n-(W) + n-(P+ - W^-1) - 5 for symmetric 5 x 5
 // matrices given by their upper triangles, index u(a, b) = a (9 - a) / 2 + b for a <= b.  The block [[W, -I], [-I, P+]] over the five components with a costate column has the

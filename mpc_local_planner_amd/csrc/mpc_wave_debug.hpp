@@ -36,6 +36,7 @@ enum ProfCol : int {
     // the sweeps' inner counters (MPC_LAP; parts of `backward` / `forward`): backward stage loops | hand-off + combines (serial: the set-up before the loop) | forward stage loop |
     // the partitioned sweeps' fixed work: backward_pit up to its first stage | forward_pit before / behind its segment loop
     PROF_BWD_LOOP, PROF_BWD_SETUP, PROF_FWD_LOOP, PROF_PIT_PRE, PROF_FWD_PRE, PROF_FWD_POST,
+    // not ticks (r25, MPC_PROF_ROOT_ROWS): the roots of backward_pit at which the four DPP rows did NOT hold the same bits in the registers the tableau is broadcast from; 0
     PROF_SPARE
 };
 constexpr int kProfCols = 26;
@@ -46,7 +47,8 @@ __device__ long long g_mpc_prof[4096][mpc::kProfCols];      // (one per translat
 
 #define MPC_PROF_MEMBERS \
     mutable long long prof_mult = 0; \
-    mutable long long prof_bwd_loop = 0, prof_bwd_setup = 0, prof_fwd_loop = 0, prof_pit_pre = 0, prof_fwd_pre = 0, prof_fwd_post = 0;
+    mutable long long prof_bwd_loop = 0, prof_bwd_setup = 0, prof_fwd_loop = 0, prof_pit_pre = 0, prof_fwd_pre = 0, prof_fwd_post = 0; \
+    mutable long long prof_root_rows = 0;
 #define MPC_PROF_BEGIN \
         long long tk[mpc::kProfTicks] = {}; int nfac = 0, ntrial = 0; \
         const long long t_begin = __builtin_readcyclecounter(); \
@@ -63,10 +65,18 @@ __device__ long long g_mpc_prof[4096][mpc::kProfCols];      // (one per translat
             o[mpc::PROF_BWD_LOOP] = prof_bwd_loop; o[mpc::PROF_BWD_SETUP] = prof_bwd_setup; o[mpc::PROF_FWD_LOOP] = prof_fwd_loop; \
             o[mpc::PROF_PIT_PRE] = prof_pit_pre; o[mpc::PROF_FWD_PRE] = prof_fwd_pre; o[mpc::PROF_FWD_POST] = prof_fwd_post; \
             if (prof_mult) o[mpc::PROF_LOGS0] = prof_mult; \
+            o[mpc::PROF_SPARE] = prof_root_rows; \
         }
 // the sweeps' inner counters: MPC_LAP_BEGIN(t) stamps a local, MPC_LAP(counter, t) adds the ticks since t's stamp to prof_<counter> and stamps t again
 #define MPC_LAP_BEGIN(t) long long t = __builtin_readcyclecounter();
 #define MPC_LAP(counter, t) { const long long now_ = __builtin_readcyclecounter(); prof_##counter += now_ - t; t = now_; }
+// the shape-known kernels take the root system's entries by ROW broadcasts (MPC_DPP_BLOCK_ROOT), which is right when lanes c, c + 16, c + 32, c + 48 of the five source registers
+// hold the same bits: every lane compares its words with those of its column in row 0 (ds_bpermute), and a root at which any lane differs counts once (wave-uniform)
+#define MPC_PROF_ROOT_ROWS(v5, om_, w0, w1, w2) { \
+            const T src_[5] = {v5, om_, w0, w1, w2}; bool diff_ = false; \
+            for (int i_ = 0; i_ < 5; ++i_) { const T r0_ = lane_gather(src_[i_], lane & 15); \
+                                             diff_ = diff_ || __double2hiint((double)r0_) != __double2hiint((double)src_[i_]) || __double2loint((double)r0_) != __double2loint((double)src_[i_]); } \
+            if (__builtin_amdgcn_ballot_w64(diff_) != 0) ++prof_root_rows; }
 #else
 #define MPC_PROF_MEMBERS
 #define MPC_PROF_BEGIN
@@ -76,6 +86,7 @@ __device__ long long g_mpc_prof[4096][mpc::kProfCols];      // (one per translat
 #define MPC_PROF_END
 #define MPC_LAP_BEGIN(t)
 #define MPC_LAP(counter, t) do { } while (0)
+#define MPC_PROF_ROOT_ROWS(v5, om_, w0, w1, w2) do { } while (0)
 #endif
 #if defined(MPC_PROFILE) && defined(MPC_PROFILE_MULT)      // the ticks of the enclosing scope go to prof_mult, which takes the place of `logs0` in the row
 #define MPC_PROF_SCOPE_MULT \

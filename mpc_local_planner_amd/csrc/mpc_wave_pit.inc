@@ -64,7 +64,8 @@
         unsigned ci;           // pit_combine_inertia: word of the row's saved value function | its first source lane << 16
         unsigned fp[4], fs[4]; // forward half: byte offsets of the eight coefficient streams at the row's first stage and their steps in bytes, two per word
         unsigned fo;           // forward half: byte offset of the lane's output word at the row's first stage | its step in bytes << 16
-        unsigned fx;           // forward half: word of the lane's component of its row's boundary state (a zero word where there is none) | segment of stage `lane` << 16
+        unsigned fx;           // forward half: word of the lane's component of its row's boundary state (a zero word where there is none) | segment of stage `lane` << 16 |
+                               // min(c, 4) << 29, the lane's row of a saved tile in the boundary products (bits 26..28 are zero: fx >> 26 is that row times 8)
         __device__ __forceinline__ unsigned bptr(int i, bool tail) const { return tail ? bp[i] >> 16 : bp[i] & 0xffffu; }
         __device__ __forceinline__ int bstep(int i) const { return (int)((i & 1) ? bs[i >> 1] >> 16 : bs[i >> 1] & 0xffffu); }
         __device__ __forceinline__ unsigned fptr(int j) const { return (j & 1) ? fp[j >> 1] >> 16 : fp[j >> 1] & 0xffffu; }
@@ -137,7 +138,7 @@
             const int os = c < 5 ? 1 : 0;
             C.fo = (unsigned)(((c < 3 ? L.DX + c * L.NS + 1 : (c < 5 ? L.DU + (c - 3) * L.NS : L.VP + 12)) + os * k0) * B8) | ((unsigned)(os * B8) << 16);
             const int seg = (lane >= Lm ? 1 : 0) + (lane >= 2 * Lm ? 1 : 0) + (lane >= 3 * Lm ? 1 : 0);
-            C.fx = (unsigned)((c < 5 && row > 0) ? L.DX + 100 + 5 * (row - 1) + c : L.ZC) | ((unsigned)seg << 16);
+            C.fx = (unsigned)((c < 5 && row > 0) ? L.DX + 100 + 5 * (row - 1) + c : L.ZC) | ((unsigned)seg << 16) | ((unsigned)(c < 4 ? c : 4) << 29);
         }
         return C;
     }
@@ -450,6 +451,25 @@
         // ---- root: the value function at stage 0 has its P columns in lane set B (lane 15 = column 5)
         RicState<T> Vr;
         Vr.neg = inert;                                                    // segments' control pivots + the excess of the three combine blocks (pit_combine_inertia)
+        int okr;      // 1 good, -1 wrong inertia (no point in repeating the sweep), 0 breakdown
+        if constexpr (SHAPE != 0) {
+            // r25: the entries by row broadcast, one v_mov_b64_dpp each, wave-uniform in vector registers -- where the fp64 arithmetic wants them (a v_readlane pair
+            // leaves a scalar pair that the next two-operand instruction copies back).  All four DPP rows hold the same Vp / Wp / omp here: they read the same hand-off
+            // tiles and run the same combines, whose per-lane constants (comb_lane, lm, cz) depend on the lane's place in its row alone.
+            // The profile build counts the roots at which that does not hold (MPC_PROF_ROOT_ROWS; tests/test_gpu_boundary_root.py asserts none in every case).
+            T rt_p55, rt_p5, rt_s5[3], rt_om[3], rt_w[3][3];
+            MPC_PROF_ROOT_ROWS(Vp[5], omp, Wp[0], Wp[1], Wp[2]);
+            MPC_DPP_BLOCK_ROOT
+            Vr.P[5][5] = rt_p55;
+            Vr.p[5] = rt_p5;
+#pragma unroll
+            for (int b = 0; b < 3; ++b) { Vr.S[5][b] = rt_s5[b]; Vr.om[b] = rt_om[b]; }
+            Vr.W[0][0] = rt_w[0][0] - (fx(0) ? dc : T(0)); Vr.W[1][1] = rt_w[1][1] - (fx(1) ? dc : T(0)); Vr.W[2][2] = rt_w[2][2] - (fx(2) ? dc : T(0));
+            Vr.W[0][1] = Vr.W[1][0] = T(0.5) * (rt_w[0][1] + rt_w[1][0]);
+            Vr.W[0][2] = Vr.W[2][0] = T(0.5) * (rt_w[0][2] + rt_w[2][0]);
+            Vr.W[1][2] = Vr.W[2][1] = T(0.5) * (rt_w[1][2] + rt_w[2][1]);
+            okr = riccati_root_uniform<((SHAPE >> 3) & 1) != 0, SHAPE & 7>(Vr, dd_out, nu_out);      // (exchanges as uniform branches, flags read once: mpc_core.hpp)
+        } else {
         Vr.P[5][5] = rd_lane(Vp[5], 15);
         Vr.p[5] = rd_lane(Vp[5], 8);
         Vr.S[5][0] = rd_lane(Vp[5], 9); Vr.S[5][1] = rd_lane(Vp[5], 10); Vr.S[5][2] = rd_lane(Vp[5], 11);
@@ -463,9 +483,8 @@
             Vr.W[0][2] = Vr.W[2][0] = T(0.5) * (w02 + w20);
             Vr.W[1][2] = Vr.W[2][1] = T(0.5) * (w12 + w21);
         }
-        int okr;
-        if constexpr (SHAPE != 0) okr = riccati_root_shape<((SHAPE >> 3) & 1) != 0, SHAPE & 7>(Vr, dd_out, nu_out);
-        else okr = riccati_root(Vr, P, dd_out, nu_out);       // 1 good, -1 wrong inertia (no point in repeating the sweep), 0 breakdown
+        okr = riccati_root(Vr, P, dd_out, nu_out);
+        }
         MPC_DBG_ROOT("pit   ", okr, rd_lane(wpiv, 0))
         return okr;
     }
@@ -478,7 +497,54 @@
         // ---- boundary states (components 0..4; component 5 is dd) and costates, wave-uniform, left to right; they go to a small table behind the s = 0 tiles:
         //      TX + 5 s + i = state at b_{s+1}, TL + 5 s + i = costate at b_{s+1}
         const int TX = L.DX + 100, TL = L.DX + 115;
-        {
+        if constexpr (NSC != 0) {
+            // r25, fixed layout: ONE output component per lane.  A product's five results were five registers that every lane computed alike, a DPP instruction per term
+            // and component; here lane i of a row works on row i of the tile (w[j] = column j, word 10 i + j of the tile: one load per column behind one address), the
+            // running 5-vector is ONE register with component j in lane j, and a term of the state part is one v_fmac_f64_dpp with that register as the broadcast
+            // operand (MPC_DPP_BLOCK_BXT).  Lane i's chain is what acc[i] was, operand for operand and in the same order -- the product's factors change places --, so
+            // TX / TL hold the same bits.  The lanes behind the fifth of a row run along as copies of lane 4: same loads, same chain, same store (same word, same value),
+            // which spares the exec mask around the stores.  Where a lane's row starts comes packed in PC.fx.
+            const unsigned r8 = PC.fx >> 26;                                   // 8 min(c, 4)
+            const LdsT* tp = ldsb(r8 * 10u);                                   // row min(c, 4) of a tile that starts at word 0
+            LdsT* bp = ldsb(r8);                                               // word min(c, 4) of a 5-vector that starts at word 0
+            // (a segment's two tiles are 100 words in a row: behind ONE address of their own the twenty columns are within the reach of the two-word loads' 8-bit offsets;
+            //  left to fold the tile's place into the offsets the compiler forms an address per pair of columns.  The empty asm keeps the three addresses apart.)
+            //  The words were saved by other lanes (pit_save: every lane its own slot): what orders those stores before these loads is the sync() at the head of
+            //  pit_combine_inertia (fixed layout: behind the last combine) and the one behind backward_pit in solve().
+            auto cols = [&](int tile, int j0, int j1, T (&wx)[10], T (&wv)[10]) {
+                const LdsT* q = tp + tile;
+                asm("" : "+v"(q));
+#pragma unroll
+                for (int j = j0; j < 10; ++j) wx[j] = q[j];
+#pragma unroll
+                for (int j = j1; j < 10; ++j) wv[j] = q[50 + j];
+            };
+            auto tail = [&](const T (&w)[10], T cx) {                          // the terms in dd and nu: uniform coefficients, plain fmas in block_bx's order
+                cx = __builtin_fma(w[5], dd, cx);
+                cx = __builtin_fma(w[7], nu[0], cx); cx = __builtin_fma(w[8], nu[1], cx); cx = __builtin_fma(w[9], nu[2], cx);
+                return cx;
+            };
+            auto prod = [&](const T (&w)[10], T xv) {
+                T cx = w[6];
+                MPC_DPP_BLOCK_BXT
+                return tail(w, cx);
+            };
+            // all six tiles first (one LDS round trip), then the six products back to back
+            T XA0[10], VB0[10], XA1[10], VB1[10], XA2[10], VB2[10];
+            cols(pit_tile(0), 5, 0, XA0, VB0);                                 // (the first boundary state starts from xi = 0: no state columns)
+            cols(pit_tile(1), 0, 0, XA1, VB1);
+            cols(pit_tile(2), 0, 0, XA2, VB2);
+            const T x1 = tail(XA0, XA0[6]);
+            bp[TX] = x1;
+            bp[TL] = prod(VB0, x1);
+            const T x2 = prod(XA1, x1);
+            bp[TX + 5] = x2;
+            bp[TL + 5] = prod(VB1, x2);
+            const T x3 = prod(XA2, x2);
+            bp[TX + 10] = x3;
+            bp[TL + 10] = prod(VB2, x3);
+            sync();                                                            // (a word of the table is read by other lanes than the one that wrote it)
+        } else {
             const CombLane cla = comb_of<true>(PC, c, L.DX), clb = comb_of<false>(PC, c, L.DX);
             // all six tiles first (one LDS round trip), then the six products back to back
             T XA0[5], VB0[5], XA1[5], VB1[5], XA2[5], VB2[5];
@@ -512,7 +578,7 @@
         // ---- lane-parallel: fold the border multiplier of the stage's own segment and dd into the affine terms (as forward_states does with nu)
         for (int k = lane; k < n - 1; k += kWave) {
             int seg;
-            if constexpr (NSC != 0) seg = (int)(PC.fx >> 16);      // (a record of NSC < kWave stages: k is `lane`, the loop has one trip)
+            if constexpr (NSC != 0) seg = (int)((PC.fx >> 16) & 3u);      // (a record of NSC < kWave stages: k is `lane`, the loop has one trip)
             else seg = (k >= Lm ? 1 : 0) + (k >= 2 * Lm ? 1 : 0) + (k >= 3 * Lm ? 1 : 0);
             T m5[5];
 #pragma unroll

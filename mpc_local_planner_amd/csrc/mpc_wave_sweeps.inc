@@ -231,7 +231,7 @@
             Vr.W[1][2] = Vr.W[2][1] = T(0.5) * (w12 + w21);
         }
         bool okr;      // the (dt, nu) root system (mpc_core.hpp): with the shape known, the form without identity rows and selects
-        if constexpr (SHAPE != 0) okr = riccati_root_shape<((SHAPE >> 3) & 1) != 0, SHAPE & 7>(Vr, dd_out, nu_out) > 0;
+        if constexpr (SHAPE != 0) okr = riccati_root_uniform<((SHAPE >> 3) & 1) != 0, SHAPE & 7>(Vr, dd_out, nu_out) > 0;      // (the same system with its exchanges as uniform branches)
         else okr = riccati_root(Vr, P, dd_out, nu_out) > 0;
         MPC_DBG_ROOT("serial", okr, rd_lane(worst, 0))
         return okr;

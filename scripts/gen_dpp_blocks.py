@@ -5,6 +5,8 @@ and of the forward recurrence (DP-ALU DPP broadcasts, v_fmac_f64_dpp ... row_new
 Why blocks: the compiler cannot see the DPP operand inside inline asm, so it does not insert the wait states that the
 'VALU write -> DPP read' hazard needs (2).  Every block therefore starts with `s_nop 1` (any copy the register allocator
 places in front of the block is covered), and inside a block no DPP source is written less than 3 instructions earlier.
+(A block whose own text opens with two or more instructions WITHOUT a DPP operand -- T1: six v_mul_f64, CWV: five v_mov_b64 -- would not need the pad: whatever was written
+in front of it is three instructions old at its first DPP read.  Dropping it there was tried in r25 and could not be told from noise: profiles/r25_wave_uniform_sweeps.md.)
 usage: python scripts/gen_dpp_blocks.py > mpc_local_planner_amd/csrc/mpc_dpp_blocks.inc"""
 
 DPP = " row_mask:0xf bank_mask:0xf"
@@ -194,6 +196,31 @@ def block_bx(sfx, Lc, first):
     return emit("bx", L, outs, ins, sfx)
 
 
+def block_bxt(sfx):
+    """the same product with ONE output component per lane (fixed-layout kernels): w{j} = column j of the tile with row i in lane i, xv = the running 5-vector with
+    component j in lane j, c = the tile's constant column on entry;  c_i += sum_j xv[lane j] w{j}_i  in block_bx's order of j.  Lane i's chain is block_bx's acc_i operand
+    for operand (the product's factors change places, no more); the dd / nu terms follow in plain code, their coefficients are wave-uniform.  xv is not written here."""
+    L = ["s_nop 1"] + [fmac(sfx, "c", "xv", f"w{j}", j) for j in range(5)]
+    outs = [("c", "+&v", "cx")]
+    ins = [("xv", "xv")] + [(f"w{j}", f"w[{j}]") for j in range(5)]
+    return emit("bxt", L, outs, ins, sfx)
+
+
+def block_root(sfx):
+    """the 17 entries of the root system behind the partitioned sweep's last combine, each left wave-uniform in a VECTOR register by one row broadcast of the register that
+    holds it (the four DPP rows hold the same values there: every row runs the combines on the same tiles with per-lane constants that depend on the lane's place in its
+    row alone).  The value function has its P columns in lane set B: lane 15 = column 5."""
+    movd = "v_mov_b64_dpp" if sfx == "f64" else "v_mov_b32_dpp"
+    L = ["s_nop 1", f"{movd} %[p55], %[v5] row_newbcast:15{DPP}", f"{movd} %[pp5], %[v5] row_newbcast:8{DPP}"]
+    L += [f"{movd} %[s5{b}], %[v5] row_newbcast:{9 + b}{DPP}" for b in range(3)]
+    L += [f"{movd} %[om{b}], %[om] row_newbcast:{9 + b}{DPP}" for b in range(3)]
+    L += [f"{movd} %[w{a}{b}], %[wp{a}] row_newbcast:{9 + b}{DPP}" for a in range(3) for b in range(3)]
+    outs = [("p55", "=&v", "rt_p55"), ("pp5", "=&v", "rt_p5")] + [(f"s5{b}", "=&v", f"rt_s5[{b}]") for b in range(3)] + [(f"om{b}", "=&v", f"rt_om[{b}]") for b in range(3)]
+    outs += [(f"w{a}{b}", "=&v", f"rt_w[{a}][{b}]") for a in range(3) for b in range(3)]
+    ins = [("v5", "Vp[5]"), ("om", "omp")] + [(f"wp{a}", f"Wp[{a}]") for a in range(3)]
+    return emit("root", L, outs, ins, sfx)
+
+
 print("// GENERATED by scripts/gen_dpp_blocks.py -- do not edit.  Inline-asm DPP blocks (see the generator for the hazard rules).")
 for nm, fn, sig in (("MPC_DPP_BLOCK_T1", block_t1, ""), ("MPC_DPP_BLOCK_H", block_h, ""), ("MPC_DPP_BLOCK_R", block_r, ""),
                     ("MPC_DPP_BLOCK_V", block_v, ""), ("MPC_DPP_BLOCK_FWD", block_fwd, ""),
@@ -202,7 +229,8 @@ for nm, fn, sig in (("MPC_DPP_BLOCK_T1", block_t1, ""), ("MPC_DPP_BLOCK_H", bloc
                     ("MPC_DPP_BLOCK_CU_A", lambda x: block_cu(x, LA), ""), ("MPC_DPP_BLOCK_CU_B", lambda x: block_cu(x, LB), ""),
                     ("MPC_DPP_BLOCK_CRA", block_cra, ""), ("MPC_DPP_BLOCK_CWN", block_cwn, ""),
                     ("MPC_DPP_BLOCK_BX_A", lambda x: block_bx(x, LA, False), ""), ("MPC_DPP_BLOCK_BX_B", lambda x: block_bx(x, LB, False), ""),
-                    ("MPC_DPP_BLOCK_BX0_A", lambda x: block_bx(x, LA, True), ""), ("MPC_DPP_BLOCK_BX0_B", lambda x: block_bx(x, LB, True), "")):
+                    ("MPC_DPP_BLOCK_BX0_A", lambda x: block_bx(x, LA, True), ""), ("MPC_DPP_BLOCK_BX0_B", lambda x: block_bx(x, LB, True), ""),
+                    ("MPC_DPP_BLOCK_BXT", block_bxt, ""), ("MPC_DPP_BLOCK_ROOT", block_root, "")):
     txt = "if constexpr (sizeof(T) == 8) {\n" + fn("f64") + "} else {\n" + fn("f32") + "}"
     print(f"#define {nm} \\")
     print(" \\\n".join(txt.split("\n")))

@@ -312,6 +312,32 @@ LINE_PROTOTYPES = {
 }
 
 
+class MpcWindowParams(C.Structure):
+    """struct mpc_window_params (include/mpc_costmap_window.h); field-for-field."""
+    _fields_ = [
+        ("map_origin", C.c_double * 2),
+        ("map_resolution", C.c_double),
+        ("lattice_anchor", C.c_double * 2),
+        ("inscribed_radius", C.c_double),
+        ("inflation_radius", C.c_double),
+        ("cost_scaling_factor", C.c_double),
+        ("map_size_x", C.c_int32),
+        ("map_size_y", C.c_int32),
+        ("outside_value", C.c_int32),
+        ("inflate_unknown", C.c_int32),
+    ]
+
+
+# ---- the functions of include/mpc_costmap_window.h, in the same form.  tests/test_costmap_window_abi.py holds every row to its declaration.
+# s, B, map, params, robot_pose, size_x, size_y, resolution, cost, origin, info
+_WINDOW = (_rc, [_p, _i, _p, C.POINTER(MpcWindowParams), _p, _i, _i, _d, _p, _p, _p])
+
+WINDOW_PROTOTYPES = {
+    "mpc_window_params_defaults": (None, [C.POINTER(MpcWindowParams), _d, _i, _i]),             # p, map_resolution, map_size_x, map_size_y
+    "mpc_costmap_window": _WINDOW, "mpc_costmap_window_device": _WINDOW,
+}
+
+
 def _diag_offdiag(w, dim):
     """a weight given as its diagonal or as a full dim x dim matrix -> (diagonal, off-diagonal terms (0,1)[, (0,2), (1,2)] of the symmetric part)"""
     rows = [list(r) if hasattr(r, "__len__") else None for r in w]

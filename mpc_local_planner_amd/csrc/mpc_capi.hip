@@ -15,6 +15,7 @@
 #include "../../include/mpc_fleet.h"
 #include "../../include/mpc_costmap_clusters.h"
 #include "../../include/mpc_costmap_lines.h"
+#include "../../include/mpc_costmap_window.h"
 #include "mpc_core.hpp"
 #include "mpc_problem.hpp"
 #include "mpc_launch_plan.hpp"
@@ -29,6 +30,7 @@
 #include "mpc_fleet_obstacles.hpp"
 #include "mpc_costmap_clusters.hpp"
 #include "mpc_costmap_lines.hpp"
+#include "mpc_costmap_window.hpp"
 
 namespace {
 
@@ -1485,6 +1487,92 @@ int mpc_costmap_to_lines(mpc_solver* s, int32_t B, const uint8_t* cost, int32_t 
     if (to_lines_error(s, cost, size_x, size_y, resolution, origin, robot_pose, params, n_obstacles, n_vertices, vertices)) return MPC_EINVAL;
     return costmap_shapes_host(s, "mpc_costmap_to_lines", B, cost, size_x, size_y, resolution, origin, robot_pose, params, n_obstacles, n_vertices, vertices, radius, velocity,
                                dropped, info, mpc_costmap_to_lines_device);
+}
+
+}  // extern "C"
+
+// ---- one shared map -> the local costmap windows of a batch (mpc_costmap_window.hpp; declared in include/mpc_costmap_window.h)
+
+// the argument checks of both variants, in the order of rule 6: true with mpc_last_error set when the call is refused; r: rule 3's radius in cells
+static bool window_error(const char* who, const mpc_solver* s, const void* map, const mpc_window_params* p, const void* robot_pose, int32_t size_x, int32_t size_y,
+                         double resolution, const void* cost, const void* origin, int& r) {
+    auto pos_finite = [](double v) { return v > 0.0 && std::isfinite(v); };
+    auto nonneg_finite = [](double v) { return v >= 0.0 && std::isfinite(v); };
+    if (!s || !map || !p || !robot_pose || !cost || !origin) return costmap_no(who, "null argument (map, params, robot_pose, cost, origin)");
+    if (size_x < 1 || size_y < 1 || size_x > mpc::kCwMaxSize || size_y > mpc::kCwMaxSize || (long long)size_x * size_y > mpc::kCwMaxCells)
+        return costmap_no(who, "bad window geometry (1 <= size_x, size_y <= 4096, size_x * size_y <= 2^20)");
+    if (!pos_finite(resolution) || !pos_finite(p->map_resolution)) return costmap_no(who, "resolution and map_resolution have to be positive and finite");
+    if (p->map_size_x < 1 || p->map_size_y < 1 || (long long)p->map_size_x * p->map_size_y > 2147483647LL) return costmap_no(who, "bad map size (at least 1 x 1, at most 2^31 - 1 bytes)");
+    r = mpc::cw_cell_radius(p->inflation_radius, resolution);
+    if (r < 0) return costmap_no(who, "inflation_radius has to be at most 32 cells of the window");
+    if (p->outside_value != 0 && p->outside_value != 255) return costmap_no(who, "outside_value has to be 0 or 255");
+    if (!nonneg_finite(p->inscribed_radius)) return costmap_no(who, "inscribed_radius has to be at least 0 and finite");
+    return costmap_no(who, nonneg_finite(p->cost_scaling_factor) ? nullptr : "cost_scaling_factor has to be at least 0 and finite");
+}
+
+extern "C" {
+
+void mpc_window_params_defaults(mpc_window_params* p, double map_resolution, int32_t map_size_x, int32_t map_size_y) {
+    if (!p) return;
+    p->map_origin[0] = p->map_origin[1] = 0.0;
+    p->map_resolution = map_resolution;
+    p->lattice_anchor[0] = p->lattice_anchor[1] = 0.0;
+    p->inscribed_radius = 0.0;
+    p->inflation_radius = 0.0;
+    p->cost_scaling_factor = 10.0;
+    p->map_size_x = map_size_x; p->map_size_y = map_size_y;
+    p->outside_value = 0;
+    p->inflate_unknown = 0;
+}
+
+int mpc_costmap_window_device(mpc_solver* s, int32_t B, const uint8_t* d_map, const mpc_window_params* params, const double* d_robot_pose, int32_t size_x,
+                              int32_t size_y, double resolution, uint8_t* d_cost, double* d_origin, int32_t* d_info) {
+    g_err[0] = 0;
+    int r = 0;
+    if (window_error("mpc_costmap_window", s, d_map, params, d_robot_pose, size_x, size_y, resolution, d_cost, d_origin, r)) return MPC_EINVAL;
+    if (B <= 0) return MPC_OK;
+    if (const int rc = refused(s, B, REF_MAX_BATCH, "mpc_costmap_window")) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    mpc::WindowArgs a;
+    memset(&a, 0, sizeof(a));
+    a.map = d_map; a.pose = d_robot_pose; a.cost = d_cost; a.origin = d_origin; a.info = d_info;
+    a.p = {params->map_origin[0], params->map_origin[1], params->map_resolution, params->lattice_anchor[0], params->lattice_anchor[1], resolution,
+           params->map_size_x, params->map_size_y, params->outside_value, params->inflate_unknown ? 1 : 0, r};
+    a.W = size_x; a.H = size_y;
+    a.tiles_x = (size_x + mpc::kCwTileX - 1) / mpc::kCwTileX;
+    a.ntiles = a.tiles_x * ((size_y + mpc::kCwTileY - 1) / mpc::kCwTileY);
+    uint8_t table[4 * mpc::kCwTableWords] = {0};      // rule 4: on the host
+    mpc::cw_table(resolution, params->inscribed_radius, params->cost_scaling_factor, r, table);
+    memcpy(a.table, table, sizeof(a.table));
+    // between the two events mpc_last_costmap_ms reads: the counts cleared (the tiles of an instance add to them), then the tiles, at most 2^22 workgroups a launch
+    HIP_TRY(hipEventRecord(s->cev0, s->stream));
+    if (d_info) HIP_TRY(hipMemsetAsync(d_info, 0, (size_t)B * 16, s->stream));
+    const int per = (1 << 22) / a.ntiles;      // ntiles <= 2^20 / 64 + 2 * 64 + 1
+    for (int b0 = 0; b0 < B; b0 += per) {
+        a.b0 = b0;
+        const int nb = B - b0 < per ? B - b0 : per;
+        hipLaunchKernelGGL(mpc::costmap_window_kernel, dim3((unsigned)nb * (unsigned)a.ntiles), dim3(mpc::kCwThreads), 0, s->stream, a);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(s->cev1, s->stream));
+    s->ctimed = true;
+    return MPC_OK;
+}
+
+int mpc_costmap_window(mpc_solver* s, int32_t B, const uint8_t* map, const mpc_window_params* params, const double* robot_pose, int32_t size_x, int32_t size_y,
+                       double resolution, uint8_t* cost, double* origin, int32_t* info) {
+    g_err[0] = 0;
+    int r = 0;
+    if (window_error("mpc_costmap_window", s, map, params, robot_pose, size_x, size_y, resolution, cost, origin, r)) return MPC_EINVAL;
+    if (B <= 0) return MPC_OK;
+    if (const int rc = refused(s, B, REF_MAX_BATCH, "mpc_costmap_window")) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t nb = (size_t)B;
+    const mpc::StagePiece pc[5] = {stage_in(map, (size_t)params->map_size_x * params->map_size_y), stage_in(robot_pose, nb * 24), stage_out(cost, nb * size_x * size_y),
+                                   stage_out(origin, nb * 16), stage_out(info, nb * 16)};
+    return staged_call(s, "mpc_costmap_window", true, true, pc, 5, [&](void** d) -> int {
+        return mpc_costmap_window_device(s, B, (const uint8_t*)d[0], params, (const double*)d[1], size_x, size_y, resolution, (uint8_t*)d[2], (double*)d[3], (int32_t*)d[4]);
+    });
 }
 
 }  // extern "C"

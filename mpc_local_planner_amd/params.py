@@ -491,6 +491,86 @@ def line_params_from_options(plugin_options: dict, converter_params: dict | None
     return c, notes
 
 
+INFLATION_LAYER = "costmap_2d::InflationLayer"
+
+
+def _inscribed_radius(footprint, padding: float) -> float:
+    """costmap_2d::padFootprint, then the min_dist of costmap_2d::calculateMinAndMaxDistances: the smallest distance from the origin to a vertex or an edge of the
+    polygon (restated from costmap_2d's published footprint.cpp; it is not part of the reference's tree)"""
+    sign0 = lambda v: (v > 0) - (v < 0)
+    pts = [(float(x) + sign0(x) * padding, float(y) + sign0(y) * padding) for x, y in footprint]
+
+    def to_segment(ax, ay, bx, by):      # costmap_2d::distanceToLine(0, 0, a, b)
+        dx, dy = bx - ax, by - ay
+        l2 = dx * dx + dy * dy
+        t = 0.0 if l2 == 0.0 else min(max((-ax * dx - ay * dy) / l2, 0.0), 1.0)
+        return math.hypot(ax + t * dx, ay + t * dy)
+
+    return min(min(math.hypot(*a), to_segment(*a, *b)) for a, b in zip(pts, pts[1:] + pts[:1]))
+
+
+def window_params_from_costmap_yaml(local_costmap: dict, common: dict | None, map_yaml: dict, map_shape):
+    """struct mpc_window_params (mpc_costmap_window*, BatchSolver.costmap_window_device) and the window's size in cells, from the parameter trees of a local costmap
+    (cfg/<robot>/local_costmap_params.yaml, with or without its `local_costmap` key), of the common block loaded into the same namespace
+    (cfg/<robot>/costmap_common_params.yaml; the local file's keys win) and of the map server's file (maps/<name>.yaml), for a map of map_shape = (rows, columns).
+    width, height and resolution are needed and rolling_window has to be true: anything else is ParamNotImplemented, as is a map with a yaw.
+    size = ((unsigned)(width / resolution), (unsigned)(height / resolution)), as Costmap2DROS sizes the master grid.  Inflation is on only when a
+    costmap_2d::InflationLayer is among the `plugins`: inflation_radius (0.55) and cost_scaling_factor (10) and inflate_unknown (false) from the block of its name; the
+    shipped local costmaps list a StaticLayer and an ObstacleLayer, so theirs is off.  inscribed_radius: robot_radius, else the padded footprint polygon's
+    (footprint_padding, 0.01) by costmap_2d::calculateMinAndMaxDistances, else 0.  outside_value: 255 iff the costmap's own track_unknown_space (false), the default
+    value of the master grid.  Returns (params, (size_x, size_y))."""
+    local = local_costmap.get("local_costmap", local_costmap) if isinstance(local_costmap.get("local_costmap", None), dict) else local_costmap
+    tree = {**(common or {}), **local}
+    for key in ("width", "height", "resolution"):
+        if not _is_number(tree.get(key)) or not tree[key] > 0:
+            raise ParamNotImplemented(f"local costmap: {key} has to be a positive number (mpc_costmap_window cuts a window of a fixed size)")
+    if tree.get("rolling_window") is not True:
+        raise ParamNotImplemented("local costmap: rolling_window has to be true (mpc_costmap_window moves the window with the robot)")
+    origin = list(map_yaml.get("origin", (0.0, 0.0, 0.0))) + [0.0] * 3
+    if float(origin[2]) != 0.0:
+        raise ParamNotImplemented("map: an origin with a yaw (mpc_costmap_window samples in one frame, without a transform)")
+    if not _is_number(map_yaml.get("resolution")) or not map_yaml["resolution"] > 0:
+        raise ParamError("map: resolution has to be a positive number")
+    res = float(tree["resolution"])
+    c = A.MpcWindowParams()
+    c.map_origin[0], c.map_origin[1] = float(origin[0]), float(origin[1])
+    c.map_resolution = float(map_yaml["resolution"])
+    c.lattice_anchor[0] = c.lattice_anchor[1] = 0.0
+    c.map_size_y, c.map_size_x = int(map_shape[0]), int(map_shape[1])
+    if _is_number(tree.get("robot_radius")):
+        c.inscribed_radius = float(tree["robot_radius"])
+    elif isinstance(tree.get("footprint"), (list, tuple)) and len(tree["footprint"]) >= 3:
+        c.inscribed_radius = _inscribed_radius(tree["footprint"], float(tree.get("footprint_padding", 0.01)))
+    else:
+        c.inscribed_radius = 0.0
+    c.inflation_radius, c.cost_scaling_factor, c.inflate_unknown = 0.0, 10.0, 0
+    for plugin in tree.get("plugins") or []:
+        if isinstance(plugin, dict) and plugin.get("type") == INFLATION_LAYER:
+            block = tree.get(plugin.get("name")) if isinstance(tree.get(plugin.get("name")), dict) else {}
+            if block.get("enabled", True):
+                c.inflation_radius = float(block.get("inflation_radius", 0.55))
+                c.cost_scaling_factor = float(block.get("cost_scaling_factor", 10.0))
+                c.inflate_unknown = 1 if block.get("inflate_unknown", False) else 0
+    c.outside_value = 255 if tree.get("track_unknown_space", False) else 0
+    return c, (int(float(tree["width"]) / res), int(float(tree["height"]) / res))
+
+
+def static_layer_costs(occupancy, lethal_threshold=100, unknown_cost_value=-1, track_unknown_space=True, trinary_costmap=True):
+    """costmap_2d::StaticLayer::interpretValue in numpy (restated from costmap_2d's published static_layer.cpp): a map server's occupancy values (-1 unknown,
+    0 .. 100) -> the costmap bytes mpc_costmap_window's map holds.  The value is read as an unsigned char, as the layer does: the unknown value is 255 with
+    track_unknown_space and 0 without it, a value at or above lethal_threshold (clamped to [0, 100]) is 254, every other one is 0 when trinary_costmap, else
+    (unsigned char)(value / lethal_threshold * 254)."""
+    import numpy as np
+    v = (np.asarray(occupancy).astype(np.int64) & 0xFF)
+    lethal = max(min(int(lethal_threshold), 100), 0)
+    unknown = int(unknown_cost_value) & 0xFF
+    with np.errstate(divide="ignore", invalid="ignore"):
+        scaled = np.zeros(v.shape, np.int64) if trinary_costmap else np.nan_to_num(v.astype(np.float64) / np.float64(lethal) * 254.0).astype(np.int64)
+    out = np.where(v >= lethal, 254, scaled)
+    out = np.where(v == unknown, 255 if track_unknown_space else 0, out)
+    return out.astype(np.uint8)
+
+
 def _is_number(v) -> bool:
     return isinstance(v, (int, float)) and not isinstance(v, bool)
 

@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._abi import MpcClusterParams, MpcConfig, MpcLineParams, MpcCycleParams, MpcEvalOut, MpcObstacles, MpcPlanParams, MpcPool, MpcPoolParams, MPC_OK
+from ._abi import MpcClusterParams, MpcConfig, MpcLineParams, MpcCycleParams, MpcEvalOut, MpcObstacles, MpcPlanParams, MpcPool, MpcPoolParams, MpcWindowParams, MPC_OK
 
 
 class MpcError(RuntimeError):
@@ -502,6 +502,39 @@ class BatchSolver:
         mpc_costmap_to_obstacles_device and mpc_costmap_to_polygons_device stand; slots at or above the new n_obstacles keep their bytes"""
         self._check(self._lib.mpc_costmap_to_lines_device(self._h, int(B), _dev(cost), int(size_x), int(size_y), float(resolution), _dev(origin), _dev(robot_pose),
                                                           C.byref(params), *map(_dev, (n_obstacles, n_vertices, vertices, radius, velocity, dropped, info))))
+
+    def window_params(self, map_resolution, map_shape, **fields) -> MpcWindowParams:
+        """mpc_window_params with the library's defaults (mpc_window_params_defaults) for a map of map_shape = (map_size_y, map_size_x) cells, then the given fields
+        (map_origin and lattice_anchor as pairs)"""
+        p = MpcWindowParams()
+        self._lib.mpc_window_params_defaults(C.byref(p), float(map_resolution), int(map_shape[1]), int(map_shape[0]))
+        for k, v in fields.items():
+            if k not in dict(MpcWindowParams._fields_):
+                raise ValueError(f"mpc_window_params has no field {k}")
+            setattr(p, k, (C.c_double * 2)(*map(float, v)) if k in ("map_origin", "lattice_anchor") else v)
+        return p
+
+    def costmap_window(self, map_cost, params: MpcWindowParams, robot_pose, size, resolution):
+        """One shared map -> the local costmap window of every robot (mpc_costmap_window, include/mpc_costmap_window.h): the window's origin from the pose alone, on the
+        lattice of the window's resolution; every cell the map byte under its centre (outside_value off the map); optionally inflated from the exact nearest lethal
+        cell, the r cells around the window included.  map_cost: uint8 (map_size_y, map_size_x) in costmap values; robot_pose (B, 3); size = (size_x, size_y) in cells.
+        Returns (cost uint8 (B, size_y, size_x), origin (B, 2), info (B, 4) = window cells inside the map, lethal cells, cells inflation changed, lethal cells in the
+        halo only): cost and origin are what the costmap converters, controller_step and check_feasibility take."""
+        m = np.ascontiguousarray(map_cost, dtype=np.uint8)
+        if m.shape != (params.map_size_y, params.map_size_x):
+            raise ValueError(f"map_cost has shape {m.shape}, params say {(params.map_size_y, params.map_size_x)}")
+        pose = np.ascontiguousarray(robot_pose, dtype=np.float64).reshape(-1, 3)
+        B, (sx, sy) = pose.shape[0], (int(size[0]), int(size[1]))
+        cost, origin, info = np.zeros((B, max(sy, 0), max(sx, 0)), np.uint8), np.zeros((B, 2)), np.zeros((B, 4), np.int32)
+        self._check(self._lib.mpc_costmap_window(self._h, B, _addr(m), C.byref(params), _addr(pose), sx, sy, float(resolution), _addr(cost), _addr(origin), _addr(info)))
+        return cost, origin, info
+
+    def costmap_window_device(self, B: int, map_cost: int, params: MpcWindowParams, robot_pose: int, size_x: int, size_y: int, resolution: float, cost: int, origin: int,
+                              info: Optional[int] = None) -> None:
+        """mpc_costmap_window_device: the same with device addresses (ints), asynchronous on the solver's stream, in front of the costmap converters of the fleet
+        cycle; cost and origin are written in full"""
+        self._check(self._lib.mpc_costmap_window_device(self._h, int(B), _dev(map_cost), C.byref(params), _dev(robot_pose), int(size_x), int(size_y), float(resolution),
+                                                        _dev(cost), _dev(origin), _dev(info)))
 
     def last_costmap_ms(self) -> float:
         """device milliseconds of the most recent costmap step (mpc_last_costmap_ms), 0 when there has been none"""

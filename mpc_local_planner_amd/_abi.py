@@ -1,4 +1,5 @@
-"""ctypes mirror of include/mpc_hip.h (its structs, its enum values and, in PROTOTYPES, its functions).
+"""ctypes mirror of the C ABI: for every header under include/, its structs, its enum values and, in a prototype table, its functions.
+HEADERS, below the tables, says which table and which mirrors belong to which header.
 
 Pure data definitions -- shared by the product binding (mpc_local_planner_amd/_lib.py)
 and by tests.  No solver code here.
@@ -184,8 +185,9 @@ PLAN_GOAL_REACHED, PLAN_EMPTY, PLAN_TRUNCATED, PLAN_VIA_DROPPED, PLAN_GOAL_INJEC
 CMD_SUCCESS, CMD_GOAL_REACHED, CMD_PLAN_EMPTY, CMD_SOLVE_FAILED, CMD_INFEASIBLE, CMD_NOT_FINITE = 0, 1, 2, 3, 4, 5
 
 
-# ---- the functions of include/mpc_hip.h: name -> (restype, argtypes), the one statement of the C ABI on the Python side.  _lib.load() assigns them, _lib.EXPORTS is
-# the names, tests/test_abi.py holds every row to the header's declaration.  A host / device pair shares one signature object.
+# ---- the functions, one table per header: name -> (restype, argtypes), the one statement of the C ABI on the Python side.  A host / device pair shares one signature
+# object.  HEADERS (below the tables) ties each table and each struct mirror to its header; _lib.load() binds every table of it to the one library, and tests/test_abi.py
+# holds every row to its header's declaration and every mirror to the C compiler's layout.  PROTOTYPES is include/mpc_hip.h alone, and _lib.EXPORTS is its names.
 _p = C.c_void_p      # a raw address (host numpy buffer or device pointer) or the opaque mpc_solver*
 _i, _d, _rc = C.c_int32, C.c_double, C.c_int
 _SOLVE = (_rc, [_p, _i] + [_p] * 7 + [_p] + [_p] * 5)      # s, B, x0, xf, u_prev, dt_prev, x_init, u_init, dt_init, const mpc_obstacles*, x_out, u_out, dt_out, status, iters
@@ -256,8 +258,7 @@ class MpcPoolParams(C.Structure):
     ]
 
 
-# ---- the functions of include/mpc_fleet.h, in the same form.  They are exported by the same library and bound by _lib.load(), but are no part of PROTOTYPES / _lib.EXPORTS:
-# those mirror include/mpc_hip.h alone.  tests/test_fleet_abi.py holds every row to its declaration.
+# ---- include/mpc_fleet.h
 # s, B, pool, robot_pose, self_index, params, n_obstacles, n_vertices, vertices, radius, velocity, dropped, n_taken
 _FROM_POOL = (_rc, [_p, _i, C.POINTER(MpcPool), _p, _p, C.POINTER(MpcPoolParams)] + [_p] * 7)
 # s, B, robot_pose, x, dt, status, robot_radius, robot_radius per robot, pool_offset, pool_n_vertices, pool_vertices, pool_radius, pool_velocity
@@ -278,8 +279,7 @@ class MpcClusterParams(C.Structure):
     ]
 
 
-# ---- the functions of include/mpc_costmap_clusters.h, in the same form: exported by the same library, bound by _lib.load(), no part of PROTOTYPES / _lib.EXPORTS.
-# tests/test_costmap_clusters_abi.py holds every row to its declaration.
+# ---- include/mpc_costmap_clusters.h
 # s, B, cost, size_x, size_y, resolution, origin, robot_pose, params, n_obstacles, n_vertices, vertices, radius, velocity, dropped, info
 _TO_POLYGONS = (_rc, [_p, _i, _p, _i, _i, _d, _p, _p, C.POINTER(MpcClusterParams)] + [_p] * 7)
 
@@ -302,7 +302,7 @@ class MpcLineParams(C.Structure):
     ]
 
 
-# ---- the functions of include/mpc_costmap_lines.h, in the same form.  tests/test_costmap_lines_abi.py holds every row to its declaration.
+# ---- include/mpc_costmap_lines.h
 # s, B, cost, size_x, size_y, resolution, origin, robot_pose, params, n_obstacles, n_vertices, vertices, radius, velocity, dropped, info
 _TO_LINES = (_rc, [_p, _i, _p, _i, _i, _d, _p, _p, C.POINTER(MpcLineParams)] + [_p] * 7)
 
@@ -328,13 +328,24 @@ class MpcWindowParams(C.Structure):
     ]
 
 
-# ---- the functions of include/mpc_costmap_window.h, in the same form.  tests/test_costmap_window_abi.py holds every row to its declaration.
+# ---- include/mpc_costmap_window.h
 # s, B, map, params, robot_pose, size_x, size_y, resolution, cost, origin, info
 _WINDOW = (_rc, [_p, _i, _p, C.POINTER(MpcWindowParams), _p, _i, _i, _d, _p, _p, _p])
 
 WINDOW_PROTOTYPES = {
     "mpc_window_params_defaults": (None, [C.POINTER(MpcWindowParams), _d, _i, _i]),             # p, map_resolution, map_size_x, map_size_y
     "mpc_costmap_window": _WINDOW, "mpc_costmap_window_device": _WINDOW,
+}
+
+
+# ---- the boundary, whole: header under include/ -> (its prototype table, {C struct: its mirror}).  A new header is one row here.
+HEADERS = {
+    "mpc_hip.h": (PROTOTYPES, {"mpc_config": MpcConfig, "mpc_obstacles": MpcObstacles, "mpc_eval_out": MpcEvalOut, "mpc_cycle_params": MpcCycleParams,
+                               "mpc_plan_params": MpcPlanParams}),
+    "mpc_fleet.h": (FLEET_PROTOTYPES, {"mpc_pool": MpcPool, "mpc_pool_params": MpcPoolParams}),
+    "mpc_costmap_clusters.h": (CLUSTER_PROTOTYPES, {"mpc_cluster_params": MpcClusterParams}),
+    "mpc_costmap_lines.h": (LINE_PROTOTYPES, {"mpc_line_params": MpcLineParams}),
+    "mpc_costmap_window.h": (WINDOW_PROTOTYPES, {"mpc_window_params": MpcWindowParams}),
 }
 
 

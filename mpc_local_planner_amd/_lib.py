@@ -11,7 +11,7 @@ import shutil
 import subprocess
 
 from . import _build
-from ._abi import CLUSTER_PROTOTYPES, FLEET_PROTOTYPES, LINE_PROTOTYPES, PROTOTYPES, WINDOW_PROTOTYPES
+from ._abi import HEADERS, PROTOTYPES
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.path.join(CSRC, "libmpc_hip.so")
@@ -91,9 +91,7 @@ _lib = None
 
 
 def load() -> C.CDLL:
-    """dlopen the C-ABI library and declare the prototypes of include/mpc_hip.h (_abi.PROTOTYPES) and include/mpc_fleet.h (_abi.FLEET_PROTOTYPES)
-    and include/mpc_costmap_clusters.h (_abi.CLUSTER_PROTOTYPES) and include/mpc_costmap_lines.h (_abi.LINE_PROTOTYPES) and
-    include/mpc_costmap_window.h (_abi.WINDOW_PROTOTYPES), once."""
+    """dlopen the C-ABI library and declare the prototypes of every header of _abi.HEADERS, once."""
     global _lib
     if _lib is not None:
         return _lib
@@ -103,8 +101,9 @@ def load() -> C.CDLL:
             f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
     lib = C.CDLL(path)
-    for name, (restype, argtypes) in {**PROTOTYPES, **FLEET_PROTOTYPES, **CLUSTER_PROTOTYPES, **LINE_PROTOTYPES, **WINDOW_PROTOTYPES}.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = restype, argtypes
+    for table, _ in HEADERS.values():
+        for name, (restype, argtypes) in table.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib

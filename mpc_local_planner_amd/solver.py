@@ -102,10 +102,10 @@ def _dev_obstacles(obstacles):
     return C.byref(MpcObstacles(*(tuple(obstacles) + (None,) * (5 - len(obstacles)))))
 
 
-def _params(lib, name, struct, fields):
-    """a parameter struct with the library's defaults (<name>_defaults), then the given fields"""
+def _params(name, struct, defaults, fields):
+    """a parameter struct `name` with the library's defaults (defaults(byref(p)): the caller's <name>_defaults call, whose other arguments differ), then the given fields"""
     p = struct()
-    getattr(lib, name + "_defaults")(C.byref(p))
+    defaults(C.byref(p))
     for k, v in fields.items():
         if k not in dict(struct._fields_):
             raise ValueError(f"{name} has no field {k}")
@@ -212,7 +212,7 @@ class BatchSolver:
 
     def cycle_params(self, **fields) -> MpcCycleParams:
         """mpc_cycle_params with the reference's in-code defaults (mpc_cycle_params_defaults), then the given fields"""
-        return _params(self._lib, "mpc_cycle_params", MpcCycleParams, fields)
+        return _params("mpc_cycle_params", MpcCycleParams, self._lib.mpc_cycle_params_defaults, fields)
 
     def controller_step(self, params: MpcCycleParams, plan, n_plan, x_feedback=None, feedback_age=None, reset=None, u_prev=None, dt_prev=None, obstacles=None):
         """One whole Controller::step cycle for B robots (mpc_controller_step_batch; src/controller.cpp:111-179): state estimate, re-initialisation decision, initial
@@ -274,7 +274,7 @@ class BatchSolver:
 
     def plan_params(self, **fields) -> MpcPlanParams:
         """mpc_plan_params with the reference's in-code defaults (mpc_plan_params_defaults), then the given fields"""
-        return _params(self._lib, "mpc_plan_params", MpcPlanParams, fields)
+        return _params("mpc_plan_params", MpcPlanParams, self._lib.mpc_plan_params_defaults, fields)
 
     def plan_inputs(self, params: MpcPlanParams, global_plan, n_global, robot_pose, plan_stride: int, plan_begin=None, via_points: bool = False) -> PlanInputs:
         """What the plugin prepares before Controller::step, for B robots (mpc_plan_inputs_batch; src/mpc_local_planner_ros.cpp:294-354): prune, select, via-points,
@@ -322,13 +322,7 @@ class BatchSolver:
 
     def pool_params(self, **fields) -> MpcPoolParams:
         """mpc_pool_params with the library's defaults (mpc_pool_params_defaults: reach = cfg.cutoff_dist, min_speed = 0.001, append = 1), then the given fields"""
-        p = MpcPoolParams()
-        self._lib.mpc_pool_params_defaults(self._h, C.byref(p))
-        for k, v in fields.items():
-            if k not in dict(MpcPoolParams._fields_):
-                raise ValueError(f"mpc_pool_params has no field {k}")
-            setattr(p, k, v)
-        return p
+        return _params("mpc_pool_params", MpcPoolParams, lambda p: self._lib.mpc_pool_params_defaults(self._h, p), fields)
 
     def obstacles_from_pool(self, pool, robot_pose, self_index=None, params=None, obstacles=None):
         """Obstacles that are not in the costmap, for B robots (mpc_obstacles_from_pool, include/mpc_fleet.h): the entries of a shared pool within params.reach of each
@@ -506,13 +500,9 @@ class BatchSolver:
     def window_params(self, map_resolution, map_shape, **fields) -> MpcWindowParams:
         """mpc_window_params with the library's defaults (mpc_window_params_defaults) for a map of map_shape = (map_size_y, map_size_x) cells, then the given fields
         (map_origin and lattice_anchor as pairs)"""
-        p = MpcWindowParams()
-        self._lib.mpc_window_params_defaults(C.byref(p), float(map_resolution), int(map_shape[1]), int(map_shape[0]))
-        for k, v in fields.items():
-            if k not in dict(MpcWindowParams._fields_):
-                raise ValueError(f"mpc_window_params has no field {k}")
-            setattr(p, k, (C.c_double * 2)(*map(float, v)) if k in ("map_origin", "lattice_anchor") else v)
-        return p
+        fields = {k: (C.c_double * 2)(*map(float, v)) if k in ("map_origin", "lattice_anchor") else v for k, v in fields.items()}
+        return _params("mpc_window_params", MpcWindowParams,
+                       lambda p: self._lib.mpc_window_params_defaults(p, float(map_resolution), int(map_shape[1]), int(map_shape[0])), fields)
 
     def costmap_window(self, map_cost, params: MpcWindowParams, robot_pose, size, resolution):
         """One shared map -> the local costmap window of every robot (mpc_costmap_window, include/mpc_costmap_window.h): the window's origin from the pose alone, on the

@@ -1,161 +1,167 @@
-"""CPU tests of the drop-in boundary: the C-ABI library builds for gfx950, loads, exports every symbol that
-include/mpc_hip.h declares, the ctypes mirror of mpc_config has the C layout, and -- without a GPU --
-mpc_create fails loudly instead of falling back to a CPU path.  No compute calls here."""
+"""CPU tests of the drop-in boundary, for every header of _abi.HEADERS: the C-ABI library builds for gfx950, loads, exports and binds every function a header declares;
+every prototype table matches its header's declarations, parameter by parameter; every ctypes mirror has the C layout; and -- without a GPU -- mpc_create fails loudly
+instead of falling back to a CPU path.  No compute calls here.  What is particular to one side header (the values of its defaults, its refusals without a handle) is in
+tests/test_fleet_abi.py and tests/test_costmap_{clusters,lines,window}_abi.py."""
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "mpc_hip.h")
+import _abi_check as K
+from _abi_check import ROOT, lib      # noqa: F401 (lib: the fixture)
+from mpc_local_planner_amd import _abi, _lib
+from mpc_local_planner_amd._abi import CLUSTER_PROTOTYPES, FLEET_PROTOTYPES, HEADERS, LINE_PROTOTYPES, PROTOTYPES, WINDOW_PROTOTYPES
 
-
-@pytest.fixture(scope="module")
-def lib():
-    from mpc_local_planner_amd import _lib
-    if shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc"):
-        _lib.build()
-    return _lib.load()
+STRUCTS = [(header, struct) for header, (_, mirrors) in HEADERS.items() for struct in mirrors]
 
 
 def _declared_functions():
-    txt = open(HEADER).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    txt = re.sub(r"/\*.*?\*/", "", K.header_text(K.MAIN), flags=re.S)
     return sorted(set(re.findall(r"\b(mpc_[a-z_0-9]+)\s*\(", txt)))
 
 
+# header -> (the name of its table in _abi, the sorted names it declares)
+PINNED = {
+    "mpc_hip.h": ("PROTOTYPES", _declared_functions()),
+    "mpc_fleet.h": ("FLEET_PROTOTYPES", ["mpc_fleet_pool", "mpc_fleet_pool_device", "mpc_obstacles_from_pool", "mpc_obstacles_from_pool_device", "mpc_pool_params_defaults"]),
+    "mpc_costmap_clusters.h": ("CLUSTER_PROTOTYPES", ["mpc_cluster_params_defaults", "mpc_costmap_to_polygons", "mpc_costmap_to_polygons_device", "mpc_last_costmap_ms"]),
+    "mpc_costmap_lines.h": ("LINE_PROTOTYPES", ["mpc_costmap_to_lines", "mpc_costmap_to_lines_device", "mpc_line_params_defaults"]),
+    "mpc_costmap_window.h": ("WINDOW_PROTOTYPES", ["mpc_costmap_window", "mpc_costmap_window_device", "mpc_window_params_defaults"]),
+}
+
+
 def test_header_functions_all_exported(lib):
-    from mpc_local_planner_amd import _lib
     names = _declared_functions()
     assert set(names) == set(_lib.EXPORTS)
     for n in names:
         assert hasattr(lib, n), n
 
 
-# ---- every prototype of _abi.PROTOTYPES against its declaration -----------------------------------------------------------------------------------------------------
-STRUCT_MIRRORS = {"mpc_config": "MpcConfig", "mpc_obstacles": "MpcObstacles", "mpc_eval_out": "MpcEvalOut", "mpc_cycle_params": "MpcCycleParams", "mpc_plan_params": "MpcPlanParams"}
+def test_the_registry_is_the_five_tables_and_they_are_disjoint():
+    assert list(HEADERS) == list(PINNED) and all(HEADERS[h][0] is getattr(_abi, t) for h, (t, _) in PINNED.items())
+    assert len(PINNED[K.MAIN][1]) == len(PROTOTYPES) == 37 and _lib.EXPORTS == list(PROTOTYPES)
+    assert sum(len(t) for t, _ in HEADERS.values()) == len(set().union(*(t for t, _ in HEADERS.values()))) == 52
 
 
-def _header_code(text):
-    return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+# ---- every prototype of every table against its declaration --------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("header", list(HEADERS))
+def test_every_prototype_matches_its_declaration(header):
+    table, mirrors = HEADERS[header]
+    text = K.header_text(header)
+    assert sorted(K.declarations(text)) == sorted(table) == PINNED[header][1]
+    assert K.mismatches(header, table) == []
+    assert sorted(re.findall(r"typedef struct (\w+) \{", text)) == sorted(mirrors)      # no struct of the header without its mirror
 
 
-def _declarations(text):
-    """{name: (return type, [(parameter type, parameter name), ...])} of every `ret name(params);` of the header, types without const"""
-    def ctype(words):
-        return " ".join(w for w in words if w != "const").replace(" *", "*")
-    out = {}
-    for ret, name, params in re.findall(r"([\w \*]+?)\b(mpc_\w+)\s*\(([^)]*)\)\s*;", _header_code(text)):
-        params = [p.replace("*", " * ").split() for p in params.split(",")]
-        out[name] = (ctype(ret.replace("*", " * ").split()), [] if params == [["void"]] else [(ctype(p[:-1]), p[-1]) for p in params])
-    return out
-
-
-# where the binding deviates from the rule of _bound (found by the comparator when the table or the header changes; kept as the parent's load() had them)
-VOID_STRUCTS = ("mpc_obstacles",)                                            # const mpc_obstacles* is bound as c_void_p everywhere: callers pass byref() or NULL
-EXCEPTIONS = {("mpc_set_parameter_sets", "sets"): C.c_void_p,                # an array of mpc_config, passed as a cast address
-              ("mpc_occupancy", "workgroups_per_cu"): C.POINTER(C.c_int32)}  # the one int32_t* that is a byref() scalar and not an array
-
-
-def _bound(function, ctype, name=None):
-    """THE ctypes object a return value (name None) or a parameter of this C type is bound as: exactly one"""
-    from mpc_local_planner_amd import _abi
-    if (function, name) in EXCEPTIONS:
-        return EXCEPTIONS[function, name]
-    if ctype in ("double", "int32_t", "int"):
-        return C.c_double if ctype == "double" else C.c_int32      # (c_int32 is c_int here: one object)
-    if name is None:
-        return {"void": None, "char*": C.c_char_p}[ctype]
-    assert ctype.endswith("*"), ctype
-    base = ctype[:-1]
-    if base in STRUCT_MIRRORS and base not in VOID_STRUCTS:
-        return C.POINTER(getattr(_abi, STRUCT_MIRRORS[base]))
-    return {"mpc_solver*": C.POINTER(C.c_void_p), "float": C.POINTER(C.c_float), "int64_t": C.POINTER(C.c_int64)}.get(base, C.c_void_p)
-
-
-def abi_mismatches(header_text, table):
-    """what differs between the header's declarations and a prototype table: a function of the two alone"""
-    decl = _declarations(header_text)
-    bad = [f"{n}: declared, not in the table" for n in sorted(set(decl) - set(table))] + [f"{n}: in the table, not declared" for n in sorted(set(table) - set(decl))]
-    for name in sorted(set(decl) & set(table)):
-        (ret, params), (restype, argtypes) = decl[name], table[name]
-        if restype is not _bound(name, ret):
-            bad.append(f"{name}: returns {ret}, bound as {restype}")
-        if len(params) != len(argtypes):
-            bad.append(f"{name}: {len(params)} parameters declared, {len(argtypes)} bound")
-            continue
-        bad += [f"{name}: parameter {i} is {t} {p}, bound as {a}" for i, ((t, p), a) in enumerate(zip(params, argtypes)) if a is not _bound(name, t, p)]
-    return bad
-
-
-def _with(table, function, index, bound):
-    """a copy of the table with one parameter of one function bound differently (index None: the parameter dropped)"""
-    restype, argtypes = table[function]
-    return {**table, function: (restype, argtypes[:-1] if index is None else argtypes[:index] + [bound] + argtypes[index + 1:])}
-
-
-def test_every_prototype_matches_its_declaration():
-    from mpc_local_planner_amd._abi import PROTOTYPES, MpcEvalOut, MpcObstacles
-    header = open(HEADER).read()
-    assert len(_declarations(header)) == len(PROTOTYPES) == 37 and set(_declarations(header)) == set(_declared_functions())
-    assert abi_mismatches(header, PROTOTYPES) == []
+def test_spot_pins():
+    """single rows, by hand: the comparator's rule and the tables agree with what callers pass"""
+    from mpc_local_planner_amd._abi import MpcClusterParams, MpcEvalOut, MpcLineParams, MpcPool, MpcWindowParams
     assert C.c_int is C.c_int32 and PROTOTYPES["mpc_evaluate_batch"][1][10] is C.POINTER(MpcEvalOut) and PROTOTYPES["mpc_grid_update_device"][1][9] is C.c_double
-    # the comparator reports each of these, and nothing else: it cannot pass by seeing nothing, and it accepts one object per parameter
-    corrupted = [
-        (_with(PROTOTYPES, "mpc_step_batch", None, None), "mpc_step_batch: 21 parameters declared, 20 bound"),
-        (_with(PROTOTYPES, "mpc_grid_update_device", 9, C.c_int32), f"mpc_grid_update_device: parameter 9 is double dt_hyst_ratio, bound as {C.c_int32}"),
-        ({k: v for k, v in PROTOTYPES.items() if k != "mpc_synchronize"}, "mpc_synchronize: declared, not in the table"),
-        (_with(PROTOTYPES, "mpc_evaluate_batch", 10, C.c_void_p), f"mpc_evaluate_batch: parameter 10 is mpc_eval_out* out, bound as {C.c_void_p}"),      # callers pass byref(MpcEvalOut)
-        (_with(PROTOTYPES, "mpc_create", 0, C.c_void_p), f"mpc_create: parameter 0 is mpc_config* cfg, bound as {C.c_void_p}"),
-        (_with(PROTOTYPES, "mpc_occupancy", 2, C.c_void_p), f"mpc_occupancy: parameter 2 is int32_t* workgroups_per_cu, bound as {C.c_void_p}"),
-        (_with(PROTOTYPES, "mpc_get_grid_sizes", 2, C.POINTER(C.c_int32)), f"mpc_get_grid_sizes: parameter 2 is int32_t* n_grid, bound as {C.POINTER(C.c_int32)}"),
-        (_with(PROTOTYPES, "mpc_solve_batch", 9, C.POINTER(MpcObstacles)), f"mpc_solve_batch: parameter 9 is mpc_obstacles* obstacles, bound as {C.POINTER(MpcObstacles)}"),
-    ]
-    for table, report in corrupted:
-        assert abi_mismatches(header, table) == [report]
+    assert len(FLEET_PROTOTYPES["mpc_fleet_pool_device"][1]) == 13 and FLEET_PROTOTYPES["mpc_obstacles_from_pool"][1][2] is C.POINTER(MpcPool)
+    poly, lines, window = (t[n][1] for t, n in ((CLUSTER_PROTOTYPES, "mpc_costmap_to_polygons_device"), (LINE_PROTOTYPES, "mpc_costmap_to_lines_device"),
+                                                (WINDOW_PROTOTYPES, "mpc_costmap_window_device")))
+    assert poly[8] is C.POINTER(MpcClusterParams) and len(poly) == 16
+    assert lines[8] is C.POINTER(MpcLineParams) and len(lines) == 16
+    assert window[3] is C.POINTER(MpcWindowParams) and len(window) == 11
+    assert lines[:8] == poly[:8] and lines[9:] == poly[9:]      # the argument lists of the line step mirror the polygon step's, the params struct aside
+
+
+# the comparator reports each of these, and nothing else: it cannot pass by seeing nothing, and it accepts one object per parameter.
+# (header, function, parameter, bound as, the report); parameter None: the last one dropped; MISSING: the function taken out of the table
+MISSING = "missing"
+_OBSTACLES, _I32P = C.POINTER(_abi.MpcObstacles), C.POINTER(C.c_int32)
+CORRUPTED = [
+    ("mpc_hip.h", "mpc_step_batch", None, None, "mpc_step_batch: 21 parameters declared, 20 bound"),
+    ("mpc_hip.h", "mpc_grid_update_device", 9, C.c_int32, f"mpc_grid_update_device: parameter 9 is double dt_hyst_ratio, bound as {C.c_int32}"),
+    ("mpc_hip.h", "mpc_synchronize", MISSING, None, "mpc_synchronize: declared, not in the table"),
+    ("mpc_hip.h", "mpc_evaluate_batch", 10, C.c_void_p, f"mpc_evaluate_batch: parameter 10 is mpc_eval_out* out, bound as {C.c_void_p}"),      # callers pass byref(MpcEvalOut)
+    ("mpc_hip.h", "mpc_create", 0, C.c_void_p, f"mpc_create: parameter 0 is mpc_config* cfg, bound as {C.c_void_p}"),
+    ("mpc_hip.h", "mpc_occupancy", 2, C.c_void_p, f"mpc_occupancy: parameter 2 is int32_t* workgroups_per_cu, bound as {C.c_void_p}"),
+    ("mpc_hip.h", "mpc_get_grid_sizes", 2, _I32P, f"mpc_get_grid_sizes: parameter 2 is int32_t* n_grid, bound as {_I32P}"),
+    ("mpc_hip.h", "mpc_solve_batch", 9, _OBSTACLES, f"mpc_solve_batch: parameter 9 is mpc_obstacles* obstacles, bound as {_OBSTACLES}"),
+    ("mpc_fleet.h", "mpc_fleet_pool_device", 6, C.c_int32, f"mpc_fleet_pool_device: parameter 6 is double robot_radius, bound as {C.c_int32}"),
+    ("mpc_fleet.h", "mpc_obstacles_from_pool", 2, C.c_void_p, f"mpc_obstacles_from_pool: parameter 2 is mpc_pool* pool, bound as {C.c_void_p}"),
+    ("mpc_fleet.h", "mpc_fleet_pool", MISSING, None, "mpc_fleet_pool: declared, not in the table"),
+    ("mpc_costmap_clusters.h", "mpc_costmap_to_polygons_device", 5, C.c_int32, f"mpc_costmap_to_polygons_device: parameter 5 is double resolution, bound as {C.c_int32}"),
+    ("mpc_costmap_clusters.h", "mpc_costmap_to_polygons", 8, C.c_void_p, f"mpc_costmap_to_polygons: parameter 8 is mpc_cluster_params* params, bound as {C.c_void_p}"),
+    ("mpc_costmap_clusters.h", "mpc_last_costmap_ms", MISSING, None, "mpc_last_costmap_ms: declared, not in the table"),
+    ("mpc_costmap_lines.h", "mpc_costmap_to_lines", 8, C.c_void_p, f"mpc_costmap_to_lines: parameter 8 is mpc_line_params* params, bound as {C.c_void_p}"),
+    ("mpc_costmap_window.h", "mpc_costmap_window_device", 7, C.c_int32, f"mpc_costmap_window_device: parameter 7 is double resolution, bound as {C.c_int32}"),
+    ("mpc_costmap_window.h", "mpc_costmap_window", 3, C.c_void_p, f"mpc_costmap_window: parameter 3 is mpc_window_params* params, bound as {C.c_void_p}"),
+    ("mpc_costmap_window.h", "mpc_window_params_defaults", MISSING, None, "mpc_window_params_defaults: declared, not in the table"),
+]
+
+
+@pytest.mark.parametrize("header,function,index,bound,report", CORRUPTED, ids=[f"{r[1]}-{r[2]}" for r in CORRUPTED])
+def test_the_comparator_reports_a_corrupted_table(header, function, index, bound, report):
+    table = dict(HEADERS[header][0])
+    restype, argtypes = table.pop(function)
+    if index != MISSING:
+        table[function] = (restype, argtypes[:-1] if index is None else argtypes[:index] + [bound] + argtypes[index + 1:])
+    assert K.mismatches(header, table) == [report]
+
+
+@pytest.mark.parametrize("header", K.SIDE)
+def test_mpc_hip_h_declares_nothing_of_a_side_header(header):
+    """a side header's functions and structs are declared there alone; include/mpc_hip.h keeps its 37 declarations and does not know the side header"""
+    table, mirrors = HEADERS[header]
+    hip_text = K.header_text(K.MAIN)
+    hip = K.header_code(hip_text)
+    for name in list(table) + list(mirrors):
+        assert not re.search(r"\b%s\b" % name, hip), name
+    assert len(K.declarations(hip_text)) == 37
+    assert '#include "mpc_hip.h"' in K.header_text(header) and header[:-len(".h")] not in hip_text
 
 
 # ---- every mirrored struct against the C compiler's layout ----------------------------------------------------------------------------------------------------------------
-# struct -> (number of fields, the enumerators that ride with it: C name -> the Python constant of _abi)
+# struct -> (the field names or their number, sizeof, the enumerators that ride with it: C name -> the Python constant of _abi); None: not pinned here
 LAYOUTS = {
-    "mpc_config": (None, {}),
-    "mpc_obstacles": (5, {}),
-    "mpc_eval_out": (5, {}),
-    "mpc_cycle_params": (14, {f"MPC_REINIT_{k}": f"REINIT_{k}" for k in ("FIRST", "NUM_STEPS", "GOAL_DIST", "GOAL_ANGULAR", "RESET", "PLAN_GUESS")}),
-    "mpc_plan_params": (10, {**{f"MPC_PLAN_{k}": f"PLAN_{k}" for k in ("GOAL_REACHED", "EMPTY", "TRUNCATED", "VIA_DROPPED", "GOAL_INJECTED")},
-                             **{f"MPC_CMD_{k}": f"CMD_{k}" for k in ("SUCCESS", "GOAL_REACHED", "PLAN_EMPTY", "SOLVE_FAILED", "INFEASIBLE", "NOT_FINITE")}}),
+    "mpc_config": (None, None, {}),
+    "mpc_obstacles": (5, None, {}),
+    "mpc_eval_out": (5, None, {}),
+    "mpc_cycle_params": (14, None, {f"MPC_REINIT_{k}": f"REINIT_{k}" for k in ("FIRST", "NUM_STEPS", "GOAL_DIST", "GOAL_ANGULAR", "RESET", "PLAN_GUESS")}),
+    "mpc_plan_params": (10, None, {**{f"MPC_PLAN_{k}": f"PLAN_{k}" for k in ("GOAL_REACHED", "EMPTY", "TRUNCATED", "VIA_DROPPED", "GOAL_INJECTED")},
+                                   **{f"MPC_CMD_{k}": f"CMD_{k}" for k in ("SUCCESS", "GOAL_REACHED", "PLAN_EMPTY", "SOLVE_FAILED", "INFEASIBLE", "NOT_FINITE")}}),
+    "mpc_pool": (5, None, {}),
+    "mpc_pool_params": (3, None, {}),
+    "mpc_cluster_params": (["behind_robot_dist", "link_dist_sq"], None, {}),
+    "mpc_line_params": (["behind_robot_dist", "link_dist_sq", "inlier_dist_sq", "min_inliers", "n_hypotheses", "remaining_outliers"], 32, {}),
+    "mpc_window_params": (["map_origin", "map_resolution", "lattice_anchor", "inscribed_radius", "inflation_radius", "cost_scaling_factor", "map_size_x", "map_size_y",
+                           "outside_value", "inflate_unknown"], 80, {}),
 }
 
 
-def _header_fields(struct):
-    """the field names of `typedef struct <struct> {...} <struct>;` in header order"""
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), _header_code(open(HEADER).read()), flags=re.S).group(1)
-    return [re.search(r"(\w+)\s*(?:\[\w+\])?\s*$", d).group(1) for decl in body.split(";") if decl.strip() for d in decl.split(",")]      # `double Q[3], R[2]` -> Q, R
+def test_every_struct_of_the_registry_has_its_pins():
+    assert sorted(s for _, s in STRUCTS) == sorted(LAYOUTS) and len(LAYOUTS) == 10
 
 
-@pytest.mark.parametrize("struct", sorted(LAYOUTS))
-def test_struct_layout_matches_c(struct, tmp_path):
-    """sizeof, every offsetof and the field names in header order of the ctypes mirror, against the C compiler; and the enumerators that belong to the struct's calls"""
-    from mpc_local_planner_amd import _abi
-    mirror = getattr(_abi, STRUCT_MIRRORS[struct])
-    count, enums = LAYOUTS[struct]
+@pytest.mark.parametrize("header,struct", STRUCTS, ids=[s for _, s in STRUCTS])
+def test_struct_layout_matches_c(header, struct, tmp_path):
+    """sizeof, every offsetof and the field names in header order of the ctypes mirror, against the C compiler (every header compiles as C); and the enumerators that
+    belong to the struct's calls"""
+    mirror = HEADERS[header][1][struct]
+    pinned, size, enums = LAYOUTS[struct]
     fields = [f[0] for f in mirror._fields_]
-    assert fields == _header_fields(struct) and (count is None or len(fields) == count)
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "mpc_hip.h"\nint main(){\nprintf("%%zu\\n", sizeof(%s));\n' % struct +
-                   "".join('printf("%%zu\\n", offsetof(%s,%s));\n' % (struct, f) for f in fields) + "".join('printf("%%d\\n", %s);\n' % e for e in enums) + 'return 0;}\n')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    out = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert len(out) == 1 + len(fields) + len(enums) and out[0] == C.sizeof(mirror)
+    assert fields == K.struct_fields(header, struct) and pinned in (None, len(fields), fields)
+    out = K.c_layout(header, struct, fields, enums, tmp_path)
+    assert len(out) == 1 + len(fields) + len(enums) and out[0] == C.sizeof(mirror) and size in (None, out[0])
     for f, o in zip(fields, out[1:]):
         assert getattr(mirror, f).offset == o, f
     assert out[1 + len(fields):] == [getattr(_abi, v) for v in enums.values()]
+
+
+@pytest.mark.parametrize("header", list(HEADERS))
+def test_library_exports_and_binds_every_prototype(header, lib):
+    table = HEADERS[header][0]
+    assert len(_lib.EXPORTS) == 37 and (header == K.MAIN or not set(table) & set(_lib.EXPORTS))
+    for name, (restype, argtypes) in table.items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype and fn.argtypes == argtypes, name
+    assert lib.mpc_version() == 900
 
 
 def test_defaults_match_reference_in_code_defaults(lib):
@@ -191,6 +197,19 @@ def test_per_instance_int32_arrays_are_checked():
         _as_i32(np.zeros(3), 4, "n_plan")
     with pytest.raises(ValueError):      # reset of controller_step: numpy's own message
         _as_i32(np.zeros(3, np.int32), 4)
+
+
+def test_parameter_structs_are_the_defaults_then_the_given_fields(lib):
+    """what cycle_params, plan_params, pool_params and window_params go through: the caller's defaults call, then the fields; an unknown field raises by the struct's name"""
+    from mpc_local_planner_amd._abi import MpcCycleParams, MpcPoolParams
+    from mpc_local_planner_amd.solver import _params
+    ref, p = MpcCycleParams(), _params("mpc_cycle_params", MpcCycleParams, lib.mpc_cycle_params_defaults, {"n_min": 7})
+    lib.mpc_cycle_params_defaults(C.byref(ref))
+    assert p.n_min == 7 and [getattr(p, f) for f, _ in p._fields_ if f != "n_min"] == [getattr(ref, f) for f, _ in p._fields_ if f != "n_min"]
+    q = _params("mpc_pool_params", MpcPoolParams, lambda p: lib.mpc_pool_params_defaults(None, p), {"append": 0})
+    assert (q.reach, q.min_speed, q.append) == (0.0, 0.001, 0)
+    with pytest.raises(ValueError, match="^mpc_pool_params has no field bogus$"):
+        _params("mpc_pool_params", MpcPoolParams, lambda p: lib.mpc_pool_params_defaults(None, p), {"bogus": 1})
 
 
 def test_no_gpu_means_loud_failure_not_cpu_fallback(lib):

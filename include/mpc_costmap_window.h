@@ -2,6 +2,7 @@
  * costmap converters, the controller cycle and the feasibility check start from, cost [B][size_y][size_x] and origin [B][2].
  *
  *     mpc_costmap_window_device        (one map on the device, B robot poses -> B windows and their origins)
+ *  -> mpc_costmap_scans_device         (optional, include/mpc_costmap_scans.h: B laser scans -> B obstacle layers kept between cycles, combined into the windows)
  *  -> mpc_costmap_to_obstacles_device  (one point per lethal cell)
  *  or mpc_costmap_to_polygons_device   (one point, line or convex polygon per cluster of lethal cells)
  *  or mpc_costmap_to_lines_device      (line segments along the walls of a cluster, points for what is left)

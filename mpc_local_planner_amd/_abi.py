@@ -349,6 +349,42 @@ HEADERS = {
 }
 
 
+class MpcScanParams(C.Structure):
+    """struct mpc_scan_params (include/mpc_costmap_scans.h); field-for-field."""
+    _fields_ = [
+        ("lattice_anchor", C.c_double * 2),
+        ("sensor_pose", C.c_double * 3),
+        ("angle_min", C.c_double),
+        ("angle_increment", C.c_double),
+        ("range_min", C.c_double),
+        ("range_max", C.c_double),
+        ("obstacle_range", C.c_double),
+        ("raytrace_range", C.c_double),
+        ("footprint_clear_radius", C.c_double),
+        ("marking", C.c_int32),
+        ("clearing", C.c_int32),
+        ("inf_is_valid", C.c_int32),
+        ("track_unknown", C.c_int32),
+        ("combination_method", C.c_int32),
+    ]
+
+
+# ---- include/mpc_costmap_scans.h
+# s, B, params, robot_pose, ranges, n_beams, keep, size_x, size_y, resolution, layer, layer_cell, cost, info
+_SCANS = (_rc, [_p, _i, C.POINTER(MpcScanParams), _p, C.POINTER(C.c_float), _i, _p, _i, _i, _d, _p, _p, _p, _p])
+
+SCAN_PROTOTYPES = {
+    "mpc_scan_params_defaults": (None, [C.POINTER(MpcScanParams)]),                             # p
+    "mpc_costmap_scans": _SCANS, "mpc_costmap_scans_device": _SCANS,
+}
+
+# Headers that came after tests/test_abi.py pinned HEADERS to its five tables and their 52 functions: the same row, bound by _lib.load() in the same loop, and held to
+# its header by the same comparator in the header's own test module (tests/test_costmap_scans_abi.py).
+LATER_HEADERS = {
+    "mpc_costmap_scans.h": (SCAN_PROTOTYPES, {"mpc_scan_params": MpcScanParams}),
+}
+
+
 def _diag_offdiag(w, dim):
     """a weight given as its diagonal or as a full dim x dim matrix -> (diagonal, off-diagonal terms (0,1)[, (0,2), (1,2)] of the symmetric part)"""
     rows = [list(r) if hasattr(r, "__len__") else None for r in w]

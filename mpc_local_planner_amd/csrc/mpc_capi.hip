@@ -16,6 +16,7 @@
 #include "../../include/mpc_costmap_clusters.h"
 #include "../../include/mpc_costmap_lines.h"
 #include "../../include/mpc_costmap_window.h"
+#include "../../include/mpc_costmap_scans.h"
 #include "mpc_core.hpp"
 #include "mpc_problem.hpp"
 #include "mpc_launch_plan.hpp"
@@ -31,6 +32,7 @@
 #include "mpc_costmap_clusters.hpp"
 #include "mpc_costmap_lines.hpp"
 #include "mpc_costmap_window.hpp"
+#include "mpc_costmap_scans.hpp"
 
 namespace {
 
@@ -1572,6 +1574,90 @@ int mpc_costmap_window(mpc_solver* s, int32_t B, const uint8_t* map, const mpc_w
                                    stage_out(origin, nb * 16), stage_out(info, nb * 16)};
     return staged_call(s, "mpc_costmap_window", true, true, pc, 5, [&](void** d) -> int {
         return mpc_costmap_window_device(s, B, (const uint8_t*)d[0], params, (const double*)d[1], size_x, size_y, resolution, (uint8_t*)d[2], (double*)d[3], (int32_t*)d[4]);
+    });
+}
+
+}  // extern "C"
+
+// ---- the laser-scan obstacle layer of a batch (mpc_costmap_scans.hpp; declared in include/mpc_costmap_scans.h)
+
+// the argument checks of both variants, in the order of rule 8: true with mpc_last_error set when the call is refused; R: rule 4's longest ray in cells
+static bool scans_error(const char* who, const mpc_solver* s, const mpc_scan_params* p, const void* robot_pose, const void* ranges, int32_t n_beams, int32_t size_x,
+                        int32_t size_y, double resolution, const void* layer, const void* layer_cell, int& R) {
+    auto nonneg_finite = [](double v) { return v >= 0.0 && std::isfinite(v); };
+    if (!s || !p || !robot_pose || !ranges || !layer || !layer_cell) return costmap_no(who, "null argument (params, robot_pose, ranges, layer, layer_cell)");
+    if (n_beams < 1 || n_beams > mpc::kCsMaxBeams) return costmap_no(who, "n_beams has to be in [1, 4096]");
+    if (size_x < 1 || size_y < 1 || (long long)size_x * size_y > mpc::kCsMaxCells) return costmap_no(who, "bad layer geometry (1 <= size_x, size_y; size_x * size_y <= 65536)");
+    if (!(resolution > 0.0) || !std::isfinite(resolution)) return costmap_no(who, "resolution has to be positive and finite");
+    if (!nonneg_finite(p->range_min) || !nonneg_finite(p->range_max) || !nonneg_finite(p->obstacle_range) || !nonneg_finite(p->raytrace_range))
+        return costmap_no(who, "range_min, range_max, obstacle_range and raytrace_range have to be at least 0 and finite");
+    R = mpc::cs_ray_cells(p->raytrace_range, resolution);
+    if (R < 0) return costmap_no(who, "raytrace_range has to be at most 4096 cells");
+    if (!(p->range_max / resolution < mpc::kCsMaxRangeCells)) return costmap_no(who, "range_max has to be below 2^15 cells");
+    if (!std::isfinite(p->angle_min) || !std::isfinite(p->angle_increment) || !std::isfinite(p->sensor_pose[0]) || !std::isfinite(p->sensor_pose[1]) || !std::isfinite(p->sensor_pose[2]))
+        return costmap_no(who, "angle_min, angle_increment and sensor_pose have to be finite");
+    if (std::isnan(p->footprint_clear_radius)) return costmap_no(who, "footprint_clear_radius is not a number");
+    return costmap_no(who, p->combination_method == 0 || p->combination_method == 1 ? nullptr : "combination_method has to be 0 or 1");
+}
+
+extern "C" {
+
+void mpc_scan_params_defaults(mpc_scan_params* p) {
+    if (!p) return;
+    p->lattice_anchor[0] = p->lattice_anchor[1] = 0.0;
+    p->sensor_pose[0] = p->sensor_pose[1] = p->sensor_pose[2] = 0.0;
+    p->angle_min = -3.14159265358979323846;
+    p->angle_increment = 2.0 * 3.14159265358979323846 / 360.0;
+    p->range_min = 0.0; p->range_max = 30.0;
+    p->obstacle_range = 2.5; p->raytrace_range = 3.0;
+    p->footprint_clear_radius = 0.0;
+    p->marking = p->clearing = 1;
+    p->inf_is_valid = 0;
+    p->track_unknown = 0;
+    p->combination_method = 1;
+}
+
+int mpc_costmap_scans_device(mpc_solver* s, int32_t B, const mpc_scan_params* params, const double* d_robot_pose, const float* d_ranges, int32_t n_beams,
+                             const int32_t* d_keep, int32_t size_x, int32_t size_y, double resolution, uint8_t* d_layer, int32_t* d_layer_cell, uint8_t* d_cost,
+                             int32_t* d_info) {
+    g_err[0] = 0;
+    int R = 0;
+    if (scans_error("mpc_costmap_scans", s, params, d_robot_pose, d_ranges, n_beams, size_x, size_y, resolution, d_layer, d_layer_cell, R)) return MPC_EINVAL;
+    if (B <= 0) return MPC_OK;
+    if (const int rc = refused(s, B, REF_MAX_BATCH, "mpc_costmap_scans")) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    mpc::ScanArgs a;
+    memset(&a, 0, sizeof(a));
+    a.pose = d_robot_pose; a.ranges = d_ranges; a.keep = d_keep; a.layer = d_layer; a.layer_cell = d_layer_cell; a.cost = d_cost; a.info = d_info;
+    a.p = {params->lattice_anchor[0], params->lattice_anchor[1], resolution, params->sensor_pose[0], params->sensor_pose[1], params->sensor_pose[2], params->angle_min,
+           params->angle_increment, params->range_min, params->range_max, params->obstacle_range, params->footprint_clear_radius, params->marking ? 1 : 0,
+           params->clearing ? 1 : 0, params->inf_is_valid ? 1 : 0, params->combination_method, R, params->track_unknown ? 255 : 0};
+    a.W = size_x; a.H = size_y; a.n_beams = n_beams;
+    const size_t lds = mpc::cs_lds_bytes(size_x, size_y);      // the layer of an instance, at most 64 KB, and the counts
+    if (lds > 48u * 1024u) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(mpc::costmap_scans_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIP_TRY(hipEventRecord(s->cev0, s->stream));
+    hipLaunchKernelGGL(mpc::costmap_scans_kernel, dim3((unsigned)B), dim3(mpc::kCsThreads), lds, s->stream, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(s->cev1, s->stream));
+    s->ctimed = true;
+    return MPC_OK;
+}
+
+int mpc_costmap_scans(mpc_solver* s, int32_t B, const mpc_scan_params* params, const double* robot_pose, const float* ranges, int32_t n_beams, const int32_t* keep,
+                      int32_t size_x, int32_t size_y, double resolution, uint8_t* layer, int32_t* layer_cell, uint8_t* cost, int32_t* info) {
+    g_err[0] = 0;
+    int R = 0;
+    if (scans_error("mpc_costmap_scans", s, params, robot_pose, ranges, n_beams, size_x, size_y, resolution, layer, layer_cell, R)) return MPC_EINVAL;
+    if (B <= 0) return MPC_OK;
+    if (const int rc = refused(s, B, REF_MAX_BATCH, "mpc_costmap_scans")) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t nb = (size_t)B, cells = (size_t)size_x * size_y;
+    // in / out: the layer and its cell are the state the call rolls; the window is combined in place
+    const mpc::StagePiece pc[7] = {stage_in(robot_pose, nb * 24), stage_in(ranges, nb * (size_t)n_beams * 4), stage_in(keep, nb * 4), stage_inout(layer, nb * cells),
+                                   stage_inout(layer_cell, nb * 8), stage_inout(cost, nb * cells), stage_out(info, nb * 16)};
+    return staged_call(s, "mpc_costmap_scans", true, true, pc, 7, [&](void** d) -> int {
+        return mpc_costmap_scans_device(s, B, params, (const double*)d[0], (const float*)d[1], n_beams, (const int32_t*)d[2], size_x, size_y, resolution, (uint8_t*)d[3],
+                                        (int32_t*)d[4], (uint8_t*)d[5], (int32_t*)d[6]);
     });
 }
 

@@ -555,6 +555,70 @@ def window_params_from_costmap_yaml(local_costmap: dict, common: dict | None, ma
     return c, (int(float(tree["width"]) / res), int(float(tree["height"]) / res))
 
 
+OBSTACLE_LAYER, VOXEL_LAYER = "costmap_2d::ObstacleLayer", "costmap_2d::VoxelLayer"
+
+
+def scan_params_from_costmap_yaml(local_costmap: dict, common: dict | None, scan: dict | None):
+    """struct mpc_scan_params (mpc_costmap_scans*, BatchSolver.costmap_scans_device) from the parameter trees of a local costmap (cfg/<robot>/local_costmap_params.yaml,
+    with or without its `local_costmap` key) and of the common block loaded into the same namespace (cfg/<robot>/costmap_common_params.yaml; the local file's keys win),
+    and from what the sensor's messages carry, `scan`: angle_min, angle_increment, range_min, range_max and sensor_pose (x, y, yaw in the robot frame); what it leaves
+    out keeps the library's default, any other key is ParamNotImplemented.
+    The costmap_2d::ObstacleLayer among `plugins` names its block: obstacle_range (2.5), raytrace_range (3.0), track_unknown_space (false), combination_method (1),
+    footprint_clearing_enabled (true), and observation_sources, which has to name ONE source with data_type LaserScan; its marking (true), clearing (false, as
+    costmap_2d has it) and inf_is_valid (false) are read, and an obstacle_range or raytrace_range of the source's own wins over the layer's.  Where footprint clearing is
+    enabled and the tree has a robot_radius, footprint_clear_radius is that radius (mpc_costmap_scans clears a disc, not a polygon); otherwise it is 0.
+    ParamNotImplemented: a costmap_2d::VoxelLayer, a PointCloud or PointCloud2 source, more or fewer than one source, no obstacle layer, a combination_method other than
+    0 and 1.  lattice_anchor is (0, 0), as window_params_from_costmap_yaml has it."""
+    local = local_costmap.get("local_costmap", local_costmap) if isinstance(local_costmap.get("local_costmap", None), dict) else local_costmap
+    tree = {**(common or {}), **local}
+    plugins = [pl for pl in tree.get("plugins") or [] if isinstance(pl, dict)]
+    if any(pl.get("type") == VOXEL_LAYER for pl in plugins):
+        raise ParamNotImplemented("local costmap: a costmap_2d::VoxelLayer (mpc_costmap_scans keeps a flat layer from one laser scan)")
+    layers = [pl for pl in plugins if pl.get("type") == OBSTACLE_LAYER]
+    if len(layers) != 1:
+        raise ParamNotImplemented("local costmap: exactly one costmap_2d::ObstacleLayer has to be among the plugins")
+    block = tree.get(layers[0].get("name")) if isinstance(tree.get(layers[0].get("name")), dict) else {}
+    sources = str(block.get("observation_sources", "")).split()
+    if len(sources) != 1:
+        raise ParamNotImplemented(f"obstacle layer: observation_sources has to name one source, not {len(sources)} (mpc_costmap_scans takes one scan per robot)")
+    source = block.get(sources[0])
+    if not isinstance(source, dict):
+        raise ParamNotImplemented(f"obstacle layer: the source {sources[0]} has no block")
+    if source.get("data_type", "PointCloud") != "LaserScan":
+        raise ParamNotImplemented(f"obstacle layer: a {source.get('data_type', 'PointCloud')} source (mpc_costmap_scans takes a LaserScan)")
+    method = int(block.get("combination_method", 1))
+    if method not in (0, 1):
+        raise ParamNotImplemented(f"obstacle layer: combination_method {method} (0 and 1 are implemented)")
+    p = A.MpcScanParams()
+    _lib_defaults_scan(p)
+    p.obstacle_range = float(source.get("obstacle_range", block.get("obstacle_range", 2.5)))
+    p.raytrace_range = float(source.get("raytrace_range", block.get("raytrace_range", 3.0)))
+    p.track_unknown = 1 if block.get("track_unknown_space", False) else 0
+    p.combination_method = method
+    p.marking = 1 if source.get("marking", True) else 0
+    p.clearing = 1 if source.get("clearing", False) else 0
+    p.inf_is_valid = 1 if source.get("inf_is_valid", False) else 0
+    clear = block.get("footprint_clearing_enabled", True) and _is_number(tree.get("robot_radius"))
+    p.footprint_clear_radius = float(tree["robot_radius"]) if clear else 0.0
+    for key, value in (scan or {}).items():
+        if key == "sensor_pose":
+            p.sensor_pose[0], p.sensor_pose[1], p.sensor_pose[2] = (float(v) for v in value)
+        elif key in ("angle_min", "angle_increment", "range_min", "range_max"):
+            setattr(p, key, float(value))
+        else:
+            raise ParamNotImplemented(f"scan: {key} (angle_min, angle_increment, range_min, range_max and sensor_pose are read)")
+    return p
+
+
+def _lib_defaults_scan(p):
+    """mpc_scan_params_defaults, restated so that reading a parameter file needs no library: include/mpc_costmap_scans.h states the values"""
+    p.lattice_anchor[0] = p.lattice_anchor[1] = 0.0
+    p.sensor_pose[0] = p.sensor_pose[1] = p.sensor_pose[2] = 0.0
+    p.angle_min, p.angle_increment = -math.pi, 2.0 * math.pi / 360.0
+    p.range_min, p.range_max, p.obstacle_range, p.raytrace_range, p.footprint_clear_radius = 0.0, 30.0, 2.5, 3.0, 0.0
+    p.marking, p.clearing, p.inf_is_valid, p.track_unknown, p.combination_method = 1, 1, 0, 0, 1
+
+
 def static_layer_costs(occupancy, lethal_threshold=100, unknown_cost_value=-1, track_unknown_space=True, trinary_costmap=True):
     """costmap_2d::StaticLayer::interpretValue in numpy (restated from costmap_2d's published static_layer.cpp): a map server's occupancy values (-1 unknown,
     0 .. 100) -> the costmap bytes mpc_costmap_window's map holds.  The value is read as an unsigned char, as the layer does: the unknown value is 255 with

@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._abi import MpcClusterParams, MpcConfig, MpcLineParams, MpcCycleParams, MpcEvalOut, MpcObstacles, MpcPlanParams, MpcPool, MpcPoolParams, MpcWindowParams, MPC_OK
+from ._abi import MpcClusterParams, MpcConfig, MpcLineParams, MpcCycleParams, MpcEvalOut, MpcObstacles, MpcPlanParams, MpcPool, MpcPoolParams, MpcScanParams, MpcWindowParams, MPC_OK
 
 
 class MpcError(RuntimeError):
@@ -72,6 +72,11 @@ def _addr(a):
 def _dev(p):
     """a device address (int), 0 / None -> NULL"""
     return C.c_void_p(p) if p else None
+
+
+def _floats(p):
+    """a float array at an address (int; host or device), as the tables bind `const float*`; 0 / None -> NULL"""
+    return C.cast(C.c_void_p(p), C.POINTER(C.c_float)) if p else None
 
 
 def _as_f64(a, shape):
@@ -525,6 +530,39 @@ class BatchSolver:
         cycle; cost and origin are written in full"""
         self._check(self._lib.mpc_costmap_window_device(self._h, int(B), _dev(map_cost), C.byref(params), _dev(robot_pose), int(size_x), int(size_y), float(resolution),
                                                         _dev(cost), _dev(origin), _dev(info)))
+
+    def scan_params(self, **fields) -> MpcScanParams:
+        """mpc_scan_params with the library's defaults (mpc_scan_params_defaults), then the given fields (lattice_anchor as a pair, sensor_pose as a triple)"""
+        sized = {"lattice_anchor": 2, "sensor_pose": 3}
+        fields = {k: (C.c_double * sized[k])(*map(float, v)) if k in sized else v for k, v in fields.items()}
+        return _params("mpc_scan_params", MpcScanParams, self._lib.mpc_scan_params_defaults, fields)
+
+    def costmap_scans(self, params: MpcScanParams, robot_pose, ranges, size, resolution, layer=None, layer_cell=None, keep=None, cost=None, want_info=True):
+        """One cycle of every robot's laser-scan obstacle layer (mpc_costmap_scans, include/mpc_costmap_scans.h): the layer rolled with the window, cleared along the
+        rays, marked at the returns, and combined into the windows costmap_window made.  robot_pose (B, 3); ranges float32 (B, n_beams); size = (size_x, size_y) in
+        cells; layer uint8 (B, size_y, size_x) and layer_cell int32 (B, 2) are the state of the previous cycle (None: a first cycle, which needs no keep); keep (B,)
+        says which instances keep theirs (None: none does); cost uint8 (B, size_y, size_x) or None.  Nothing passed in is changed.
+        Returns (layer, layer_cell, cost or None, info (B, 4) = beams kept, marked cells, free cells, window cells changed; None without want_info)."""
+        pose = np.ascontiguousarray(robot_pose, dtype=np.float64).reshape(-1, 3)
+        B, (sx, sy) = pose.shape[0], (int(size[0]), int(size[1]))
+        rng = np.ascontiguousarray(ranges, dtype=np.float32).reshape(B, -1)
+        shape = (B, max(sy, 0), max(sx, 0))
+        if (layer is None) != (layer_cell is None) or (layer is None and keep is not None):
+            raise ValueError("layer and layer_cell come together, and keep needs them")
+        layer = np.zeros(shape, np.uint8) if layer is None else np.array(layer, dtype=np.uint8).reshape(shape)
+        layer_cell = np.zeros((B, 2), np.int32) if layer_cell is None else np.array(layer_cell, dtype=np.int32).reshape(B, 2)
+        cost = None if cost is None else np.array(cost, dtype=np.uint8).reshape(shape)
+        info = np.zeros((B, 4), np.int32) if want_info else None
+        self._check(self._lib.mpc_costmap_scans(self._h, B, C.byref(params), _addr(pose), _floats(rng.ctypes.data), int(rng.shape[1]), _addr(_as_i32(keep, B, "keep")), sx, sy,
+                                                float(resolution), _addr(layer), _addr(layer_cell), _addr(cost), _addr(info)))
+        return layer, layer_cell, cost, info
+
+    def costmap_scans_device(self, B: int, params: MpcScanParams, robot_pose: int, ranges: int, n_beams: int, keep: Optional[int], size_x: int, size_y: int,
+                             resolution: float, layer: int, layer_cell: int, cost: Optional[int] = None, info: Optional[int] = None) -> None:
+        """mpc_costmap_scans_device: the same with device addresses (ints), asynchronous on the solver's stream, between costmap_window_device and the costmap
+        converters of the fleet cycle; layer and layer_cell are the caller's and are rolled in place, cost is combined in place"""
+        self._check(self._lib.mpc_costmap_scans_device(self._h, int(B), C.byref(params), _dev(robot_pose), _floats(ranges), int(n_beams), _dev(keep), int(size_x), int(size_y),
+                                                       float(resolution), _dev(layer), _dev(layer_cell), _dev(cost), _dev(info)))
 
     def last_costmap_ms(self) -> float:
         """device milliseconds of the most recent costmap step (mpc_last_costmap_ms), 0 when there has been none"""

@@ -1,0 +1,79 @@
+/* mpc_scan_cast.h -- the laser scan of every planner instance of a batch, cast on the device through one shared map and through a pool of other bodies: the array
+ * ranges [B][n_beams] that mpc_costmap_scans_device takes, made where it is used.
+ *
+ *     mpc_scan_cast_device             (one map on the device, B robot poses, optionally the fleet's pool -> B laser scans)
+ *  -> mpc_costmap_window_device        (the same map, the same poses -> B windows and their origins)
+ *  -> mpc_costmap_scans_device         (the B scans -> B obstacle layers rolled, cleared, marked, and combined into the windows)
+ *  -> mpc_costmap_to_obstacles_device | mpc_costmap_to_polygons_device | mpc_costmap_to_lines_device -> ... (include/mpc_costmap_window.h has the whole cycle)
+ *  -> mpc_fleet_pool_device            (include/mpc_fleet.h: the poses of this cycle -> the pool the next cycle's cast sees)
+ *
+ * Every demo of the reference takes its scan from the Stage simulator: ex/stage/robots/carlike_robot.inc and diff_drive_robot.inc define a `ranger` with range_max 6.5,
+ * fov 58.0, samples 640 at pose [-0.1 0.0 ...], and the ex/stage/ world files set laser_return 1 on the map and on the other robots.  Stage is not part of the
+ * reference's tree; what restates it (a beam without a return reports range_max) cannot be verified here.  The rest is a rule OF OURS: an exact traversal of the
+ * map's cells with no marching step, a return reported at the middle of the beam's chord through the blocking cell, discs and closed polygons for the pool.
+ * OUT OF SCOPE, and so visible deviations from Stage: no sensor noise, not Stage's own 0.02 m ray resolution, one sensor per robot, the plant step stays the
+ * caller's, and marks made from these ranges are not inflated.  The rule is stated in full in mpc_local_planner_amd/csrc/mpc_scan_cast.hpp.
+ *
+ * The functions live in the same library as include/mpc_hip.h's and are built with it; they are declared here, apart from that header, whose set of declarations and
+ * mpc_version stay as they are.  Callers that load the library at run time find them with dlsym under the names below.  mpc_last_costmap_ms
+ * (include/mpc_costmap_clusters.h) reports this step too.
+ */
+#ifndef MPC_SCAN_CAST_H
+#define MPC_SCAN_CAST_H
+
+#include "mpc_fleet.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct mpc_cast_params {
+    double  map_origin[2];           /* the same map description as mpc_window_params: the world position of the corner of cell (0, 0) */
+    double  map_resolution;
+    double  sensor_pose[3];          /* x, y, yaw of the scanner in the robot frame, one for the whole batch, as mpc_scan_params */
+    double  angle_min, angle_increment;
+    double  range_max;               /* nothing at or beyond it returns */
+    int32_t map_size_x, map_size_y;
+    int32_t block_threshold;         /* a map byte v blocks when block_threshold <= v <= 254 */
+    int32_t unknown_blocks;          /* non-zero: 255 blocks too */
+    int32_t hit_point;               /* 0: where the beam enters the blocking cell; 1: the middle of its chord through that cell */
+    int32_t miss_is_inf;             /* a beam without a return: 1: +inf, 0: (float)range_max, as Stage reports it */
+} mpc_cast_params;
+
+/* map_origin = (0, 0), the given map geometry, sensor_pose = (0, 0, 0), angle_min = -pi, angle_increment = 2 pi / 360, range_max = 6.5, block_threshold = 254,
+ * unknown_blocks = 0, hit_point = 1, miss_is_inf = 1. */
+void mpc_cast_params_defaults(mpc_cast_params* p, double map_resolution, int32_t map_size_x, int32_t map_size_y);
+
+/* Per instance b (map [map_size_y][map_size_x] bytes, shared; robot_pose [B][3], all three read; pool: NULL or a host struct (include/mpc_fleet.h) laid out with
+ * V = cfg.max_vertices, velocity not read; self_index [B] or NULL; ranges [B][n_beams] float; hit [B][n_beams] or NULL; info [B][4] or NULL):
+ *   1. geometry: as mpc_costmap_scans reads a scan: the sensor at pose_xy + R(wrap(yaw)) * sensor_xy, beam k along wrap(((yaw + sensor_yaw) + angle_min) +
+ *      k * angle_increment).  A pose that is not finite or a heading that does not wrap: every beam misses, info = {-1, 0, 0, 0}.  A beam angle that does not wrap: a miss.
+ *   2. map: with u = (sensor_x - map_origin_x) / map_resolution and v likewise, the beam is followed from cell (floor(u), floor(v)) across every cell boundary it
+ *      crosses, exactly: the crossing of the next boundary is ((c > 0 ? i + 1 : i) - u) * (1 / c) in cells, from the integer index every time, the nearer axis is
+ *      stepped, x on a tie.  The walk ends without a return when the crossing times map_resolution is not below range_max, or leaves the map.  A blocking cell ends
+ *      it with t = the crossing it was entered at (hit_point 0) or the mean of that and the crossing it would be left at (hit_point 1); r_map = t * map_resolution.  A
+ *      sensor in a blocking cell: r_map = 0.  A sensor off the map: no return from the map.
+ *   3. pool: entry p is skipped when n_vertices[p] < 1, p == self_index[b], a valid vertex is not finite, or (a disc) its radius is not finite.  One vertex and
+ *      radius > 0: a disc, t = the nearer root of the ray with the circle, 0 for a sensor inside it.  Two vertices: a segment; three or more: the closed polygon; the
+ *      radius is ignored.  r_pool is the smallest t, ties to the lower p.
+ *   4. result: r = min(r_map, r_pool), the map winning a tie; a return when r < range_max: ranges = (float)r, hit = -2 (the map) or p.  Otherwise ranges = +inf
+ *      (miss_is_inf) or (float)range_max, hit = -1.
+ *   5. info[b] = {beams returned by the map, by a pool entry, without a return, blocking map cells within Rc = ceil(range_max / map_resolution) + 1 cells of the sensor's
+ *      cell on either axis (0 for a sensor off the map)}.
+ * The result does not depend on the order of the beams or pool entries, on B, on the position in the batch or on the run, and equals a host build of
+ * mpc_local_planner_amd/csrc/mpc_scan_cast.hpp bit for bit.
+ * DEVICE pointers (pool: a host struct with device pointers inside), on the solver's stream, no synchronisation: d_ranges goes straight into mpc_costmap_scans_device.
+ * MPC_EINVAL: a null required pointer (s, d_map, params, d_robot_pose, d_ranges); n_beams below 1 or above 4096; map_size_x or map_size_y below 1 or their product above
+ * 2^31 - 1; a map_resolution or range_max that is not positive and finite; a map_origin, sensor_pose, angle_min or angle_increment that is not finite; Rc above 351 (the
+ * blocking cells of the (2 Rc + 1)^2 square stay as bits in the 64 KB of LDS of one workgroup: 703 rows of 11 words); block_threshold outside 1 .. 254; pool->P < 0, or
+ * pool->P > 0 without n_vertices and vertices.  MPC_EBATCH: B above max_batch.  A refused call changes nothing. */
+int mpc_scan_cast_device(mpc_solver* s, int32_t B, const uint8_t* d_map, const mpc_cast_params* params, const double* d_robot_pose, const mpc_pool* pool,
+                         const int32_t* d_self_index, int32_t n_beams, float* d_ranges, int32_t* d_hit, int32_t* d_info);
+/* Same with HOST pointers (pool: host pointers inside), staged through the handle's buffers; blocking. */
+int mpc_scan_cast(mpc_solver* s, int32_t B, const uint8_t* map, const mpc_cast_params* params, const double* robot_pose, const mpc_pool* pool,
+                  const int32_t* self_index, int32_t n_beams, float* ranges, int32_t* hit, int32_t* info);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -385,6 +385,41 @@ LATER_HEADERS = {
 }
 
 
+class MpcCastParams(C.Structure):
+    """struct mpc_cast_params (include/mpc_scan_cast.h); field-for-field."""
+    _fields_ = [
+        ("map_origin", C.c_double * 2),
+        ("map_resolution", C.c_double),
+        ("sensor_pose", C.c_double * 3),
+        ("angle_min", C.c_double),
+        ("angle_increment", C.c_double),
+        ("range_max", C.c_double),
+        ("map_size_x", C.c_int32),
+        ("map_size_y", C.c_int32),
+        ("block_threshold", C.c_int32),
+        ("unknown_blocks", C.c_int32),
+        ("hit_point", C.c_int32),
+        ("miss_is_inf", C.c_int32),
+    ]
+
+
+# ---- include/mpc_scan_cast.h
+# s, B, map, params, robot_pose, pool, self_index, n_beams, ranges, hit, info
+_CAST = (_rc, [_p, _i, _p, C.POINTER(MpcCastParams), _p, C.POINTER(MpcPool), _p, _i, C.POINTER(C.c_float), _p, _p])
+
+CAST_PROTOTYPES = {
+    "mpc_cast_params_defaults": (None, [C.POINTER(MpcCastParams), _d, _i, _i]),                  # p, map_resolution, map_size_x, map_size_y
+    "mpc_scan_cast": _CAST, "mpc_scan_cast_device": _CAST,
+}
+
+# The registry that stays open: tests/test_abi.py pins HEADERS and tests/test_costmap_scans_abi.py pins LATER_HEADERS to the rows they were written for, so a header
+# that comes after them is a row HERE, bound by _lib.load() in the same loop; its own test module holds the row to its header and does not count the others.  A row's
+# mirrors are the structs its declarations name that mpc_hip.h does not have: the header's own and, for this one, mpc_fleet.h's pool.
+OPEN_HEADERS = {
+    "mpc_scan_cast.h": (CAST_PROTOTYPES, {"mpc_cast_params": MpcCastParams, "mpc_pool": MpcPool}),
+}
+
+
 def _diag_offdiag(w, dim):
     """a weight given as its diagonal or as a full dim x dim matrix -> (diagonal, off-diagonal terms (0,1)[, (0,2), (1,2)] of the symmetric part)"""
     rows = [list(r) if hasattr(r, "__len__") else None for r in w]

@@ -11,7 +11,7 @@ import shutil
 import subprocess
 
 from . import _build
-from ._abi import HEADERS, LATER_HEADERS, PROTOTYPES
+from ._abi import HEADERS, LATER_HEADERS, OPEN_HEADERS, PROTOTYPES
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.path.join(CSRC, "libmpc_hip.so")
@@ -91,7 +91,7 @@ _lib = None
 
 
 def load() -> C.CDLL:
-    """dlopen the C-ABI library and declare the prototypes of every header of _abi.HEADERS and _abi.LATER_HEADERS, once."""
+    """dlopen the C-ABI library and declare the prototypes of every header of _abi.HEADERS, _abi.LATER_HEADERS and _abi.OPEN_HEADERS, once."""
     global _lib
     if _lib is not None:
         return _lib
@@ -101,7 +101,7 @@ def load() -> C.CDLL:
             f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
     lib = C.CDLL(path)
-    for table, _ in list(HEADERS.values()) + list(LATER_HEADERS.values()):
+    for table, _ in list(HEADERS.values()) + list(LATER_HEADERS.values()) + list(OPEN_HEADERS.values()):
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes

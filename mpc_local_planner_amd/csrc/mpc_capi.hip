@@ -17,6 +17,7 @@
 #include "../../include/mpc_costmap_lines.h"
 #include "../../include/mpc_costmap_window.h"
 #include "../../include/mpc_costmap_scans.h"
+#include "../../include/mpc_scan_cast.h"
 #include "mpc_core.hpp"
 #include "mpc_problem.hpp"
 #include "mpc_launch_plan.hpp"
@@ -33,6 +34,7 @@
 #include "mpc_costmap_lines.hpp"
 #include "mpc_costmap_window.hpp"
 #include "mpc_costmap_scans.hpp"
+#include "mpc_scan_cast.hpp"
 
 namespace {
 
@@ -1658,6 +1660,90 @@ int mpc_costmap_scans(mpc_solver* s, int32_t B, const mpc_scan_params* params, c
     return staged_call(s, "mpc_costmap_scans", true, true, pc, 7, [&](void** d) -> int {
         return mpc_costmap_scans_device(s, B, params, (const double*)d[0], (const float*)d[1], n_beams, (const int32_t*)d[2], size_x, size_y, resolution, (uint8_t*)d[3],
                                         (int32_t*)d[4], (uint8_t*)d[5], (int32_t*)d[6]);
+    });
+}
+
+}  // extern "C"
+
+// ---- the laser scans of a batch, cast through the shared map and the pool (mpc_scan_cast.hpp; declared in include/mpc_scan_cast.h)
+
+// the argument checks of both variants, in the order of rule 6: true with mpc_last_error set when the call is refused; Rc: rule 5's reach in cells
+static bool cast_error(const char* who, const mpc_solver* s, const void* map, const mpc_cast_params* p, const void* robot_pose, const mpc_pool* pool, int32_t n_beams,
+                       const void* ranges, int& Rc) {
+    auto pos_finite = [](double v) { return v > 0.0 && std::isfinite(v); };
+    if (!s || !map || !p || !robot_pose || !ranges) return costmap_no(who, "null argument (map, params, robot_pose, ranges)");
+    if (n_beams < 1 || n_beams > mpc::kScMaxBeams) return costmap_no(who, "n_beams has to be in [1, 4096]");
+    if (p->map_size_x < 1 || p->map_size_y < 1 || (long long)p->map_size_x * p->map_size_y > 2147483647LL) return costmap_no(who, "bad map size (at least 1 x 1, at most 2^31 - 1 bytes)");
+    if (!pos_finite(p->map_resolution) || !pos_finite(p->range_max)) return costmap_no(who, "map_resolution and range_max have to be positive and finite");
+    if (!std::isfinite(p->map_origin[0]) || !std::isfinite(p->map_origin[1]) || !std::isfinite(p->angle_min) || !std::isfinite(p->angle_increment) ||
+        !std::isfinite(p->sensor_pose[0]) || !std::isfinite(p->sensor_pose[1]) || !std::isfinite(p->sensor_pose[2]))
+        return costmap_no(who, "map_origin, sensor_pose, angle_min and angle_increment have to be finite");
+    Rc = mpc::sc_cells(p->range_max, p->map_resolution);
+    if (Rc < 0) return costmap_no(who, "range_max has to be at most 350 cells of the map (the blocking cells around the sensor stay in the LDS of one workgroup)");
+    if (p->block_threshold < 1 || p->block_threshold > 254) return costmap_no(who, "block_threshold has to be in [1, 254]");
+    if (pool && pool->P < 0) return costmap_no(who, "pool: P is negative");
+    return costmap_no(who, pool && pool->P > 0 && (!pool->n_vertices || !pool->vertices) ? "pool: n_vertices and vertices are needed with P > 0" : nullptr);
+}
+
+extern "C" {
+
+void mpc_cast_params_defaults(mpc_cast_params* p, double map_resolution, int32_t map_size_x, int32_t map_size_y) {
+    if (!p) return;
+    p->map_origin[0] = p->map_origin[1] = 0.0;
+    p->map_resolution = map_resolution;
+    p->sensor_pose[0] = p->sensor_pose[1] = p->sensor_pose[2] = 0.0;
+    p->angle_min = -3.14159265358979323846;
+    p->angle_increment = 2.0 * 3.14159265358979323846 / 360.0;
+    p->range_max = 6.5;
+    p->map_size_x = map_size_x; p->map_size_y = map_size_y;
+    p->block_threshold = 254;
+    p->unknown_blocks = 0;
+    p->hit_point = 1;
+    p->miss_is_inf = 1;
+}
+
+int mpc_scan_cast_device(mpc_solver* s, int32_t B, const uint8_t* d_map, const mpc_cast_params* params, const double* d_robot_pose, const mpc_pool* pool,
+                         const int32_t* d_self_index, int32_t n_beams, float* d_ranges, int32_t* d_hit, int32_t* d_info) {
+    g_err[0] = 0;
+    int Rc = 0;
+    if (cast_error("mpc_scan_cast", s, d_map, params, d_robot_pose, pool, n_beams, d_ranges, Rc)) return MPC_EINVAL;
+    if (B <= 0) return MPC_OK;
+    if (const int rc = refused(s, B, REF_MAX_BATCH, "mpc_scan_cast")) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    mpc::CastArgs a;
+    memset(&a, 0, sizeof(a));
+    a.map = d_map; a.pose = d_robot_pose; a.self_index = d_self_index; a.ranges = d_ranges; a.hit = d_hit; a.info = d_info;
+    if (pool && pool->P > 0) a.pool = {pool->P, pool->n_vertices, pool->vertices, pool->radius, nullptr};
+    a.p = {params->map_origin[0], params->map_origin[1], params->map_resolution, params->sensor_pose[0], params->sensor_pose[1], params->sensor_pose[2], params->angle_min,
+           params->angle_increment, params->range_max, params->map_size_x, params->map_size_y, params->block_threshold, params->unknown_blocks ? 1 : 0,
+           params->hit_point ? 1 : 0, params->miss_is_inf ? 1 : 0, Rc};
+    a.n_beams = n_beams; a.V = s->cfg.max_vertices > 0 ? s->cfg.max_vertices : 1;
+    const size_t lds = mpc::sc_lds_bytes(Rc);      // the bitmap of the square around the sensor, the culled list and the counts: at most 64 KB
+    if (lds > 48u * 1024u) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(mpc::scan_cast_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIP_TRY(hipEventRecord(s->cev0, s->stream));
+    hipLaunchKernelGGL(mpc::scan_cast_kernel, dim3((unsigned)B), dim3(mpc::kScThreads), lds, s->stream, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(s->cev1, s->stream));
+    s->ctimed = true;
+    return MPC_OK;
+}
+
+int mpc_scan_cast(mpc_solver* s, int32_t B, const uint8_t* map, const mpc_cast_params* params, const double* robot_pose, const mpc_pool* pool, const int32_t* self_index,
+                  int32_t n_beams, float* ranges, int32_t* hit, int32_t* info) {
+    g_err[0] = 0;
+    int Rc = 0;
+    if (cast_error("mpc_scan_cast", s, map, params, robot_pose, pool, n_beams, ranges, Rc)) return MPC_EINVAL;
+    if (B <= 0) return MPC_OK;
+    if (const int rc = refused(s, B, REF_MAX_BATCH, "mpc_scan_cast")) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t nb = (size_t)B, V = s->cfg.max_vertices > 0 ? s->cfg.max_vertices : 1, np = pool && pool->P > 0 ? (size_t)pool->P : 0;
+    const mpc::StagePiece pc[9] = {stage_in(map, (size_t)params->map_size_x * params->map_size_y), stage_in(robot_pose, nb * 24), stage_in(np ? pool->n_vertices : nullptr, np * 4),
+                                   stage_in(np ? pool->vertices : nullptr, np * V * 16), stage_in(np ? pool->radius : nullptr, np * 8), stage_in(self_index, nb * 4),
+                                   stage_out(ranges, nb * (size_t)n_beams * 4), stage_out(hit, nb * (size_t)n_beams * 4), stage_out(info, nb * 16)};
+    return staged_call(s, "mpc_scan_cast", true, true, pc, 9, [&](void** d) -> int {
+        const mpc_pool dp = {(int32_t)np, (const int32_t*)d[2], (const double*)d[3], (const double*)d[4], nullptr};
+        return mpc_scan_cast_device(s, B, (const uint8_t*)d[0], params, (const double*)d[1], np ? &dp : nullptr, (const int32_t*)d[5], n_beams, (float*)d[6], (int32_t*)d[7],
+                                    (int32_t*)d[8]);
     });
 }
 

@@ -135,6 +135,18 @@ MPC_CM_HD double cs_cell(double w, double origin, double res) {
 }
 MPC_CM_HD bool cs_inside(double cell, int size) { return cell >= 0.0 && cell < (double)size; }
 
+// rule 3: the sensor of a robot at (px, py) with the wrapped heading th: pose_xy + R(th) * sensor_xy, every product and sum rounded on its own (mpc_scan_cast.hpp
+// places its sensor by the same lines)
+MPC_CM_HD void cs_place_sensor(double px, double py, double th, double sensor_x, double sensor_y, double& sx, double& sy) {
+#pragma clang fp contract(off)
+    double sn, cs;
+    cs_sincos(th, sn, cs);
+    const double xa = cs * sensor_x, xb = sn * sensor_y, ya = sn * sensor_x, yb = cs * sensor_y;
+    const double rx = xa - xb, ry = ya + yb;
+    sx = px + rx;
+    sy = py + ry;
+}
+
 // what the instance's beams share: the origin and the sensor (rule 3), the sensor's cell when it lies in the window (rule 4)
 struct ScanFrame {
     double ox, oy, sx, sy;
@@ -154,12 +166,7 @@ MPC_CM_HD ScanFrame cs_frame(const ScanParams& p, const double* pose, int W, int
     const double th = cs_wrap(pose[2]);
     f.heading = cs_wrapped(th);
     if (!f.heading) return f;
-    double sn, cs;
-    cs_sincos(th, sn, cs);
-    const double xa = cs * p.sensor_x, xb = sn * p.sensor_y, ya = sn * p.sensor_x, yb = cs * p.sensor_y;
-    const double rx = xa - xb, ry = ya + yb;
-    f.sx = pose[0] + rx;
-    f.sy = pose[1] + ry;
+    cs_place_sensor(pose[0], pose[1], th, p.sensor_x, p.sensor_y, f.sx, f.sy);
     const double fx = cs_cell(f.sx, f.ox, p.res), fy = cs_cell(f.sy, f.oy, p.res);
     f.sensor_in = cs_inside(fx, W) && cs_inside(fy, H);
     if (f.sensor_in) { f.scx = (int32_t)fx; f.scy = (int32_t)fy; }

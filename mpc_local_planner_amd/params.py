@@ -619,6 +619,27 @@ def _lib_defaults_scan(p):
     p.marking, p.clearing, p.inf_is_valid, p.track_unknown, p.combination_method = 1, 1, 0, 0, 1
 
 
+def cast_params_from_ranger(fov_deg, samples, range_max, sensor_pose, map_resolution, map_shape):
+    """struct mpc_cast_params (mpc_scan_cast*, BatchSolver.scan_cast_device) from the numbers of a Stage `ranger` block (ex/stage/robots/*.inc: range_max, fov in
+    degrees, samples, and pose [x y z yaw in degrees], of which sensor_pose = (x, y, yaw in radians) is given here) and the map's geometry, map_shape =
+    (map_size_y, map_size_x).  angle_min = -fov / 2 and angle_increment = fov / (samples - 1), in radians: as stage_ros is BELIEVED to fill its LaserScan (it is not part
+    of the reference's tree).  One sample looks straight ahead.  The other fields keep the library's defaults, restated here so that reading a robot file needs no
+    library: include/mpc_scan_cast.h states the values."""
+    samples = int(samples)
+    if samples < 1:
+        raise ValueError("a ranger has at least one sample")
+    fov = math.radians(float(fov_deg))
+    p = A.MpcCastParams()
+    p.map_origin[0] = p.map_origin[1] = 0.0
+    p.map_resolution = float(map_resolution)
+    p.sensor_pose[0], p.sensor_pose[1], p.sensor_pose[2] = (float(v) for v in sensor_pose)
+    p.angle_min, p.angle_increment = (-fov / 2, fov / (samples - 1)) if samples > 1 else (0.0, 0.0)
+    p.range_max = float(range_max)
+    p.map_size_x, p.map_size_y = int(map_shape[1]), int(map_shape[0])
+    p.block_threshold, p.unknown_blocks, p.hit_point, p.miss_is_inf = 254, 0, 1, 1
+    return p
+
+
 def static_layer_costs(occupancy, lethal_threshold=100, unknown_cost_value=-1, track_unknown_space=True, trinary_costmap=True):
     """costmap_2d::StaticLayer::interpretValue in numpy (restated from costmap_2d's published static_layer.cpp): a map server's occupancy values (-1 unknown,
     0 .. 100) -> the costmap bytes mpc_costmap_window's map holds.  The value is read as an unsigned char, as the layer does: the unknown value is 255 with

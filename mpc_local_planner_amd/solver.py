@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._abi import MpcClusterParams, MpcConfig, MpcLineParams, MpcCycleParams, MpcEvalOut, MpcObstacles, MpcPlanParams, MpcPool, MpcPoolParams, MpcScanParams, MpcWindowParams, MPC_OK
+from ._abi import MpcCastParams, MpcClusterParams, MpcConfig, MpcLineParams, MpcCycleParams, MpcEvalOut, MpcObstacles, MpcPlanParams, MpcPool, MpcPoolParams, MpcScanParams, MpcWindowParams, MPC_OK
 
 
 class MpcError(RuntimeError):
@@ -563,6 +563,46 @@ class BatchSolver:
         converters of the fleet cycle; layer and layer_cell are the caller's and are rolled in place, cost is combined in place"""
         self._check(self._lib.mpc_costmap_scans_device(self._h, int(B), C.byref(params), _dev(robot_pose), _floats(ranges), int(n_beams), _dev(keep), int(size_x), int(size_y),
                                                        float(resolution), _dev(layer), _dev(layer_cell), _dev(cost), _dev(info)))
+
+    def cast_params(self, map_resolution, map_shape, **fields) -> MpcCastParams:
+        """mpc_cast_params with the library's defaults (mpc_cast_params_defaults) for a map of map_shape = (map_size_y, map_size_x) cells, then the given fields
+        (map_origin as a pair, sensor_pose as a triple)"""
+        sized = {"map_origin": 2, "sensor_pose": 3}
+        fields = {k: (C.c_double * sized[k])(*map(float, v)) if k in sized else v for k, v in fields.items()}
+        return _params("mpc_cast_params", MpcCastParams,
+                       lambda p: self._lib.mpc_cast_params_defaults(p, float(map_resolution), int(map_shape[1]), int(map_shape[0])), fields)
+
+    def scan_cast(self, map_cost, params: MpcCastParams, robot_pose, n_beams, pool=None, self_index=None):
+        """The laser scan of every robot, cast through one shared map and a pool of other bodies (mpc_scan_cast, include/mpc_scan_cast.h): the ranges costmap_scans
+        takes.  map_cost: uint8 (map_size_y, map_size_x) in costmap values; robot_pose (B, 3); pool = (n_vertices (P,), vertices (P, V, 2)[, radius (P,)]) as
+        obstacles_from_pool and fleet_pool have it (a velocity behind them is not read), or None; self_index (B,): the pool entry that is the robot itself (None: none).
+        Returns (ranges float32 (B, n_beams), hit int32 (B, n_beams): -2 the map, p a pool entry, -1 no return, info (B, 4) = beams returned by the map, by the pool,
+        without a return, blocking map cells around the sensor)."""
+        m = np.ascontiguousarray(map_cost, dtype=np.uint8)
+        if m.shape != (params.map_size_y, params.map_size_x):
+            raise ValueError(f"map_cost has shape {m.shape}, params say {(params.map_size_y, params.map_size_x)}")
+        pose = np.ascontiguousarray(robot_pose, dtype=np.float64).reshape(-1, 3)
+        B, n, V = pose.shape[0], int(n_beams), max(1, int(self.cfg.max_vertices))
+        cp = None
+        if pool is not None:
+            pnv = np.ascontiguousarray(pool[0], dtype=np.int32).reshape(-1)
+            P = int(pnv.shape[0])
+            pv = _as_f64(pool[1], (P, V, 2))
+            pr = _as_f64(pool[2], (P,)) if len(pool) > 2 and pool[2] is not None else None
+            cp = MpcPool(P, *(a.ctypes.data if a is not None and P > 0 else None for a in (pnv, pv, pr)), None)
+        si = _as_i32(self_index, B, "self_index")
+        ranges, hit, info = np.zeros((B, max(n, 0)), np.float32), np.zeros((B, max(n, 0)), np.int32), np.zeros((B, 4), np.int32)
+        self._check(self._lib.mpc_scan_cast(self._h, B, _addr(m), C.byref(params), _addr(pose), None if cp is None else C.byref(cp), _addr(si), n, _floats(ranges.ctypes.data),
+                                            _addr(hit), _addr(info)))
+        return ranges, hit, info
+
+    def scan_cast_device(self, B: int, map_cost: int, params: MpcCastParams, robot_pose: int, n_beams: int, ranges: int, pool=None, self_index: Optional[int] = None,
+                         hit: Optional[int] = None, info: Optional[int] = None) -> None:
+        """mpc_scan_cast_device: the same with device addresses (ints), asynchronous on the solver's stream, in front of costmap_window_device and
+        costmap_scans_device, which takes `ranges` as it is; pool = (P, n_vertices, vertices[, radius]) with device addresses, or None"""
+        cp = None if pool is None else MpcPool(int(pool[0]), *((tuple(a or None for a in pool[1:4]) + (None,) * 4)[:4]))
+        self._check(self._lib.mpc_scan_cast_device(self._h, int(B), _dev(map_cost), C.byref(params), _dev(robot_pose), None if cp is None else C.byref(cp), _dev(self_index),
+                                                   int(n_beams), _floats(ranges), _dev(hit), _dev(info)))
 
     def last_costmap_ms(self) -> float:
         """device milliseconds of the most recent costmap step (mpc_last_costmap_ms), 0 when there has been none"""

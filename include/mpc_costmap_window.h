@@ -7,7 +7,8 @@
  *  or mpc_costmap_to_polygons_device   (one point, line or convex polygon per cluster of lethal cells)
  *  or mpc_costmap_to_lines_device      (line segments along the walls of a cluster, points for what is left)
  *  -> mpc_obstacles_from_pool_device (append) -> mpc_plan_inputs_batch_device -> mpc_controller_step_batch_device -> mpc_check_feasibility_device
- *  -> mpc_commands_batch_device -> mpc_fleet_pool_device -> [next cycle] mpc_costmap_window_device ...
+ *  -> mpc_commands_batch_device -> mpc_plant_step_device (optional, include/mpc_plant.h: simulated robots moved by their commands) -> mpc_fleet_pool_device
+ *  -> [next cycle] mpc_costmap_window_device ...
  *
  * In the shipped demos the local costmap is a rolling window (cfg/<robot>/local_costmap_params.yaml: rolling_window true, width / height 5.5, resolution 0.1, a StaticLayer)
  * over one static map (maps/<name>.yaml, 0.05 m per cell).  A fleet shares that map: it is uploaded once, and a window is a gather plus, optionally, an inflation.

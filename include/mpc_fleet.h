@@ -8,6 +8,7 @@
  *
  * The fleet cycle on device memory:
  *     mpc_controller_step_batch_device -> mpc_check_feasibility_device -> mpc_commands_batch_device
+ *  -> mpc_plant_step_device            (optional, include/mpc_plant.h: simulated robots moved by their commands, stalled by the map and by this pool)
  *  -> mpc_fleet_pool_device            (poses and first plan intervals of this cycle -> pool entries)
  *  -> [next cycle] mpc_costmap_to_obstacles_device -> mpc_obstacles_from_pool_device (append) -> mpc_controller_step_batch_device ...
  */

@@ -5,14 +5,15 @@
  *  -> mpc_costmap_window_device        (the same map, the same poses -> B windows and their origins)
  *  -> mpc_costmap_scans_device         (the B scans -> B obstacle layers rolled, cleared, marked, and combined into the windows)
  *  -> mpc_costmap_to_obstacles_device | mpc_costmap_to_polygons_device | mpc_costmap_to_lines_device -> ... (include/mpc_costmap_window.h has the whole cycle)
+ *  -> mpc_plant_step_device            (optional, include/mpc_plant.h: the commands of this cycle -> the next poses of simulated robots)
  *  -> mpc_fleet_pool_device            (include/mpc_fleet.h: the poses of this cycle -> the pool the next cycle's cast sees)
  *
  * Every demo of the reference takes its scan from the Stage simulator: ex/stage/robots/carlike_robot.inc and diff_drive_robot.inc define a `ranger` with range_max 6.5,
  * fov 58.0, samples 640 at pose [-0.1 0.0 ...], and the ex/stage/ world files set laser_return 1 on the map and on the other robots.  Stage is not part of the
  * reference's tree; what restates it (a beam without a return reports range_max) cannot be verified here.  The rest is a rule OF OURS: an exact traversal of the
  * map's cells with no marching step, a return reported at the middle of the beam's chord through the blocking cell, discs and closed polygons for the pool.
- * OUT OF SCOPE, and so visible deviations from Stage: no sensor noise, not Stage's own 0.02 m ray resolution, one sensor per robot, the plant step stays the
- * caller's, and marks made from these ranges are not inflated.  The rule is stated in full in mpc_local_planner_amd/csrc/mpc_scan_cast.hpp.
+ * OUT OF SCOPE, and so visible deviations from Stage: no sensor noise, not Stage's own 0.02 m ray resolution, one sensor per robot, this step does not move
+ * the plant (include/mpc_plant.h does), and marks made from these ranges are not inflated.  The rule is stated in full in mpc_local_planner_amd/csrc/mpc_scan_cast.hpp.
  *
  * The functions live in the same library as include/mpc_hip.h's and are built with it; they are declared here, apart from that header, whose set of declarations and
  * mpc_version stay as they are.  Callers that load the library at run time find them with dlsym under the names below.  mpc_last_costmap_ms

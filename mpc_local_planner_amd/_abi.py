@@ -420,6 +420,43 @@ OPEN_HEADERS = {
 }
 
 
+DRIVE_DIFF, DRIVE_OMNI, DRIVE_CAR_STAGE, DRIVE_CAR_REAR = 0, 1, 2, 3      # MPC_DRIVE_* of include/mpc_plant.h
+
+
+class MpcPlantParams(C.Structure):
+    """struct mpc_plant_params (include/mpc_plant.h); field-for-field."""
+    _fields_ = [
+        ("map_origin", C.c_double * 2),
+        ("map_resolution", C.c_double),
+        ("interval", C.c_double),
+        ("wheelbase", C.c_double),
+        ("v_min", C.c_double * 3),
+        ("v_max", C.c_double * 3),
+        ("a_max", C.c_double * 3),
+        ("footprint", (C.c_double * 2) * 16),
+        ("n_footprint", C.c_int32),
+        ("n_substeps", C.c_int32),
+        ("drive", C.c_int32),
+        ("map_size_x", C.c_int32),
+        ("map_size_y", C.c_int32),
+        ("block_threshold", C.c_int32),
+        ("unknown_blocks", C.c_int32),
+        ("outside_blocks", C.c_int32),
+    ]
+
+
+# ---- include/mpc_plant.h
+# s, B, map, params, cmd, pool, self_index, pose, vel, stall, info
+_PLANT = (_rc, [_p, _i, _p, C.POINTER(MpcPlantParams), _p, C.POINTER(MpcPool), _p, _p, _p, _p, _p])
+
+PLANT_PROTOTYPES = {
+    "mpc_plant_params_defaults": (None, [C.POINTER(MpcPlantParams), _d, _i, _i]),                # p, map_resolution, map_size_x, map_size_y
+    "mpc_plant_step": _PLANT, "mpc_plant_step_device": _PLANT,
+}
+
+OPEN_HEADERS["mpc_plant.h"] = (PLANT_PROTOTYPES, {"mpc_plant_params": MpcPlantParams, "mpc_pool": MpcPool})
+
+
 def _diag_offdiag(w, dim):
     """a weight given as its diagonal or as a full dim x dim matrix -> (diagonal, off-diagonal terms (0,1)[, (0,2), (1,2)] of the symmetric part)"""
     rows = [list(r) if hasattr(r, "__len__") else None for r in w]

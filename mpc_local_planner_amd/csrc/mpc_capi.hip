@@ -18,6 +18,7 @@
 #include "../../include/mpc_costmap_window.h"
 #include "../../include/mpc_costmap_scans.h"
 #include "../../include/mpc_scan_cast.h"
+#include "../../include/mpc_plant.h"
 #include "mpc_core.hpp"
 #include "mpc_problem.hpp"
 #include "mpc_launch_plan.hpp"
@@ -35,6 +36,7 @@
 #include "mpc_costmap_window.hpp"
 #include "mpc_costmap_scans.hpp"
 #include "mpc_scan_cast.hpp"
+#include "mpc_plant.hpp"
 
 namespace {
 
@@ -1744,6 +1746,96 @@ int mpc_scan_cast(mpc_solver* s, int32_t B, const uint8_t* map, const mpc_cast_p
         const mpc_pool dp = {(int32_t)np, (const int32_t*)d[2], (const double*)d[3], (const double*)d[4], nullptr};
         return mpc_scan_cast_device(s, B, (const uint8_t*)d[0], params, (const double*)d[1], np ? &dp : nullptr, (const int32_t*)d[5], n_beams, (float*)d[6], (int32_t*)d[7],
                                     (int32_t*)d[8]);
+    });
+}
+
+}  // extern "C"
+
+// ---- the plant step of a batch: every robot moved by its command, stalled by the map and the pool (mpc_plant.hpp; declared in include/mpc_plant.h)
+
+// the argument checks of both variants, in the order of rule 7: true with mpc_last_error set when the call is refused; q: the parameters as the rule reads them
+static bool plant_error(const char* who, const mpc_solver* s, const void* map, const mpc_plant_params* p, const void* cmd, const mpc_pool* pool, const void* pose,
+                        mpc::PlantParams& q) {
+    auto pos_finite = [](double v) { return v > 0.0 && std::isfinite(v); };
+    if (!s || !p || !cmd || !pose) return costmap_no(who, "null argument (params, cmd, pose)");
+    if (p->n_substeps < 1 || p->n_substeps > mpc::kPlMaxSubsteps) return costmap_no(who, "n_substeps has to be in [1, 64]");
+    if (!pos_finite(p->interval)) return costmap_no(who, "interval has to be positive and finite");
+    if (p->drive < 0 || p->drive > 3) return costmap_no(who, "drive has to be in [0, 3]");
+    if (p->drive >= MPC_DRIVE_CAR_STAGE && !pos_finite(p->wheelbase)) return costmap_no(who, "wheelbase has to be positive and finite for a car drive");
+    if (p->n_footprint < 0 || p->n_footprint == 1 || p->n_footprint > mpc::kPlMaxFootprint) return costmap_no(who, "n_footprint has to be 0 or in [2, 16]");
+    for (int j = 0; j < p->n_footprint; ++j)
+        if (!std::isfinite(p->footprint[j][0]) || !std::isfinite(p->footprint[j][1])) return costmap_no(who, "a footprint vertex is not finite");
+    memset(&q, 0, sizeof(q));
+    q.map_ox = p->map_origin[0]; q.map_oy = p->map_origin[1]; q.res = p->map_resolution; q.dt = p->interval; q.wheelbase = p->wheelbase;
+    for (int i = 0; i < 3; ++i) { q.v_min[i] = p->v_min[i]; q.v_max[i] = p->v_max[i]; q.a_max[i] = p->a_max[i]; }
+    for (int j = 0; j < p->n_footprint; ++j) { q.fx[j] = p->footprint[j][0]; q.fy[j] = p->footprint[j][1]; }
+    q.nf = p->n_footprint; q.n_sub = p->n_substeps; q.drive = p->drive; q.map_sx = p->map_size_x; q.map_sy = p->map_size_y; q.threshold = p->block_threshold;
+    q.unknown_blocks = p->unknown_blocks ? 1 : 0; q.outside_blocks = p->outside_blocks ? 1 : 0; q.has_map = map ? 1 : 0;
+    if (map) {
+        if (p->map_size_x < 1 || p->map_size_y < 1 || (long long)p->map_size_x * p->map_size_y > 2147483647LL) return costmap_no(who, "bad map size (at least 1 x 1, at most 2^31 - 1 bytes)");
+        if (!pos_finite(p->map_resolution)) return costmap_no(who, "map_resolution has to be positive and finite");
+        if (!std::isfinite(p->map_origin[0]) || !std::isfinite(p->map_origin[1])) return costmap_no(who, "map_origin has to be finite");
+        if (p->block_threshold < 1 || p->block_threshold > 254) return costmap_no(who, "block_threshold has to be in [1, 254]");
+    }
+    if (!mpc::pl_reach(q)) return costmap_no(who, "a footprint edge has to be at most 350 cells of the map");
+    for (int i = 0; i < 3; ++i) {
+        if (!(p->a_max[i] >= 0.0)) return costmap_no(who, "a_max has to be at least 0");
+        if (!(p->v_min[i] <= p->v_max[i])) return costmap_no(who, "v_min has to be at most v_max");
+    }
+    if (pool && pool->P < 0) return costmap_no(who, "pool: P is negative");
+    return costmap_no(who, pool && pool->P > 0 && (!pool->n_vertices || !pool->vertices) ? "pool: n_vertices and vertices are needed with P > 0" : nullptr);
+}
+
+extern "C" {
+
+void mpc_plant_params_defaults(mpc_plant_params* p, double map_resolution, int32_t map_size_x, int32_t map_size_y) {
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->map_resolution = map_resolution;
+    p->interval = 0.1;
+    p->wheelbase = 0.4;
+    for (int i = 0; i < 3; ++i) { p->v_min[i] = -INFINITY; p->v_max[i] = p->a_max[i] = INFINITY; }
+    p->n_footprint = 0;
+    p->n_substeps = 1;
+    p->drive = MPC_DRIVE_DIFF;
+    p->map_size_x = map_size_x; p->map_size_y = map_size_y;
+    p->block_threshold = 254;
+    p->unknown_blocks = 0;
+    p->outside_blocks = 1;
+}
+
+int mpc_plant_step_device(mpc_solver* s, int32_t B, const uint8_t* d_map, const mpc_plant_params* params, const double* d_cmd, const mpc_pool* pool,
+                          const int32_t* d_self_index, double* d_pose, double* d_vel, int32_t* d_stall, int32_t* d_info) {
+    g_err[0] = 0;
+    mpc::PlantArgs a;
+    memset(&a, 0, sizeof(a));
+    if (plant_error("mpc_plant_step", s, d_map, params, d_cmd, pool, d_pose, a.p)) return MPC_EINVAL;
+    if (B <= 0) return MPC_OK;
+    if (const int rc = refused(s, B, REF_MAX_BATCH, "mpc_plant_step")) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    a.map = d_map; a.cmd = d_cmd; a.self_index = d_self_index; a.pose = d_pose; a.vel = d_vel; a.stall = d_stall; a.info = d_info;
+    if (pool && pool->P > 0) a.pool = {pool->P, pool->n_vertices, pool->vertices, pool->radius, nullptr};
+    a.V = s->cfg.max_vertices > 0 ? s->cfg.max_vertices : 1;
+    return costmap_timed_launch(s, mpc::plant_step_kernel, B, mpc::kPlThreads, a);
+}
+
+int mpc_plant_step(mpc_solver* s, int32_t B, const uint8_t* map, const mpc_plant_params* params, const double* cmd, const mpc_pool* pool, const int32_t* self_index,
+                   double* pose, double* vel, int32_t* stall, int32_t* info) {
+    g_err[0] = 0;
+    mpc::PlantParams q;
+    if (plant_error("mpc_plant_step", s, map, params, cmd, pool, pose, q)) return MPC_EINVAL;
+    if (B <= 0) return MPC_OK;
+    if (const int rc = refused(s, B, REF_MAX_BATCH, "mpc_plant_step")) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t nb = (size_t)B, V = s->cfg.max_vertices > 0 ? s->cfg.max_vertices : 1, np = pool && pool->P > 0 ? (size_t)pool->P : 0;
+    // in / out: the pose and the velocity are the state the call advances
+    const mpc::StagePiece pc[10] = {stage_in(map, map ? (size_t)params->map_size_x * params->map_size_y : 0), stage_in(cmd, nb * 24), stage_in(np ? pool->n_vertices : nullptr, np * 4),
+                                    stage_in(np ? pool->vertices : nullptr, np * V * 16), stage_in(np ? pool->radius : nullptr, np * 8), stage_in(self_index, nb * 4),
+                                    stage_inout(pose, nb * 24), stage_inout(vel, nb * 24), stage_out(stall, nb * 4), stage_out(info, nb * 16)};
+    return staged_call(s, "mpc_plant_step", true, true, pc, 10, [&](void** d) -> int {
+        const mpc_pool dp = {(int32_t)np, (const int32_t*)d[2], (const double*)d[3], (const double*)d[4], nullptr};
+        return mpc_plant_step_device(s, B, (const uint8_t*)d[0], params, (const double*)d[1], np ? &dp : nullptr, (const int32_t*)d[5], (double*)d[6], (double*)d[7],
+                                     (int32_t*)d[8], (int32_t*)d[9]);
     });
 }
 

@@ -35,7 +35,7 @@
 //   6. refusals: a null required pointer; n_beams outside 1 .. kScMaxBeams = 4096; map_size_x or map_size_y below 1 or their product above 2^31 - 1; map_resolution or
 //                range_max not positive and finite; map_origin, sensor_pose, angle_min or angle_increment not finite; Rc above kScMaxRc; block_threshold outside
 //                1 .. 254; P < 0, or P > 0 without n_vertices and vertices.
-// Out of scope, and so visible deviations from Stage: no sensor noise, not Stage's own 0.02 m ray resolution, one sensor, the plant is the caller's, marks are not
+// Out of scope, and so visible deviations from Stage: no sensor noise, not Stage's own 0.02 m ray resolution, one sensor, the plant is not moved here (mpc_plant.hpp), marks are not
 // inflated.
 // Every double is produced by + - * /, floor and sqrt in un-fused arithmetic (and cs_sincos' explicit fmas), so a g++ build and the device round alike; a beam's
 // result is a function of its own inputs, so the output depends neither on B, the place in the batch, the order of beams or the run.

@@ -640,6 +640,37 @@ def cast_params_from_ranger(fov_deg, samples, range_max, sensor_pose, map_resolu
     return p
 
 
+STAGE_DRIVES = {"diff": A.DRIVE_DIFF, "omni": A.DRIVE_OMNI, "car": A.DRIVE_CAR_STAGE}
+
+
+def plant_params_from_position(drive, wheelbase, size, origin, interval_sim_ms, map_resolution, map_shape):
+    """struct mpc_plant_params (mpc_plant_step*, BatchSolver.plant_step_device) from the numbers of a Stage `position` block (ex/stage/robots/*.inc: drive, wheelbase --
+    None where the block has none --, size [x y z], origin [x y z yaw]), the world file's interval_sim in milliseconds and the map's geometry, map_shape = (map_size_y,
+    map_size_x).  The footprint is the box origin_xy +- size_xy / 2, counter-clockwise from (-x, -y): for carlike_robot.inc the one printed in its line 16.  drive
+    "car" is Stage's own car (MPC_DRIVE_CAR_STAGE); a drive Stage does not have is ParamNotImplemented, as is an origin with a yaw.  One sub-step of interval_sim per
+    call; the other fields keep the library's defaults, restated here so that reading a robot file needs no library: include/mpc_plant.h states the values."""
+    if drive not in STAGE_DRIVES:
+        raise ParamNotImplemented(f"position: drive \"{drive}\" (diff, omni and car are implemented)")
+    if len(origin) > 3 and float(origin[3]) != 0.0:
+        raise ParamNotImplemented("position: an origin with a yaw (the footprint is the box of size around origin, along the robot's axes)")
+    interval = float(interval_sim_ms) / 1000.0
+    if not interval > 0.0:
+        raise ValueError("interval_sim has to be positive")
+    p = A.MpcPlantParams()
+    p.map_origin[0] = p.map_origin[1] = 0.0
+    p.map_resolution, p.interval = float(map_resolution), interval
+    p.wheelbase = 0.4 if wheelbase is None else float(wheelbase)
+    for i in range(3):
+        p.v_min[i], p.v_max[i], p.a_max[i] = -math.inf, math.inf, math.inf
+    ox, oy, hx, hy = float(origin[0]), float(origin[1]), float(size[0]) / 2, float(size[1]) / 2
+    for j, (x, y) in enumerate(((ox - hx, oy - hy), (ox + hx, oy - hy), (ox + hx, oy + hy), (ox - hx, oy + hy))):
+        p.footprint[j][0], p.footprint[j][1] = x, y
+    p.n_footprint, p.n_substeps, p.drive = 4, 1, STAGE_DRIVES[drive]
+    p.map_size_x, p.map_size_y = int(map_shape[1]), int(map_shape[0])
+    p.block_threshold, p.unknown_blocks, p.outside_blocks = 254, 0, 1
+    return p
+
+
 def static_layer_costs(occupancy, lethal_threshold=100, unknown_cost_value=-1, track_unknown_space=True, trinary_costmap=True):
     """costmap_2d::StaticLayer::interpretValue in numpy (restated from costmap_2d's published static_layer.cpp): a map server's occupancy values (-1 unknown,
     0 .. 100) -> the costmap bytes mpc_costmap_window's map holds.  The value is read as an unsigned char, as the layer does: the unknown value is 255 with

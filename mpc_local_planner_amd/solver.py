@@ -13,7 +13,8 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._abi import MpcCastParams, MpcClusterParams, MpcConfig, MpcLineParams, MpcCycleParams, MpcEvalOut, MpcObstacles, MpcPlanParams, MpcPool, MpcPoolParams, MpcScanParams, MpcWindowParams, MPC_OK
+from ._abi import (MpcCastParams, MpcClusterParams, MpcConfig, MpcLineParams, MpcCycleParams, MpcEvalOut, MpcObstacles, MpcPlanParams, MpcPlantParams, MpcPool, MpcPoolParams, MpcScanParams,
+                   MpcWindowParams, MPC_OK)
 
 
 class MpcError(RuntimeError):
@@ -603,6 +604,58 @@ class BatchSolver:
         cp = None if pool is None else MpcPool(int(pool[0]), *((tuple(a or None for a in pool[1:4]) + (None,) * 4)[:4]))
         self._check(self._lib.mpc_scan_cast_device(self._h, int(B), _dev(map_cost), C.byref(params), _dev(robot_pose), None if cp is None else C.byref(cp), _dev(self_index),
                                                    int(n_beams), _floats(ranges), _dev(hit), _dev(info)))
+
+    def plant_params(self, map_resolution, map_shape, **fields) -> MpcPlantParams:
+        """mpc_plant_params with the library's defaults (mpc_plant_params_defaults) for a map of map_shape = (map_size_y, map_size_x) cells, then the given fields
+        (map_origin as a pair, v_min / v_max / a_max as triples; footprint as up to 16 (x, y) pairs in the robot frame, which sets n_footprint too unless it is given)"""
+        fields = dict(fields)
+        if "footprint" in fields:
+            pts = [(float(x), float(y)) for x, y in fields["footprint"]]
+            if len(pts) > 16:
+                raise ValueError("mpc_plant_params holds a footprint of at most 16 vertices")
+            fields.setdefault("n_footprint", len(pts))
+            fields["footprint"] = ((C.c_double * 2) * 16)(*((C.c_double * 2)(*q) for q in pts))
+        sized = {"map_origin": 2, "v_min": 3, "v_max": 3, "a_max": 3}
+        fields = {k: (C.c_double * sized[k])(*map(float, v)) if k in sized else v for k, v in fields.items()}
+        return _params("mpc_plant_params", MpcPlantParams,
+                       lambda p: self._lib.mpc_plant_params_defaults(p, float(map_resolution), int(map_shape[1]), int(map_shape[0])), fields)
+
+    def plant_step(self, params: MpcPlantParams, cmd, pose, map_cost=None, pool=None, self_index=None, vel=None):
+        """Every robot moved by its command for params.n_substeps sub-steps of params.interval seconds, stalled where its footprint's outline would meet the map or a
+        body of the pool (mpc_plant_step, include/mpc_plant.h).  cmd (B, 3) = Commands.cmd; pose (B, 3); map_cost: uint8 (map_size_y, map_size_x) in costmap values, or
+        None for no map test; pool = (n_vertices (P,), vertices (P, V, 2)[, radius (P,)]) as scan_cast takes it, or None; self_index (B,): the pool entry that is the
+        robot itself (None: none); vel (B, 3): the body velocity kept between calls, or None to start every call at the commanded velocity.  Nothing given is written.
+        Returns (pose (B, 3), vel (B, 3) or None, stall (B,) = blocked sub-steps, info (B, 4) = sub-steps moved, first blocked sub-step, its reason (-4 heading, -3 off
+        the map, -2 the map, p a pool entry), the lowest edge that shows it)."""
+        pose = np.array(pose, dtype=np.float64).reshape(-1, 3)
+        B, V = pose.shape[0], max(1, int(self.cfg.max_vertices))
+        cmd = _as_f64(cmd, (B, 3))
+        vel = None if vel is None else np.array(_as_f64(vel, (B, 3)))
+        m = None
+        if map_cost is not None:
+            m = np.ascontiguousarray(map_cost, dtype=np.uint8)
+            if m.shape != (params.map_size_y, params.map_size_x):
+                raise ValueError(f"map_cost has shape {m.shape}, params say {(params.map_size_y, params.map_size_x)}")
+        cp = None
+        if pool is not None:
+            pnv = np.ascontiguousarray(pool[0], dtype=np.int32).reshape(-1)
+            P = int(pnv.shape[0])
+            pv = _as_f64(pool[1], (P, V, 2))
+            pr = _as_f64(pool[2], (P,)) if len(pool) > 2 and pool[2] is not None else None
+            cp = MpcPool(P, *(a.ctypes.data if a is not None and P > 0 else None for a in (pnv, pv, pr)), None)
+        si = _as_i32(self_index, B, "self_index")
+        stall, info = np.zeros(B, np.int32), np.zeros((B, 4), np.int32)
+        self._check(self._lib.mpc_plant_step(self._h, B, _addr(m), C.byref(params), _addr(cmd), None if cp is None else C.byref(cp), _addr(si), _addr(pose), _addr(vel),
+                                             _addr(stall), _addr(info)))
+        return pose, vel, stall, info
+
+    def plant_step_device(self, B: int, params: MpcPlantParams, cmd: int, pose: int, map_cost: Optional[int] = None, pool=None, self_index: Optional[int] = None,
+                          vel: Optional[int] = None, stall: Optional[int] = None, info: Optional[int] = None) -> None:
+        """mpc_plant_step_device: the same with device addresses (ints), asynchronous on the solver's stream, behind commands_device, whose `cmd` it takes as it is, and
+        in front of fleet_pool_device, which takes `pose`; pose and vel are advanced in place; pool = (P, n_vertices, vertices[, radius]) with device addresses, or None"""
+        cp = None if pool is None else MpcPool(int(pool[0]), *((tuple(a or None for a in pool[1:4]) + (None,) * 4)[:4]))
+        self._check(self._lib.mpc_plant_step_device(self._h, int(B), _dev(map_cost), C.byref(params), _dev(cmd), None if cp is None else C.byref(cp), _dev(self_index),
+                                                    _dev(pose), _dev(vel), _dev(stall), _dev(info)))
 
     def last_costmap_ms(self) -> float:
         """device milliseconds of the most recent costmap step (mpc_last_costmap_ms), 0 when there has been none"""

